@@ -6,7 +6,11 @@ joints -> 5 part windows (K=80), C=2, d_model=128, depths [2,2,4], 2002 classes,
 fp32, train mode with the reference defaults (dropout 0.1, stochastic attention
 drop).  Inputs are synthetic, resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+
+`--steps K` is the number of timed steps; the result line's `ms_per_step` is their mean wall time.  With
+`--dump-outputs DIR` the last timed step's results are written to DIR as .npy files (`dump_outputs`); every input --
+weights, clips, labels, dropout seeds -- is seeded, so two runs with the same arguments start from the same data.
 
 N>1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), and as a plain `python bench.py --gpus N`,
@@ -540,6 +544,39 @@ def dist_record(dist, world, device_name, step_ms, pin):
             "distinct_processes": len({r["pid"] for r in every})}
 
 
+DUMP_SAMPLE = 1 << 22       # entries per sampled array of --dump-outputs: 16 MB in float32
+
+
+def dump_outputs(model, step, out_dir):
+    """--dump-outputs DIR: what the last timed train step handed its caller, as DIR/<name>.npy --
+    loss.npy (float32, the step's mean loss), correct.npy (float64, correctly classified clips), and of the trainable
+    parameters in `named_parameters()` order, flattened and concatenated: params.npy (after the AdamW update) and
+    grads.npy (the step's gradients), both float32.  When there are more than DUMP_SAMPLE parameter entries, both hold
+    the same fixed sample of them: entries numpy.random.default_rng(0).choice(N, DUMP_SAMPLE, replace=False), sorted
+    (a function of N only, so two builds of the same model dump the same entries).  At most ~32 MB in all.
+    Call after the timed region; it synchronises and copies to the host."""
+    import numpy as np
+    ps = [p for p in model.parameters() if p.requires_grad]
+    n = sum(p.numel() for p in ps)
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        idx_dev = torch.from_numpy(idx).to(ps[0].device)
+
+    def flat(ts):
+        v = torch.cat([t.detach().reshape(-1).float() for t in ts])
+        return (v if idx is None else v[idx_dev]).cpu().numpy()
+    arrays = {
+        "loss": np.asarray(float(step.loss), dtype=np.float32),
+        "correct": np.asarray(float(step.correct), dtype=np.float64),
+        "params": flat(ps),
+        "grads": flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in ps]),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def dry_run(args, json_fd):
     """HWGAT_BENCH_DRYRUN=1: the launcher / rendezvous / max-over-ranks / one-JSON-line plumbing on the gloo
     backend with no model and no GPU (tests/test_dist_cpu.py); `value` is meaningless."""
@@ -598,7 +635,12 @@ def main():
     ap.add_argument("--from-host", action="store_true",
                     help="feed every step from host samples through collate.PinnedBatcher (pinned staging + async H2D): "
                          "the PCIe-inclusive rate DESIGN.md quotes; never the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, correct count, updated "
+                         "parameters and gradients, a fixed sample of the latter two) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1: ms_per_step is the mean over the timed steps")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, sys.argv[1:])         # nothing above or in there touches the GPU
@@ -723,6 +765,8 @@ def main():
         run_step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                          # before any later step changes the weights
+        dump_outputs(model, step, args.dump_outputs)
     if graph_timers:                                             # the same kernels, launched one by one, with events
         HF.TIMERS = store
         for _ in range(2):

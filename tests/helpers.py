@@ -121,6 +121,41 @@ def grad_digest_check(named_grads, fx, prefix, tol):
     return worst
 
 
+def reference_structure(fx, tag):
+    """[(key, shape, dtype, is_parameter, requires_grad)] of a reference `Model` state_dict, in its order, from
+    tests/golden/checkpoint_ref.npz (make_fixtures_checkpoint.py)"""
+    keys, ndim, dims = fx[tag + ".keys"], fx[tag + ".ndim"], fx[tag + ".dims"]
+    grad = dict(zip(fx[tag + ".params"].tolist(), fx[tag + ".requires_grad"].tolist()))
+    out, at = [], 0
+    for k, n, dt in zip(keys.tolist(), ndim.tolist(), fx[tag + ".dtypes"].tolist()):
+        out.append((k, tuple(int(d) for d in dims[at:at + n]), getattr(torch, dt), k in grad, grad.get(k, False)))
+        at += n
+    return out
+
+
+def reference_standin(fx, tag, seed=0):
+    """an nn.Module with exactly the parameters and buffers of the reference `Model` recorded under `tag` (names,
+    order, shapes, dtypes, requires_grad; derived buffers with the reference's values, parameters seeded random):
+    what state_dict / load_state_dict / AdamW see of the reference class, without its source"""
+    g = torch.Generator().manual_seed(seed)
+    root = torch.nn.Module()
+    for key, shape, dtype, is_param, requires_grad in reference_structure(fx, tag):
+        *path, leaf = key.split(".")
+        mod = root
+        for part in path:
+            if not hasattr(mod, part):
+                mod.add_module(part, torch.nn.Module())
+            mod = getattr(mod, part)
+        if is_param:
+            mod.register_parameter(leaf, torch.nn.Parameter((torch.randn(shape, generator=g) * 0.02).to(dtype),
+                                                            requires_grad=requires_grad))
+        else:
+            mod.register_buffer(leaf, torch.from_numpy(np.array(fx[f"{tag}.buf.{key}"])).to(dtype))
+    assert list(root.state_dict()) == fx[tag + ".keys"].tolist()
+    assert [n for n, _ in root.named_parameters()] == fx[tag + ".params"].tolist()
+    return root
+
+
 def hgate_oracle_from_fixture(fx, dtype=torch.float32):
     """(OracleHGAT, params, cfg) of a tests/golden/hgate_*.npz fixture"""
     from oracle import hgat_oracle as OH

@@ -221,11 +221,13 @@ def _run_bench(extra_env, *argv):
 
 
 @pytest.mark.timeout(300)
-def test_bench_parent_spawns_ranks_and_relays_one_json_line():
+def test_bench_parent_spawns_ranks_and_relays_one_json_line(tmp_path):
     """`python bench.py --gpus 2` with no launcher: the parent starts 2 rank processes (gloo dry run: no model, no
     GPU), relays rank 0's line, and reports the launcher-visible fields (n_gpus, global batch = 64 * N)."""
     import json
-    res = _run_bench({}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    empty_sysfs = tmp_path / "sys"                          # no KFD topology, whatever the host has
+    empty_sysfs.mkdir()
+    res = _run_bench({"HWGAT_BENCH_SYSFS": str(empty_sysfs)}, "--gpus", "2", "--steps", "3", "--warmup", "1")
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout
@@ -238,7 +240,7 @@ def test_bench_parent_spawns_ranks_and_relays_one_json_line():
     assert d["backend"] == "gloo" and d["world_size_seen"] == 2 and d["distinct_processes"] == 2
     assert d["devices"] == ["dry-run device of rank 0", "dry-run device of rank 1"]
     assert d["step_ms_min"] < d["step_ms_max"]
-    assert len(d["cpu_pin"]) == 2 and all(p["pinned"] is False for p in d["cpu_pin"])   # no KFD topology in this container
+    assert len(d["cpu_pin"]) == 2 and all(p["pinned"] is False for p in d["cpu_pin"])   # no KFD topology: not pinned
 
 
 def _fake_sysfs(root, gpus, cpulists):
