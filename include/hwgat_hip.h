@@ -45,8 +45,9 @@ extern "C" {
  *   3000  round 3: see INTEGRATION.md section 3
  *   4000  round 4: every entry point with a dropout seed takes `const uint32_t* seed_base` in front of `stream`;
  *         hwgat_seed_set / hwgat_seed_advance; hwgat_is_lab_build; hwgat_blk_attn_*_drop, hwgat_band_attn_*_drop;
- *         hwgat_ln_bwd_det, hwgat_linear_tn_*_det (bit-reproducible parameter gradients) */
-#define HWGAT_ABI_VERSION 4000
+ *         hwgat_ln_bwd_det, hwgat_linear_tn_*_det (bit-reproducible parameter gradients)
+ *   4001  hwgat_aug_hand_fill(_ws_bytes), hwgat_aug_resample: device-side train / eval transforms (additions only) */
+#define HWGAT_ABI_VERSION 4001
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -390,6 +391,44 @@ int hwgat_weight_prep(const hwgat_prep_entry* table, int n, int total_blocks, in
 
 /* the dropout mask the fused kernels use: out[i] = keep(seed, i) ? 1/(1-p) : 0 */
 int hwgat_dropout_mask_f32(float* out, int64_t n, uint32_t seed, float p, const uint32_t* seed_base, void* stream);
+
+/* ---- device-side train / val-test transforms (reference hwgat/configs.py:93-108; host half: sl-hwgat_amd/augment.py).
+ * A batch of n_clips ragged raw clips is packed frame after frame: x (total_frames, J, C) fp32, C in {2, 3}, clip i
+ * owning frames [clip_off[i], clip_off[i+1]) (clip_off: n_clips + 1 device int32, clip_off[0] = 0,
+ * clip_off[n_clips] <= total_frames).
+ *
+ * hwgat_aug_hand_fill: KeypointMasking's zeroing + HandCorrection (dataTransform.py:236-253, 328-403) in place on x.
+ *   masked   (total_frames) device uint8, 1 = the frame's hand joints are zeroed first; NULL = no masking (eval)
+ *   hands    HOST int32[6] = {left first joint, left end joint, left wrist, right first, right end, right wrist}; two
+ *            disjoint ranges of at most 32 / C joints, wrists outside both
+ *   per (clip, hand): "present" = any coordinate of the hand's joints is non-zero (and the frame is not masked).  No
+ *   present frame: every frame takes its wrist.  Otherwise frames before the first / after the last present frame take
+ *   their wrist, and with >= 3 present frames every absent frame in between takes the value at that frame of the
+ *   interpolating quadratic spline (scipy splrep(k=2, s=0) / splev) through the present frames, per joint and
+ *   coordinate, solved in fp64 and rounded to fp32; with fewer the gaps stay zero (the reference's bare except).
+ *   max_frames >= every clip length, <= HWGAT_AUG_MAX_FRAMES (LDS: 12 bytes per frame);
+ *   ws: device workspace of >= hwgat_aug_hand_fill_ws_bytes(total_frames) bytes (fp64 elimination columns);
+ *   tap: NULL, or (total_frames, J, C) fp64 receiving the unrounded spline values at the elements the spline writes.
+ * hwgat_aug_resample: out (n_clips, src_len, J_out, C) fp32 =
+ *   flip(rotate(shear(normalise(x[clip_off[b] + src[b][t], gather[k]])))) per clip b, in fp64 after a normalisation in
+ *   fp32 (as the reference computes it), one rounding to fp32 at the end
+ *   src      (n_clips, src_len) device int32 frame map into the clip (TemporalAugmentation + TemporalSample composed)
+ *   gather   (J_out) device int32 raw joint per output slot (the 64-slot WindowCreate table: parts.part_table(29)),
+ *            or NULL with J_out = J
+ *   prm      (n_clips, HWGAT_AUG_NPRM) device fp64 per clip: [0..2] left_top (fp32 values), [3] edge_dist (fp32
+ *            value), [4..6] shear origin, [7] shear, [8..10] rotation origin, [11..19] rotation matrix M, row-major
+ *            3x3, applied as x @ M (C = 2: its upper-left 2x2), [20] flip (x0 -> 1 - x0) if non-zero, [21] non-zero:
+ *            the flip is taken in fp32 of the rounded value (TemporalSample padded the clip into an fp32 buffer).
+ *            Coordinates past C of the 3-vectors are ignored.  Eval: zero origins and shear, M = I, no flip. */
+#define HWGAT_AUG_NPRM 24
+#define HWGAT_AUG_MAX_FRAMES 4096
+int64_t hwgat_aug_hand_fill_ws_bytes(int64_t total_frames);
+int hwgat_aug_hand_fill(float* x, const int32_t* clip_off, const uint8_t* masked, int n_clips, int64_t total_frames,
+                        int max_frames, int J, int C, const int32_t* hands, void* ws, int64_t ws_bytes, double* tap,
+                        void* stream);
+int hwgat_aug_resample(const float* x, const int32_t* clip_off, const int32_t* src, const double* prm,
+                       const int32_t* gather, float* out, int n_clips, int src_len, int J, int J_out, int C,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,9 @@ _SIGS = {
     "hwgat_linear_tn_bf16_ws": [_P, _P, _P, _P, _L, _I, _I, _P, _L, _P],
     "hwgat_transpose_f32": [_P, _P, _I, _I, _P],
     "hwgat_dropout_mask_f32": [_P, _L, _U, _F, _P, _P],
+    "hwgat_aug_hand_fill_ws_bytes": [_L],
+    "hwgat_aug_hand_fill": [_P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _L, _P, _P],
+    "hwgat_aug_resample": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 _lib = None
 
