@@ -46,8 +46,9 @@ extern "C" {
  *   4000  round 4: every entry point with a dropout seed takes `const uint32_t* seed_base` in front of `stream`;
  *         hwgat_seed_set / hwgat_seed_advance; hwgat_is_lab_build; hwgat_blk_attn_*_drop, hwgat_band_attn_*_drop;
  *         hwgat_ln_bwd_det, hwgat_linear_tn_*_det (bit-reproducible parameter gradients)
- *   4001  hwgat_aug_hand_fill(_ws_bytes), hwgat_aug_resample: device-side train / eval transforms (additions only) */
-#define HWGAT_ABI_VERSION 4001
+ *   4001  hwgat_aug_hand_fill(_ws_bytes), hwgat_aug_resample: device-side train / eval transforms (additions only)
+ *   4002  hwgat_pwin_attn_{fwd,bwd}(_drop): HWGATE part-window attention for window sizes 1..32 (additions only) */
+#define HWGAT_ABI_VERSION 4002
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -166,6 +167,30 @@ int hwgat_win_attn_fwd_drop(const void* qkv, void* o, const uint32_t* maskbits, 
 int hwgat_win_attn_bwd_drop(const void* qkv, const void* dO, void* dqkv, const uint32_t* maskbits,
                             const float* thr, int B, int F, int nW, int nH, int hd, int shifted,
                             int dtype, uint32_t drop_seed, float drop_p, const uint32_t* seed_base, void* stream);
+
+/* ---- HWGATE part-window attention with a general window size W (1 <= W <= 32; W = 16 models use the entries
+ * above).  A window is joints [wi W, (wi+1) W) of the frame pair (2 fi, 2 fi + 1), after the roll by one frame in
+ * odd blocks (`shifted`): n = 2 W tokens, slot t = tp W + joint (HWGATE.py:30-38).  Same semantics as
+ * hwgat_win_attn_*: the train-mode threshold drop over the n raw logits (thr, or NULL for eval), the adjacency and
+ * shift masks, the "== 0 -> -10000" fill, the softmax over the n keys, attention dropout.
+ *   qkv      (B, F, K, 3, nH, hd) `dtype`, o / dO (B, F, K, nH, hd), dqkv like qkv; K = nW W, F even, hd in {32, 64}
+ *   maskbits (2, nW, n) uint64: bit j of word [s][w][i] = key slot j visible to query slot i of part window w;
+ *            s=0 adjacency only, s=1 adjacency AND the last-slot same-frame mask (the last frame pair of a shifted
+ *            block, HWGATE.py:169-187).  Bits >= n are ignored.
+ * Attention dropout hashes the element index of the reference's (B f nW, nH, n, n) attention tensor:
+ * hwgat_dropout_mask_f32(out, B (F/2) nW nH n^2, drop_seed, drop_p) is the mask.  drop_p > 0 needs thr.
+ * No atomics: forward and backward are bit-reproducible.  HWGAT_ESHAPE for W outside 1..32, K % W != 0, odd F,
+ * hd not in {32, 64}. */
+int hwgat_pwin_attn_fwd(const void* qkv, void* o, const uint64_t* maskbits, const float* thr, int B, int F, int K,
+                        int W, int nH, int hd, int shifted, int dtype, void* stream);
+int hwgat_pwin_attn_bwd(const void* qkv, const void* dO, void* dqkv, const uint64_t* maskbits, const float* thr,
+                        int B, int F, int K, int W, int nH, int hd, int shifted, int dtype, void* stream);
+int hwgat_pwin_attn_fwd_drop(const void* qkv, void* o, const uint64_t* maskbits, const float* thr, int B, int F,
+                             int K, int W, int nH, int hd, int shifted, int dtype, uint32_t drop_seed, float drop_p,
+                             const uint32_t* seed_base, void* stream);
+int hwgat_pwin_attn_bwd_drop(const void* qkv, const void* dO, void* dqkv, const uint64_t* maskbits, const float* thr,
+                             int B, int F, int K, int W, int nH, int hd, int shifted, int dtype, uint32_t drop_seed,
+                             float drop_p, const uint32_t* seed_base, void* stream);
 
 /* ---- (f) rank 3, sibling model HGATE: fused BLOCK attention (MSA.forward of
  * hwgat/models/HGATE.py:84-108) with block_partition / block_reverse / torch.roll

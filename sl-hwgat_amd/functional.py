@@ -70,6 +70,32 @@ def mask_bits(adj: torch.Tensor) -> torch.Tensor:
     return bits.contiguous()
 
 
+def pwin_mask_bits(adj: torch.Tensor, window_size: int) -> torch.Tensor:
+    """(nW, 2W, 2W) 0/1 adjacency of an HWGATE with window size W <= 32 (reference model_params.py:373-392) -> the
+    (2, nW, 2W) int64 rows `hwgat_pwin_attn_*` consume: bit j of row [s][w][i] = key slot j visible to query slot i
+    (slot = tp * W + joint), [0] adjacency only, [1] adjacency AND the last-slot same-frame mask (HWGATE.py:169-187)."""
+    W = int(window_size)
+    a = adj.detach().to("cpu", torch.float32)
+    if not 1 <= W <= 32:
+        raise NotImplementedError(f"window_size {W}: the part-window attention kernels take windows of at most 32 "
+                                  f"joints (2 x 32 = 64 tokens, one key per lane)")
+    n = 2 * W
+    if a.dim() != 3 or a.shape[1:] != (n, n):
+        raise ValueError(f"adjacency must be (nW, {n}, {n}) (temporal_patch_size 2 x window {W}), got {tuple(a.shape)}")
+    if not bool(((a == 0) | (a == 1)).all()):
+        raise ValueError("adjacency must be a 0/1 matrix")
+    live = a != 0
+    tp = torch.arange(n) // W
+    same_frame = tp[:, None] == tp[None, :]
+    rows = []
+    for m in (live, live & same_frame):
+        acc = torch.zeros(a.shape[0], n, dtype=torch.int64)
+        for j in range(n):                       # OR of single bits: bit 63 (W = 32) is the sign bit of the int64 word
+            acc |= m[..., j].to(torch.int64) << j
+        rows.append(acc)
+    return torch.stack(rows).contiguous()
+
+
 def blk_mask_bits(adj: torch.Tensor, n_joints: int) -> torch.Tensor:
     """(2*KJ, 2*KJ) 0/1 block adjacency of HGATE (reference model_params.py:460-476) -> the (2,64,2)
     uint32 rows `hwgat_blk_attn_*` consume.  Query slot i = tp*32 + joint; word [s][i][kt] has bit j
@@ -172,36 +198,52 @@ def layer_norm(x, gamma, beta):
 # ---------------------------------------------------------------- attention
 class _WinAttn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, bits, thr, n_heads, shifted, drop):
+    def forward(ctx, qkv, bits, thr, n_heads, shifted, drop, kind="win"):
         B, F, K, d3 = qkv.shape
         d = d3 // 3
         o = torch.empty(B, F, K, d, device=qkv.device, dtype=qkv.dtype)
-        attn_fwd("win", qkv, o, bits, thr, n_heads, shifted, drop)
+        attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop)
         ctx.save_for_backward(qkv, bits, thr)
-        ctx.cfg = (n_heads, int(shifted), drop)
+        ctx.cfg = (n_heads, int(shifted), drop, kind)
         return o
 
     @staticmethod
     def backward(ctx, do):
         qkv, bits, thr = ctx.saved_tensors
-        n_heads, shifted, drop = ctx.cfg
+        n_heads, shifted, drop, kind = ctx.cfg
         do = do.contiguous()
         dqkv = torch.empty_like(qkv)
-        attn_bwd("win", qkv, do, dqkv, bits, thr, n_heads, shifted, drop)
-        return dqkv, None, None, None, None, None
+        attn_bwd(kind, qkv, do, dqkv, bits, thr, n_heads, shifted, drop)
+        return dqkv, None, None, None, None, None, None
 
 
 def _attn_drop(kind, thr, drop):
     """(seed, p, seed_base) of the attention dropout (reference HWGATE.py:78,112, HGATE.py:78,106, WGATE.py:81,103) or None"""
     if drop is None or float(drop[1]) <= 0.0:
         return None
-    if kind == "win" and thr is None:
+    if kind in ("win", "pwin") and thr is None:
         raise ValueError("attention dropout is a train-mode operation: it needs the train-mode threshold tensor")
     return int(drop[0]) & 0xFFFFFFFF, float(drop[1]), (drop[2] if len(drop) > 2 else None)
 
 
+def _pwin_shape(o, bits, n_heads):
+    """(B, F, K, W, head_dim) of a 'pwin' launch; W comes from the (2, nW, 2W) mask rows"""
+    B, F, K, d = o.shape
+    if bits.dtype != torch.int64 or bits.dim() != 3 or bits.shape[0] != 2 or bits.shape[2] % 2:
+        raise ValueError("'pwin' attention needs the (2, nW, 2W) int64 rows of functional.pwin_mask_bits")
+    W = bits.shape[2] // 2
+    if bits.shape[1] * W != K:
+        raise ValueError(f"mask rows are for {bits.shape[1]} windows of {W} joints, activations have {K} joints")
+    hd = d // n_heads
+    if hd not in (32, 64):
+        raise NotImplementedError(f"head_dim {hd}: the part-window attention kernels for window sizes other than 16 "
+                                  f"take head_dim 32 or 64")
+    return B, F, K, W, hd
+
+
 def attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop=None):
-    """launch the attention forward of a model family: 'win' = HWGATE part windows, 'blk' = HGATE blocks, 'band' = WGATE.
+    """launch the attention forward of a model family: 'win' = HWGATE part windows (W = 16), 'pwin' = HWGATE part
+    windows of any other size W <= 32 (W from `bits`, functional.pwin_mask_bits), 'blk' = HGATE blocks, 'band' = WGATE.
     `drop` = (seed, p) or (seed, p, seed_base): attention dropout ('win', train mode only)"""
     B, F, K, d = o.shape
     drop = _attn_drop(kind, thr, drop)
@@ -211,6 +253,14 @@ def attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop=None):
     elif kind == "win":
         call("hwgat_win_attn_fwd", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B, F, K // 16, n_heads, d // n_heads,
              int(shifted), dtype_code(qkv), stream())
+    elif kind == "pwin":
+        B_, F_, K_, W, hd = _pwin_shape(o, bits, n_heads)
+        if drop is not None:
+            call("hwgat_pwin_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads, hd,
+                 int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
+        else:
+            call("hwgat_pwin_attn_fwd", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads, hd, int(shifted),
+                 dtype_code(qkv), stream())
     elif kind == "blk":
         assert thr is None, "HGATE has no train-mode threshold"
         if drop is not None:
@@ -240,6 +290,14 @@ def attn_bwd(kind, qkv, do, dqkv, bits, thr, n_heads, shifted, drop=None):
     elif kind == "win":
         call("hwgat_win_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B, F, K // 16, n_heads,
              d // n_heads, int(shifted), dtype_code(qkv), stream())
+    elif kind == "pwin":
+        B_, F_, K_, W, hd = _pwin_shape(do, bits, n_heads)
+        if drop is not None:
+            call("hwgat_pwin_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads,
+                 hd, int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
+        else:
+            call("hwgat_pwin_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads, hd,
+                 int(shifted), dtype_code(qkv), stream())
     elif kind == "blk":
         if drop is not None:
             call("hwgat_blk_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B, F, K, n_heads, d // n_heads,
@@ -316,6 +374,13 @@ def window_attention(qkv, bits, thr, n_heads, shifted, drop=None):
     probabilities (reference HWGATE.py:112), train mode only."""
     drop = _attn_drop("win", thr, drop)
     return _WinAttn.apply(qkv.contiguous(), bits, thr, n_heads, shifted, drop)
+
+
+def part_window_attention(qkv, bits, thr, n_heads, shifted, drop=None):
+    """HWGATE with a window size W != 16: qkv (B,F,K,3d) -> o (B,F,K,d); `bits` = functional.pwin_mask_bits(adj, W)
+    (on the device), the rest as window_attention."""
+    drop = _attn_drop("pwin", thr, drop)
+    return _WinAttn.apply(qkv.contiguous(), bits, thr, n_heads, shifted, drop, "pwin")
 
 
 # ---------------------------------------------------------------- merge

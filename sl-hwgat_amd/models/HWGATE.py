@@ -38,20 +38,21 @@ def _sinusoid(max_len, d):
     return pe.view(1, max_len, 1, d)
 
 
-def _last_slot_mask(frames, n_windows):
+def _last_slot_mask(frames, n_windows, window_size=16):
     """value of the reference's `attn_mask` buffer (HWGATE.py:169-187): all
     ones except the last temporal slot, which is block-diagonal per frame."""
-    f = frames // 2
-    m = torch.ones(f, n_windows, 32, 32)
-    blk = torch.zeros(32, 32)
-    blk[:16, :16] = 1
-    blk[16:, 16:] = 1
+    f, n = frames // 2, 2 * window_size
+    m = torch.ones(f, n_windows, n, n)
+    blk = torch.zeros(n, n)
+    blk[:window_size, :window_size] = 1
+    blk[window_size:, window_size:] = 1
     m[f - 1] = blk
-    return m.view(f * n_windows, 32, 32)
+    return m.view(f * n_windows, n, n)
 
 
 class Model(nn.Module):
-    _attn_kind = "win"          # part-window attention (hwgat_win_attn_*); HGATE overrides with "blk", WGATE with "band"
+    _attn_kind = "win"          # part-window attention (hwgat_win_attn_*); HGATE overrides with "blk", WGATE with "band";
+                                # an HWGATE with window_size != 16 sets "pwin" on the instance (hwgat_pwin_attn_*)
 
     def __init__(self, kp_dim=26, num_kps=64, temporal_dim=256, num_classes=1000, embed_dim=64,
                  temporal_patch_size=4, pe=False, depths=[2, 2, 6, 2], num_heads=[2, 4, 8, 16],
@@ -62,8 +63,9 @@ class Model(nn.Module):
             # the reference's TemporalMerging doubles the width per stage, which is only
             # consistent with temporal_patch_size == 2 (HWGATE.py:61 vs :312)
             raise NotImplementedError("HWGAT HIP backend supports temporal_patch_size == 2")
-        if window_size != 16:
-            raise NotImplementedError("HWGAT HIP backend supports window_size == 16")
+        if not 1 <= window_size <= 32:
+            raise NotImplementedError(f"window_size {window_size}: the HWGAT HIP backend takes windows of at most 32 "
+                                      f"joints (2 frames x 32 = 64 tokens per window)")
         if not 0.0 <= float(attn_drop_rate) < 1.0:
             raise ValueError("attn_drop_rate must be in [0, 1)")
         if norm_layer is not nn.LayerNorm:
@@ -79,7 +81,10 @@ class Model(nn.Module):
         self.attn_drop_rate = float(attn_drop_rate)          # nn.Dropout on the attention probabilities (HWGATE.py:78,112)
         self.num_layers = n_stage
         self.num_features = int(embed_dim * 2 ** (n_stage - 1))
-        self.n_windows = num_kps // 16
+        self.window_size = int(window_size)
+        self.n_windows = num_kps // window_size
+        if window_size != 16:
+            self._attn_kind = "pwin"                   # W = 16 stays on the "win" kernels, unchanged
 
         self.B = nn.Parameter(torch.normal(0.0, 1.0, (embed_dim // 2, kp_dim)) * 10, requires_grad=False)
         if pe:
@@ -96,6 +101,10 @@ class Model(nn.Module):
                     f"row maps exist for these widths; embed_dim = 64, the reference constructor's default that no "
                     f"reference config uses, would need 64-column instantiations -- INTEGRATION.md section 6) and "
                     f"head_dim in (32, 64, 128)")
+            if self._attn_kind == "pwin" and d // num_heads[i] not in (32, 64):
+                raise NotImplementedError(
+                    f"stage {i}: head_dim {d // num_heads[i]} with window_size {window_size}: the part-window attention "
+                    f"kernels for window sizes other than 16 take head_dim 32 or 64")
             stage = _Slot()
             stage.blocks = nn.ModuleList()
             for j in range(depths[i]):
@@ -108,7 +117,7 @@ class Model(nn.Module):
                 blk.ff = _Slot()
                 blk.ff.fc1 = nn.Linear(d, int(d * ff_ratio))
                 blk.ff.fc2 = nn.Linear(int(d * ff_ratio), d)
-                blk.register_buffer("attn_mask", _last_slot_mask(temporal_dim // 2 ** i, self.n_windows)
+                blk.register_buffer("attn_mask", _last_slot_mask(temporal_dim // 2 ** i, self.n_windows, window_size)
                                     if j % 2 == 1 else None)
                 stage.blocks.append(blk)
             self.layers.append(stage)
@@ -121,10 +130,13 @@ class Model(nn.Module):
                 nn.init.zeros_(m.bias)
 
         if adj_mat is None:
-            adj_mat = torch.ones(self.n_windows, 32, 32)
+            adj_mat = torch.ones(self.n_windows, 2 * window_size, 2 * window_size)
         self.adj_mat = adj_mat
         # compact bit rows derived from adjacency + shift structure; not part of state_dict
-        self.register_buffer("_mask_bits", HF.mask_bits(adj_mat), persistent=False)
+        bits = HF.mask_bits(adj_mat) if self._attn_kind == "win" else HF.pwin_mask_bits(adj_mat, window_size)
+        if bits.shape[1] != self.n_windows:
+            raise ValueError(f"adjacency has {bits.shape[1]} windows, num_kps / window_size = {self.n_windows}")
+        self.register_buffer("_mask_bits", bits, persistent=False)
         self.part_index: Optional[torch.Tensor] = None           # set by use_part_table()
         self.activation_dtype = torch.float32
         self.threshold_override: Optional[List[float]] = None    # tests: inject train thresholds
@@ -251,7 +263,7 @@ class Model(nn.Module):
         for i, stage in enumerate(self.layers):
             for j, blk in enumerate(stage.blocks):
                 thr = None
-                if self.training and self._attn_kind == "win":     # HGATE has no threshold drop
+                if self.training and self._attn_kind in ("win", "pwin"):     # HGATE / WGATE have no threshold drop
                     if self.threshold_override is not None:
                         thr = torch.full((1,), float(self.threshold_override[k]), device=x.device)
                     else:
