@@ -47,8 +47,10 @@ extern "C" {
  *         hwgat_seed_set / hwgat_seed_advance; hwgat_is_lab_build; hwgat_blk_attn_*_drop, hwgat_band_attn_*_drop;
  *         hwgat_ln_bwd_det, hwgat_linear_tn_*_det (bit-reproducible parameter gradients)
  *   4001  hwgat_aug_hand_fill(_ws_bytes), hwgat_aug_resample: device-side train / eval transforms (additions only)
- *   4002  hwgat_pwin_attn_{fwd,bwd}(_drop): HWGATE part-window attention for window sizes 1..32 (additions only) */
-#define HWGAT_ABI_VERSION 4002
+ *   4002  hwgat_pwin_attn_{fwd,bwd}(_drop): HWGATE part-window attention for window sizes 1..32 (additions only)
+ *   4003  widths that are odd multiples of 64 (additions only): the NT linears take N % 64 == 0, the TN linears
+ *         N % 64 == K % 64 == 0, the LayerNorm family every d = 64 n <= 1024 */
+#define HWGAT_ABI_VERSION 4003
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -94,8 +96,9 @@ int hwgat_embed_fwd(const float* x, const int32_t* idx, const float* bmat, const
 
 /* ---- LayerNorm over the last axis (HWGATE.py:203, 219, 353), eps 1e-5.
  *   x, y (N, d) `dtype`; gamma, beta (d) fp32; mean, rstd (N) fp32 (saved
- *   for backward).  d in {128, 256, 512, 1024}.  y may be NULL: statistics only
- *   (the fused linears normalise on the fly from mean/rstd). */
+ *   for backward).  d in {128, 256, 512, 1024}, or (ABI 4003) any other d = 64 n <= 1024 -- 16 lanes per
+ *   row, the same arithmetic; this holds for every LayerNorm entry point below (bwd, _masked, _xn, _det,
+ *   lnpool).  y may be NULL: statistics only (the fused linears normalise on the fly from mean/rstd). */
 int hwgat_ln_fwd(const void* x, const float* gamma, const float* beta, void* y,
                  float* mean, float* rstd, int64_t N, int d, int dtype, void* stream);
 
@@ -287,8 +290,9 @@ int hwgat_unmerge_masked(const void* in, void* out, void* out_masked, int B, int
 /* ---- a-6/a-7/a-8: fp32 Linear layers on f32 MFMA with fused elementwise work.
  * Replaces nn.Linear (HWGATE.py:86,115,131,134) + bias + GELU (:132) + Dropout
  * (:116,:133,:135) + residual adds (:217,:219) forward, and their dX backward.
- *   C[M,N] = pro(A)[M,K] . W[N,K]^T, all fp32 row-major; N % 128 == K % 32 == 0, any M >= 1
- *   (a ragged last 128-row block clamps its loads to row M-1 and guards its stores).
+ *   C[M,N] = pro(A)[M,K] . W[N,K]^T, all fp32 row-major; N % 64 == K % 32 == 0, any M >= 1
+ *   (a ragged last 128-row block clamps its loads to row M-1 and guards its stores).  N % 128 == 64 (ABI 4003) runs
+ *   on 128x64 tiles, every pro / epi code; the _ex statistics / merged store are not built for it (HWGAT_ESHAPE).
  *   pro: 0 none | 1 LayerNorm: (A-mean[m])*rstd[m]*gamma[k]+beta[k] | 2 dropout mask on A
  *        (keep-scale 1/(1-pro_p), element index m*K+k, seed pro_seed)
  *        | 3 folded LayerNorm (hwgat_ln_fold below): A is the un-normalised input, W = W o gamma, gamma = s[N],
@@ -339,7 +343,12 @@ int hwgat_ln_finalize(float* sum_mean, float* sq_rstd, int64_t n, int d, void* s
 /* weight/bias gradient: dW[N,K] += dropmask(A)[M,N]^T . ln(B)[M,K] ; db[N] += colsum(dropmask(A))
  * (db may be NULL).  Accumulates with fp32 atomics across M slices: caller provides zeroed
  * (or to-be-accumulated-into) dW/db.  N % 128 == K % 128 == 0, any M >= 1.  pro_p == 0: no mask.
- * mean != NULL: B is LayerNorm-ed on the fly, (B-mean[m])*rstd[m]*gamma[k]+beta[k]. */
+ * mean != NULL: B is LayerNorm-ed on the fly, (B-mean[m])*rstd[m]*gamma[k]+beta[k].
+ * ABI 4003: N % 64 == K % 64 == 0 with N % 128 or K % 128 non-zero runs on 64x64 dW tiles WITHOUT float atomics, in both
+ * dtypes and every prologue: with a workspace (the _ws / _det entry points; hwgat_linear_tn_{f32,bf16}_ws_bytes and
+ * hwgat_linear_tn_det_bytes return its size, it need not be zeroed) each M split stores its partial tile and one pass
+ * adds the partials in split order -- bit-reproducible, any M; without one (these plain entry points) one block per
+ * tile walks all of M, which is correct but slow for large M. */
 int hwgat_linear_tn_f32(const float* A, const float* B, float* dW, float* db, int64_t M, int N, int K,
                         uint32_t pro_seed, float pro_p, const float* mean, const float* rstd,
                         const float* gamma, const float* beta, const uint32_t* seed_base, void* stream);
@@ -347,7 +356,8 @@ int hwgat_linear_tn_f32(const float* A, const float* B, float* dW, float* db, in
 /* ---- BASELINE config 3: the same two linears with bf16 activations / weights on
  * v_mfma_f32_32x32x16_bf16 (fp32 accumulate).  A, W, C, C2, res, aux are bf16; bias, LN
  * statistics/affine, dW, db stay fp32.  Semantics, prologue/epilogue codes and dropout masks are
- * identical to the fp32 entry points (any M >= 1: a ragged tail gets its own small launch); K % 64 == 0 here. */
+ * identical to the fp32 entry points (any M >= 1: a ragged tail gets its own small launch); K % 64 == 0 here, and the same
+ * N % 64 / 64x64 dW-tile rules (ABI 4003) as the fp32 entry points. */
 int hwgat_linear_nt_bf16(const void* A, const void* W, const float* bias, void* C, int64_t M, int N, int K,
                          int pro, const float* mean, const float* rstd, const float* gamma,
                          const float* beta, uint32_t pro_seed, float pro_p, int epi, const void* res,

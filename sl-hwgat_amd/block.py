@@ -84,6 +84,8 @@ class _FusedBlock(torch.autograd.Function):
         if prep and prep["qkv_f"][0].dtype != dt:
             prep = {}
         fuse = HF.can_fuse_row_stats(x)           # the producing epilogue delivers the LayerNorm statistics
+        if d % 128:
+            fuse = False                          # 128x64 tiles (d % 128 == 64): no statistics epilogue, separate pass
         if deterministic and fuse:
             # Bit-reproducible forward.  The 256-wide-tile kernels (N % 256 == 0) combine a tile's partial row sums in a
             # fixed order and add ONE (sum, sum of squares) per column tile -- and per frame of a merged row -- to the

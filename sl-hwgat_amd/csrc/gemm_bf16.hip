@@ -18,6 +18,7 @@
 #include "common.h"
 #include "fused_ops.h"
 #include "gemm_bf16.h"
+#include "gemm_tn64.h"
 
 namespace {
 
@@ -28,6 +29,9 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 //   K32 x 3 blocks/CU 19.8 ms (vs 20.2) | two-slab register prefetch ring: neutral | 8-wave 256x256: 26.4 ms
 //   | 128x256 (64x128 wave tiles, 2 blocks/CU): 22.0 ms (vs 18.9).
 using NtB64 = TileCfg<2, 2, 2, 2, 64, 2, 8, 8>;
+// 128x64 tile (4 waves x 32x64) for outputs whose width is an odd multiple of 64 (N % 128 == 64), the same kernel body;
+// 54 KB LDS -> 2 blocks / CU.  No row-statistics instantiation (its 32-column staging piece has 4 lanes per row).
+using NtB64N64 = TileCfg<4, 1, 1, 2, 64, 2, 8, 8>;
 
 // A (tile, K-slab) cursor over the work of one persistent block.
 struct SlabIt {
@@ -541,6 +545,31 @@ NtArgsB nt_rows_b(NtArgsB a, int64_t r0, int64_t rows) {
     return a;
 }
 
+// N % 128 == 64: the 128x64 tile over the whole 128-row blocks, then a RAGGED launch for the last M % 128 rows
+int launch_nt_b_n64(const NtArgsB& a, int pro, int epi, hipStream_t st) {
+    const int64_t m_bulk = a.M / 128 * 128;
+    if (m_bulk) {
+        NtArgsB b = a;
+        b.M = m_bulk;
+        int rc;
+        switch (pro) {
+            case PRO_NONE: rc = launch_nt_b<PRO_NONE, NtB64N64>(b, epi, st); break;
+            case PRO_LN_FOLD: rc = launch_nt_b<PRO_NONE, NtB64N64>(b, epi, st, true); break;
+            case PRO_LN: rc = launch_nt_b<PRO_LN, NtB64N64>(b, epi, st); break;
+            case PRO_DROP: rc = launch_nt_b<PRO_DROP, NtB64N64>(b, epi, st); break;
+            default: return HWGAT_EINVAL;
+        }
+        if (rc || m_bulk == a.M) return rc;
+    }
+    const NtArgsB t = nt_rows_b(a, m_bulk, a.M - m_bulk);
+    switch (pro) {
+        case PRO_NONE: return launch_nt_b<PRO_NONE, NtB64N64, true>(t, epi, st);
+        case PRO_LN: return launch_nt_b<PRO_LN, NtB64N64, true>(t, epi, st);
+        case PRO_DROP: return launch_nt_b<PRO_DROP, NtB64N64, true>(t, epi, st);
+        default: return HWGAT_EINVAL;
+    }
+}
+
 }  // namespace
 
 extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float* bias, void* C, int64_t M, int N,
@@ -549,7 +578,7 @@ extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float
                                        void* C2, const void* aux, uint32_t epi_seed, float epi_p, float* stat_sum,
                                        float* stat_sq, int merge_F, int merge_K, const uint32_t* seed_base, void* stream) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return HWGAT_EINVAL;
-    if (N % 128 || K % 64 || ((M + 127) / 128) * (int64_t)(N / 128) > 0x7fffffff) return HWGAT_ESHAPE;   // any M
+    if (N % 64 || K % 64 || ((M + 127) / 128) * (int64_t)(N / 64) > 0x7fffffff) return HWGAT_ESHAPE;   // any M
     if ((pro == PRO_LN || pro == PRO_LN_FOLD) && (!mean || !rstd || !gamma || !beta)) return HWGAT_EINVAL;
     if (pro == PRO_LN_FOLD) {                                      // gamma = s[N], beta = c[N] of hwgat_ln_fold; whole tiles
         if (epi != EPI_BIAS && epi != EPI_BIAS_GELU_DROP && epi != EPI_BIAS_GELU_DROP_G) return HWGAT_EINVAL;
@@ -570,6 +599,10 @@ extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float
               (const bf16_t*)aux, mean, rstd, gamma, beta, M, N, K, pro_seed, epi_seed, pro_p, epi_p, 0, stat_sum, stat_sq, merge_K > 0 ? merge_F : 0, merge_K > 0 ? merge_K : 0};
     a.seed_base = seed_base;
     hipStream_t st = (hipStream_t)stream;
+    if (N % 128) {                                              // N % 128 == 64: the 128x64 tile
+        if (stat) return HWGAT_ESHAPE;
+        return launch_nt_b_n64(a, pro, epi, st);
+    }
     const int64_t m_bulk = M / 128 * 128;                       // ragged token count: bulk launch + RAGGED tail launch
     if (m_bulk != M) {
         if (m_bulk) {
@@ -630,7 +663,10 @@ extern "C" int hwgat_linear_nt_bf16(const void* A, const void* W, const float* b
                                    epi_seed, epi_p, nullptr, nullptr, 0, 0, seed_base, stream);
 }
 
-extern "C" int64_t hwgat_linear_tn_bf16_ws_bytes(int64_t M, int N, int K) { return 4 * hwgat_tn8w_bf16_ws_floats(M, N, K); }
+extern "C" int64_t hwgat_linear_tn_bf16_ws_bytes(int64_t M, int N, int K) {
+    if (hwgat_tn64_takes(N, K)) return hwgat_tn64_ws_bytes(M, N, K);          // 64x64 dW tiles (gemm_tn64.hip)
+    return 4 * hwgat_tn8w_bf16_ws_floats(M, N, K);
+}
 
 // plain operands with a caller-owned workspace: the M-split partial tiles are combined by a fixed-order reduction instead of
 // global atomics (faster, and dW is bit-reproducible); shapes the slab kernel does not take, or a workspace that is too
@@ -638,6 +674,9 @@ extern "C" int64_t hwgat_linear_tn_bf16_ws_bytes(int64_t M, int N, int K) { retu
 extern "C" int hwgat_linear_tn_bf16_ws(const void* A, const void* B, float* dW, float* db, int64_t M, int N, int K,
                                        float* ws, int64_t ws_bytes, void* stream) {
     if (!A || !B || !dW || M <= 0 || N <= 0 || K <= 0) return HWGAT_EINVAL;
+    if (hwgat_tn64_takes(N, K))
+        return hwgat_tn64_run(HWGAT_BF16, A, B, dW, db, M, N, K, 0, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              ws && ws_bytes >= hwgat_tn64_ws_bytes(M, N, K) ? ws : nullptr, ws_bytes, (hipStream_t)stream);
     const int64_t need = hwgat_linear_tn_bf16_ws_bytes(M, N, K);
     if (need == 0 || !ws || ws_bytes < need)
         return hwgat_linear_tn_bf16(A, B, dW, db, M, N, K, 0, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
@@ -733,6 +772,9 @@ static int tn_bf16_impl(const void* A, const void* B, float* dW, float* db, int6
 extern "C" int hwgat_linear_tn_bf16(const void* A, const void* B, float* dW, float* db, int64_t M, int N, int K,
                                     uint32_t pro_seed, float pro_p, const float* mean, const float* rstd,
                                     const float* gamma, const float* beta, const uint32_t* seed_base, void* stream) {
+    if (hwgat_tn64_takes(N, K))                                 // one M split per 64x64 tile, no workspace
+        return hwgat_tn64_run(HWGAT_BF16, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base,
+                              nullptr, 0, (hipStream_t)stream);
     return tn_bf16_impl(A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, DetWs{nullptr, nullptr, 0}, stream);
 }
 
@@ -744,6 +786,9 @@ extern "C" int hwgat_linear_tn_bf16_det(const void* A, const void* B, float* dW,
                                         const float* gamma, const float* beta, const uint32_t* seed_base, float* ws,
                                         int64_t ws_bytes, void* stream) {
     if (!ws || N <= 0 || K <= 0) return HWGAT_EINVAL;
+    if (hwgat_tn64_takes(N, K))
+        return hwgat_tn64_run(HWGAT_BF16, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, ws,
+                              ws_bytes, (hipStream_t)stream);
     const int64_t per = (int64_t)N * K + N;
     const int64_t cap = ws_bytes / 4 / per;
     if (cap < 1) return HWGAT_ESHAPE;

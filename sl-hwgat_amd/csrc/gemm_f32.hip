@@ -30,6 +30,7 @@
 #include "common.h"
 #include "fused_ops.h"
 #include "gemm_f32.h"
+#include "gemm_tn64.h"
 
 namespace {
 
@@ -43,6 +44,10 @@ constexpr int BK_MIN = 16;                                      // K must be a m
 using NtSmall = TileCfg<2, 2, 2, 2>;
 using NtBig = TileCfg<4, 2, 2, 4, 32, 1>;
 using NtK16 = TileCfg<2, 2, 2, 2, 16, 3>;                      // 41 KB LDS -> 3 blocks / CU
+//   NtN64    4x1 waves x (1x2) tiles = 128x64 block, 256 threads, 2 blocks / CU: outputs whose width is an odd multiple
+//            of 64 (N % 128 == 64: stage width 64 / 192 and its qkv, HWGATE embed_dim 64 / 192).  The same kernel body
+//            as the 128x128 tile; only the per-wave tile is 32x64 instead of 64x64.
+using NtN64 = TileCfg<4, 1, 1, 2>;
 
 // RAGGED: the launch covers the last M % 128 rows of a token count that is not a multiple of the tile
 // (HGATE: M = B*F*29).  It is a separate instantiation so that the bulk launch stays exactly the code
@@ -565,6 +570,32 @@ int tile_override() {
     return v;
 }
 
+// N % 128 == 64: the 128x64 tile over the whole 128-row blocks, then a RAGGED launch for the last M % 128 rows
+// (row statistics / merged store are not built for this tile: the caller takes the separate statistics pass)
+int launch_nt_n64(const NtArgs& a, int pro, int epi, hipStream_t st) {
+    const int64_t m_bulk = a.M / 128 * 128;
+    if (m_bulk) {
+        NtArgs b = a;
+        b.M = m_bulk;
+        int rc;
+        switch (pro) {
+            case PRO_NONE: rc = launch_nt<PRO_NONE, NtN64>(b, epi, st); break;
+            case PRO_LN_FOLD: rc = launch_nt<PRO_NONE, NtN64>(b, epi, st, true); break;
+            case PRO_LN: rc = launch_nt<PRO_LN, NtN64>(b, epi, st); break;
+            case PRO_DROP: rc = launch_nt<PRO_DROP, NtN64>(b, epi, st); break;
+            default: return HWGAT_EINVAL;
+        }
+        if (rc || m_bulk == a.M) return rc;
+    }
+    const NtArgs t = nt_rows(a, m_bulk, a.M - m_bulk);
+    switch (pro) {
+        case PRO_NONE: return launch_nt<PRO_NONE, NtN64, true>(t, epi, st);
+        case PRO_LN: return launch_nt<PRO_LN, NtN64, true>(t, epi, st);
+        case PRO_DROP: return launch_nt<PRO_DROP, NtN64, true>(t, epi, st);
+        default: return HWGAT_EINVAL;
+    }
+}
+
 template <int PRO, bool BLN, typename C, bool MF16 = false, bool RAGGED = false>
 int launch_tn(TnArgs a, hipStream_t st) {
     constexpr int TM = C::BK;
@@ -602,7 +633,7 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
                                       float epi_p, float* stat_sum, float* stat_sq, int merge_F, int merge_K,
                                       const uint32_t* seed_base, void* stream) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return HWGAT_EINVAL;
-    if (N % 128 || K % 32 || ((M + 127) / 128) * (int64_t)(N / 128) > 0x7fffffff) return HWGAT_ESHAPE;   // any M
+    if (N % 64 || K % 32 || ((M + 127) / 128) * (int64_t)(N / 64) > 0x7fffffff) return HWGAT_ESHAPE;   // any M
     if ((pro == PRO_LN || pro == PRO_LN_FOLD) && (!mean || !rstd || !gamma || !beta)) return HWGAT_EINVAL;
     if (pro == PRO_LN_FOLD) {                                      // gamma = s[N], beta = c[N] of hwgat_ln_fold; whole tiles
         if (epi != EPI_BIAS && epi != EPI_BIAS_GELU_DROP && epi != EPI_BIAS_GELU_DROP_G) return HWGAT_EINVAL;
@@ -622,6 +653,10 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
     NtArgs a{A, W, bias, C, C2, res, aux, mean, rstd, gamma, beta, M, N, K, pro_seed, epi_seed, pro_p, epi_p, 0, stat_sum, stat_sq, merge_K > 0 ? merge_F : 0, merge_K > 0 ? merge_K : 0};
     a.seed_base = seed_base;
     hipStream_t st = (hipStream_t)stream;
+    if (N % 128) {                                                 // N % 128 == 64: the 128x64 tile
+        if (stat) return HWGAT_ESHAPE;
+        return launch_nt_n64(a, pro, epi, st);
+    }
     // a token count that is not a multiple of the 128-row tile: bulk launch over the aligned rows with the
     // unmodified kernels, then one small RAGGED launch for the last M % 128 rows
     const int64_t m_bulk = M / 128 * 128;
@@ -705,6 +740,7 @@ static bool tn256_takes(int64_t M, int N, int K, float pro_p, const float* mean)
 }
 
 extern "C" int64_t hwgat_linear_tn_f32_ws_bytes(int64_t M, int N, int K) {
+    if (hwgat_tn64_takes(N, K)) return hwgat_tn64_ws_bytes(M, N, K);          // 64x64 dW tiles (gemm_tn64.hip)
     if (M <= 0 || N <= 0 || K <= 0 || !tn256_takes(M, N, K, 0.f, nullptr)) return 0;
     return hwgat_tn256_ws_floats(M, N, K) * 4;
 }
@@ -716,6 +752,9 @@ extern "C" int hwgat_linear_tn_f32_ws(const float* A, const float* B, float* dW,
     if (!A || !B || !dW || M <= 0 || N <= 0 || K <= 0) return HWGAT_EINVAL;
     if (mean && (!rstd || !gamma || !beta)) return HWGAT_EINVAL;
     if (pro_p < 0.f || pro_p >= 1.f) return HWGAT_EINVAL;
+    if (hwgat_tn64_takes(N, K))
+        return hwgat_tn64_run(HWGAT_F32, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base,
+                              ws && ws_bytes >= hwgat_tn64_ws_bytes(M, N, K) ? ws : nullptr, ws_bytes, (hipStream_t)stream);
     if (ws && ws_bytes > 0 && N % 128 == 0 && K % 128 == 0 && tn256_takes(M, N, K, pro_p, mean)) {
         TnArgs a{A, B, dW, db, mean, rstd, gamma, beta, M, N, K, 0, 0, pro_seed, pro_p, 0};
         a.seed_base = seed_base;
@@ -768,6 +807,9 @@ extern "C" int hwgat_linear_tn_f32(const float* A, const float* B, float* dW, fl
                                    int K, uint32_t pro_seed, float pro_p, const float* mean,
                                    const float* rstd, const float* gamma, const float* beta,
                                    const uint32_t* seed_base, void* stream) {
+    if (hwgat_tn64_takes(N, K))                                 // one M split per 64x64 tile, no workspace
+        return hwgat_tn64_run(HWGAT_F32, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base,
+                              nullptr, 0, (hipStream_t)stream);
     return tn_f32_impl(A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, DetWs{nullptr, nullptr, 0}, stream);
 }
 
@@ -814,6 +856,7 @@ static int64_t tn_det_cap(int64_t M, int N, int K) {
     return cap + 8;
 }
 extern "C" int64_t hwgat_linear_tn_det_bytes(int64_t M, int N, int K) {
+    if (hwgat_tn64_takes(N, K)) return hwgat_tn64_ws_bytes(M, N, K);          // 64x64 dW tiles: always split images
     if (M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 128) return 0;
     return tn_det_cap(M, N, K) * ((int64_t)N * K + N) * 4;
 }
@@ -825,6 +868,9 @@ extern "C" int hwgat_linear_tn_f32_det(const float* A, const float* B, float* dW
                                        const float* rstd, const float* gamma, const float* beta,
                                        const uint32_t* seed_base, float* ws, int64_t ws_bytes, void* stream) {
     if (!ws || N <= 0 || K <= 0) return HWGAT_EINVAL;
+    if (hwgat_tn64_takes(N, K))
+        return hwgat_tn64_run(HWGAT_F32, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, ws,
+                              ws_bytes, (hipStream_t)stream);
     const int64_t per = (int64_t)N * K + N;
     const int64_t cap = ws_bytes / 4 / per;
     if (cap < 1) return HWGAT_ESHAPE;

@@ -9,6 +9,7 @@
 // are two-pass in registers (mean, then centred variance) in fp32.
 #include "common.h"
 #include "fused_ops.h"
+#include "layernorm_w64.h"
 
 namespace {
 
@@ -455,6 +456,7 @@ extern "C" int hwgat_ln_fwd(const void* x, const float* gamma, const float* beta
                             float* rstd, int64_t N, int d, int dtype, void* stream) {
     if (!x || !gamma || !beta || !mean || !rstd || N <= 0) return HWGAT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    if (hwgat_lnw_takes(d)) return hwgat_lnw_fwd(x, gamma, beta, y, mean, rstd, N, d, dtype, st);   // d = 64 n, layernorm_w64.hip
     if (dtype == HWGAT_F32) return ln_fwd_t<float>(x, gamma, beta, y, mean, rstd, N, d, st);
     if (dtype == HWGAT_BF16) return ln_fwd_t<bf16_t>(x, gamma, beta, y, mean, rstd, N, d, st);
     return HWGAT_EDTYPE;
@@ -465,6 +467,9 @@ extern "C" int hwgat_ln_bwd(const void* dy, const void* x, const float* mean, co
                             int64_t N, int d, int dtype, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || N <= 0) return HWGAT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    if (hwgat_lnw_takes(d))
+        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, nullptr, dres, dx, dgamma, dbeta, N, d, dtype, nullptr, 0, 0.f, nullptr,
+                             nullptr, nullptr, st);
     if (dtype == HWGAT_F32)
         return dres ? ln_bwd_t<float, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st)
                     : ln_bwd_t<float, false>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st);
@@ -481,6 +486,9 @@ extern "C" int hwgat_ln_bwd_masked(const void* dy, const void* x, const float* m
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !dres || !dx_masked || N <= 0) return HWGAT_EINVAL;
     if (mask_p <= 0.f || mask_p >= 1.f) return HWGAT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    if (hwgat_lnw_takes(d))
+        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, nullptr, dres, dx, dgamma, dbeta, N, d, dtype, dx_masked, mask_seed,
+                             mask_p, nullptr, seed_base, nullptr, st);
     if (dtype == HWGAT_F32)
         return ln_bwd_t<float, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, dx_masked, mask_seed, mask_p, nullptr, nullptr, seed_base);
     if (dtype == HWGAT_BF16)
@@ -496,6 +504,9 @@ extern "C" int hwgat_ln_bwd_xn(const void* dy, const void* x, const float* mean,
     if (!dy || !x || !mean || !rstd || !gamma || !beta || !dx || !dgamma || !dbeta || !dres || !xn || N <= 0) return HWGAT_EINVAL;
     if (dx_masked && (mask_p <= 0.f || mask_p >= 1.f)) return HWGAT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    if (hwgat_lnw_takes(d))
+        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, beta, dres, dx, dgamma, dbeta, N, d, dtype, dx_masked, mask_seed, mask_p,
+                             xn, seed_base, nullptr, st);
 #define GO(T)                                                                                                             \
     return dx_masked ? ln_bwd_t<T, true, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, dx_masked, \
                                                      mask_seed, mask_p, beta, xn, seed_base)                              \
@@ -514,6 +525,12 @@ extern "C" int hwgat_lnpool_fwd_det(const void* x, float* xhat_sum, float* mean,
     if (!x || !xhat_sum || !mean || !rstd || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int ch = pool_chunks(B, n_tok);
+    if (hwgat_lnw_takes(d)) {
+        const int rc = hwgat_lnw_pool_fwd(x, xhat_sum, mean, rstd, B, n_tok, ch, d, dtype, partial, st);
+        if (rc) return rc;
+        if (partial) lnpool_reduce_k<<<B, 256, 0, st>>>(partial, xhat_sum, ch, d);
+        HWGAT_LAUNCH_CHECK();
+    }
 #define GO(T, D) lnpool_fwd_k<T, D><<<B * ch, 256, 0, st>>>((const T*)x, xhat_sum, mean, rstd, n_tok, ch, partial)
 #define SW(T)                                  \
     switch (d) {                               \
@@ -545,6 +562,9 @@ extern "C" int hwgat_ln_bwd_det(const void* dy, const void* x, const float* mean
     if (dx_masked && (mask_p <= 0.f || mask_p >= 1.f)) return HWGAT_EINVAL;
     if (ws_bytes < hwgat_ln_bwd_det_bytes(d)) return HWGAT_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
+    if (hwgat_lnw_takes(d))
+        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, beta, dres, dx, dgamma, dbeta, N, d, dtype, dx_masked, mask_seed, mask_p,
+                             xn, seed_base, ws, st);
 #define GO(T)                                                                                                              \
     if (xn) return dx_masked ? ln_bwd_t<T, true, true, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, \
                                                                    dx_masked, mask_seed, mask_p, beta, xn, seed_base, ws)  \
@@ -583,6 +603,7 @@ extern "C" int hwgat_lnpool_bwd_masked(const float* g, const void* x, const floa
     if (dxm && (mp <= 0.f || mp >= 1.f)) return HWGAT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int ch = pool_chunks(B, n_tok);
+    if (hwgat_lnw_takes(d)) return hwgat_lnw_pool_bwd(g, x, mean, rstd, dx, B, n_tok, ch, d, dtype, dxm, mseed, mp, seed_base, st);
 #define GO(T, D) lnpool_bwd_k<T, D><<<B * ch, 256, 0, st>>>(g, (const T*)x, mean, rstd, (T*)dx, n_tok, ch, (T*)dxm, mseed, mp, seed_base)
     if (dtype == HWGAT_F32) { SW(float) }
     else if (dtype == HWGAT_BF16) { SW(bf16_t) }

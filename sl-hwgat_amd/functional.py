@@ -681,6 +681,18 @@ def linear_tn(A, Bm, dW, db=None, *, pro_seed=0, pro_p=0.0, ln=None, seed_base=N
     workspace, added in split order; no float atomics)."""
     N, K = dW.shape
     M = A.numel() // N
+    if N % 128 or K % 128:
+        # 64x64 dW tiles (odd multiples of 64): split images added in a fixed order in every mode -- no float atomics
+        need = _lib.lib().hwgat_linear_tn_det_bytes(M, N, K)
+        if need <= 0 or (deterministic and M % 32):
+            raise NotImplementedError("weight gradients need N, K multiples of 64 (and, deterministic, a token count "
+                                      "that is a multiple of 32)")
+        mean, rstd, gamma, beta = ln if ln is not None else (None, None, None, None)
+        ws = torch.empty(need // 4, device=A.device, dtype=torch.float32)
+        call("hwgat_linear_tn_f32_det" if A.dtype == torch.float32 else "hwgat_linear_tn_bf16_det", ptr(A), ptr(Bm), ptr(dW),
+             ptr(db), M, N, K, pro_seed & 0xFFFFFFFF, float(pro_p), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(seed_base),
+             ptr(ws), need, stream())
+        return
     if deterministic:
         need = _lib.lib().hwgat_linear_tn_det_bytes(M, N, K)
         if M % 32 or need <= 0:

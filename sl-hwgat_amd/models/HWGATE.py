@@ -22,7 +22,29 @@ from torch import nn
 from .. import functional as HF
 from ..block import fused_block
 
-_SUPPORTED_WIDTHS = (128, 256, 512, 1024)
+_SUPPORTED_WIDTHS = (128, 256, 512, 1024)         # HGATE / WGATE: the widths their kernels take
+MAX_WIDTH = 1024                                 # HWGATE: every multiple of 64 up to this (width_problem)
+
+
+def width_problem(d, hidden, n_heads, window_size):
+    """why the HWGATE kernels cannot run a stage of width d, FFN hidden width `hidden` and `n_heads` heads (None: they
+    can).  The linears tile their outputs in 64-column blocks, the LayerNorm row maps take every d = 64 n <= 1024, the
+    attention kernels head_dim 32 / 64 (and 128 with window_size 16)."""
+    if d % 64:
+        return f"stage width {d} is not a multiple of 64 (the linears and LayerNorms tile rows in 64-wide blocks)"
+    if d > MAX_WIDTH:
+        return f"stage width {d} is above {MAX_WIDTH} (the LayerNorm row maps end there)"
+    if hidden % 64:
+        return f"FFN hidden width int({d} * ff_ratio) = {hidden} is not a multiple of 64"
+    if d % n_heads:
+        return f"stage width {d} is not divisible by {n_heads} heads"
+    hd = d // n_heads
+    if window_size == 16 and hd not in (32, 64, 128):
+        return f"head_dim {hd} (width {d} / {n_heads} heads): the window attention kernels take head_dim 32, 64 or 128"
+    if window_size != 16 and hd not in (32, 64):
+        return (f"head_dim {hd} with window_size {window_size}: the part-window attention kernels for window sizes "
+                f"other than 16 take head_dim 32 or 64 (128 only with window_size 16)")
+    return None
 
 
 class _Slot(nn.Module):
@@ -62,7 +84,9 @@ class Model(nn.Module):
         if temporal_patch_size != 2:
             # the reference's TemporalMerging doubles the width per stage, which is only
             # consistent with temporal_patch_size == 2 (HWGATE.py:61 vs :312)
-            raise NotImplementedError("HWGAT HIP backend supports temporal_patch_size == 2")
+            raise NotImplementedError(f"HWGAT HIP backend supports temporal_patch_size == 2, got {temporal_patch_size} "
+                                      f"(Model() with every constructor default is refused: its default is "
+                                      f"temporal_patch_size=4; HWGATEParams passes 2)")
         if not 1 <= window_size <= 32:
             raise NotImplementedError(f"window_size {window_size}: the HWGAT HIP backend takes windows of at most 32 "
                                       f"joints (2 frames x 32 = 64 tokens per window)")
@@ -94,17 +118,10 @@ class Model(nn.Module):
         self.layers = nn.ModuleList()
         for i in range(n_stage):
             d = embed_dim * 2 ** i
-            if d not in _SUPPORTED_WIDTHS or d % num_heads[i] or (d // num_heads[i]) not in (32, 64, 128):
-                raise NotImplementedError(
-                    f"stage width {d} / heads {num_heads[i]} not supported by the HIP kernels: widths must be in "
-                    f"{_SUPPORTED_WIDTHS} (the linears tile their output in 128- / 256-column blocks and the LayerNorm "
-                    f"row maps exist for these widths; embed_dim = 64, the reference constructor's default that no "
-                    f"reference config uses, would need 64-column instantiations -- INTEGRATION.md section 6) and "
-                    f"head_dim in (32, 64, 128)")
-            if self._attn_kind == "pwin" and d // num_heads[i] not in (32, 64):
-                raise NotImplementedError(
-                    f"stage {i}: head_dim {d // num_heads[i]} with window_size {window_size}: the part-window attention "
-                    f"kernels for window sizes other than 16 take head_dim 32 or 64")
+            why = width_problem(d, int(d * ff_ratio), num_heads[i], window_size)
+            if why is not None:
+                raise NotImplementedError(f"stage {i}: {why}.  HWGATE takes stage widths d = embed_dim * 2**i that are "
+                                          f"multiples of 64 up to {MAX_WIDTH}, with int(d * ff_ratio) a multiple of 64")
             stage = _Slot()
             stage.blocks = nn.ModuleList()
             for j in range(depths[i]):

@@ -1,0 +1,405 @@
+"""GPU parity for HWGATE stage widths that are odd multiples of 64 (embed_dim 64 / 192): the 128x64-tile NT linears,
+the 64x64-tile weight gradients and the LayerNorm kernels of the new widths through the C-ABI against fp64 torch, and
+whole models against tests/golden/width_*.npz (make_fixtures_width.py) in fp32 and bf16, plus the model modes
+(deterministic eval / train, GraphedEval, GraphedTrainStep, attention dropout)."""
+import importlib
+import os
+import sys
+
+import pytest
+import torch
+
+from helpers import load_fixture, rel_err, grad_digest_check
+from oracle import hwgat_oracle as O
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+from make_fixtures_window import edge_list  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+hw = importlib.import_module("sl-hwgat_amd")
+HF = hw.functional
+train = importlib.import_module("sl-hwgat_amd.train")
+serve = importlib.import_module("sl-hwgat_amd.serve")
+DEV = "cuda:0"
+F32_TOL, BF16_TOL = 2e-5, 1e-2
+THR = [0.3, 0.1, 0.5, 0.2, 0.07, 0.4, 0.25, 0.6]
+
+
+def _tol(dt):
+    return F32_TOL if dt == torch.float32 else BF16_TOL
+
+
+def _gelu(x):
+    return 0.5 * x * (1 + torch.erf(x / 2 ** 0.5))
+
+
+def _gelu_grad(x):
+    return 0.5 * (1 + torch.erf(x / 2 ** 0.5)) + x * torch.exp(-0.5 * x * x) / (2 * torch.pi) ** 0.5
+
+
+# ------------------------------------------------------------------ NT linear, N % 128 == 64
+NT_CASES = [(pro, epi) for pro in (0, 1, 2) for epi in range(7)] + [(3, 0), (3, 2), (3, 5)]
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("N,K", [(64, 64), (192, 64), (576, 192), (64, 192)])
+def test_nt_n64_every_prologue_and_epilogue(dt, N, K):
+    g = torch.Generator().manual_seed(N + K)
+    for pro, epi in NT_CASES:
+        M = 256 if pro == 3 else 300                                  # pro 3 needs whole 128-row tiles; else a ragged tail
+        A = torch.randn(M, K, generator=g).double()
+        W = (torch.randn(N, K, generator=g) * K ** -0.5).double()
+        b = torch.randn(N, generator=g).double()
+        res = torch.randn(M, N, generator=g).double()
+        aux = torch.randn(M, N, generator=g).double()
+        gm, bt = 1 + 0.1 * torch.randn(K, generator=g).double(), 0.1 * torch.randn(K, generator=g).double()
+        p_pro, p_epi, s_pro, s_epi = 0.2, 0.25, 11, 12
+        Ad, Wd = A.to(dt).double(), W.to(dt).double()                 # the values the kernels see
+        resd, auxd = res.to(dt).double(), aux.to(dt).double()
+        mean, rstd = Ad.mean(1), (Ad.var(1, unbiased=False) + 1e-5).rsqrt()
+        a_in = Ad
+        if pro in (1, 3):
+            a_in = (Ad - mean[:, None]) * rstd[:, None] * gm + bt
+        if pro == 2:
+            a_in = Ad * HF.dropout_mask((M, K), s_pro, p_pro, DEV).cpu().double()
+        acc = a_in @ Wd.T
+        mk = HF.dropout_mask((M, N), s_epi, p_epi, DEV).cpu().double()
+        pre = acc + b
+        want2 = None
+        if epi == 0:
+            want = pre
+        elif epi == 1:
+            want = resd + pre * mk
+        elif epi == 2:
+            want, want2 = _gelu(pre) * mk, pre
+        elif epi == 3:
+            want = acc * mk * _gelu_grad(auxd)
+        elif epi == 4:
+            want = acc
+        elif epi == 5:
+            want, want2 = _gelu(pre) * mk, _gelu_grad(pre) * mk
+        else:
+            want = acc * auxd
+        kw = dict(epi=epi, res=res.to(dt).to(DEV) if epi == 1 else None, aux=aux.to(dt).to(DEV) if epi in (3, 6) else None,
+                  epi_seed=s_epi, epi_p=p_epi if epi in (1, 2, 3, 5) else 0.0)
+        Ag = A.to(dt).to(DEV)
+        gf, bf = gm.float().to(DEV), bt.float().to(DEV)
+        m32, r32 = mean.float().to(DEV), rstd.float().to(DEV)
+        if pro == 3:
+            Wf, s, c = HF.ln_fold(W.float().to(DEV), b.float().to(DEV), gf, bf, dt)
+            out = HF.linear_nt(Ag, Wf, None, pro=3, ln=(m32, r32, s, c), **kw)
+        else:
+            out = HF.linear_nt(Ag, W.to(dt).to(DEV), b.float().to(DEV), pro=pro, ln=(m32, r32, gf, bf) if pro == 1 else None,
+                               pro_seed=s_pro, pro_p=p_pro if pro == 2 else 0.0, **kw)
+        got, got2 = (out if isinstance(out, tuple) else (out, None))
+        assert rel_err(got.float().cpu(), want) < _tol(dt), (pro, epi)
+        if want2 is not None:
+            assert rel_err(got2.float().cpu(), want2) < _tol(dt), (pro, epi, "C2")
+
+
+def test_nt_n64_refuses_the_statistics_epilogue():
+    A = torch.randn(256, 64, device=DEV)
+    with pytest.raises(RuntimeError):
+        HF.linear_nt(A, torch.randn(64, 64, device=DEV), None, epi=HF.EPI_BIAS_DROP_RES, res=A, stats=True)
+
+
+# ------------------------------------------------------------------ TN weight gradients, 64x64 tiles
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("N,K", [(192, 64), (64, 64), (128, 64), (64, 128), (576, 192), (192, 192)])
+def test_tn64_weight_gradients(dt, N, K):
+    lib = hw._lib.lib()
+    g = torch.Generator().manual_seed(3 * N + K)
+    for M in (4096, 1000):
+        assert lib.hwgat_linear_tn_det_bytes(M, N, K) > 0
+        assert lib.hwgat_linear_tn_f32_ws_bytes(M, N, K) > 0 and lib.hwgat_linear_tn_bf16_ws_bytes(M, N, K) > 0
+        A = torch.randn(M, N, generator=g).to(dt)
+        Bm = torch.randn(M, K, generator=g).to(dt)
+        gm, bt = 1 + 0.1 * torch.randn(K, generator=g), 0.1 * torch.randn(K, generator=g)
+        Bd = Bm.double()
+        mean, rstd = Bd.mean(1), (Bd.var(1, unbiased=False) + 1e-5).rsqrt()
+        for kind in ("plain", "drop", "ln"):
+            a = A.double()
+            b = Bd
+            kw = {}
+            if kind == "drop":
+                a = a * HF.dropout_mask((M, N), 7, 0.2, DEV).cpu().double()
+                kw = dict(pro_seed=7, pro_p=0.2)
+            if kind == "ln":
+                b = (Bd - mean[:, None]) * rstd[:, None] * gm.double() + bt.double()
+                kw = dict(ln=(mean.float().to(DEV), rstd.float().to(DEV), gm.to(DEV), bt.to(DEV)))
+            want_w, want_b = a.T @ b, a.sum(0)
+            for det in (False, True):
+                if det and M % 32:
+                    continue
+                outs = []
+                for _ in range(2):
+                    dw, db = torch.zeros(N, K, device=DEV), torch.zeros(N, device=DEV)
+                    HF.linear_tn(A.to(DEV), Bm.to(DEV), dw, db, deterministic=det, **kw)
+                    outs.append((dw.cpu(), db.cpu()))
+                assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]), (M, kind, det)
+                assert rel_err(outs[0][0], want_w) < _tol(dt), (M, kind, det)
+                assert rel_err(outs[0][1], want_b) < _tol(dt), (M, kind, det)
+
+
+def test_tn64_plain_entry_accumulates_without_a_workspace():
+    M, N, K = 2000, 192, 64
+    A, Bm = torch.randn(M, N, device=DEV), torch.randn(M, K, device=DEV)
+    dw, db = torch.ones(N, K, device=DEV), torch.ones(N, device=DEV)
+    HF.call("hwgat_linear_tn_f32", HF.ptr(A), HF.ptr(Bm), HF.ptr(dw), HF.ptr(db), M, N, K, 0, 0.0, None, None, None, None,
+            None, HF.stream())
+    assert rel_err(dw.cpu(), 1 + (A.T @ Bm).cpu().double()) < F32_TOL
+    assert rel_err(db.cpu(), 1 + A.sum(0).cpu().double()) < F32_TOL
+
+
+# ------------------------------------------------------------------ LayerNorm family at the new widths
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d", [64, 192, 384, 768])
+def test_layernorm_new_widths(dt, d):
+    g = torch.Generator().manual_seed(d)
+    n = 1003
+    x = (torch.randn(n, d, generator=g) * 2 + 0.5).to(dt)
+    gm, bt = 1 + 0.1 * torch.randn(d, generator=g), 0.1 * torch.randn(d, generator=g)
+    dy = torch.randn(n, d, generator=g).to(dt)
+    dres = torch.randn(n, d, generator=g).to(dt)
+    xr = x.double().requires_grad_(True)
+    gr, br = gm.double().requires_grad_(True), bt.double().requires_grad_(True)
+    yr = torch.nn.functional.layer_norm(xr, (d,), gr, br, 1e-5)
+    yr.backward(dy.double())
+    xg, gg, bg = x.to(DEV), gm.to(DEV), bt.to(DEV)
+    # forward with y, and statistics only
+    y = HF.layer_norm(xg.clone().requires_grad_(True), gg, bg)
+    assert rel_err(y.detach().float().cpu(), yr.detach()) < _tol(dt)
+    mean, rstd = HF.ln_stats(xg, gg, bg)
+    assert rel_err(mean.cpu(), xr.detach().mean(1)) < F32_TOL + (1e-3 if dt != torch.float32 else 0)
+    assert rel_err(rstd.cpu(), (xr.detach().var(1, unbiased=False) + 1e-5).rsqrt()) < 1e-4
+    want_dx = xr.grad + dres.double()
+    xn_want = yr.detach()
+    mk = HF.dropout_mask((n, d), 5, 0.3, DEV).cpu().double()
+    for det in (False, True):
+        for variant in ("plain", "masked", "xn", "xn_masked"):
+            outs = []
+            for _ in range(2 if det else 1):
+                dg, db = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
+                kw = dict(deterministic=det)
+                if "masked" in variant:
+                    kw.update(mask=(5, 0.3))
+                if "xn" in variant:
+                    kw.update(beta=bg)
+                r = HF.ln_backward(dy.to(DEV), xg, mean, rstd, gg, dres.to(DEV), dg, db, **kw)
+                r = r if isinstance(r, tuple) else (r,)
+                outs.append((r, dg.cpu(), db.cpu()))
+            r, dg, db = outs[0]
+            if det:
+                assert torch.equal(outs[0][1], outs[1][1]) and torch.equal(outs[0][2], outs[1][2]), variant
+            assert rel_err(r[0].float().cpu(), want_dx) < _tol(dt), (variant, det)
+            k = 1
+            if "masked" in variant:
+                assert rel_err(r[1].float().cpu(), want_dx * mk) < _tol(dt), (variant, det)
+                k = 2
+            if "xn" in variant:
+                assert rel_err(r[k].float().cpu(), xn_want) < _tol(dt), (variant, det)
+            assert rel_err(dg, gr.grad) < 1e-4 and rel_err(db, br.grad) < 1e-4, (variant, det)
+    # no residual
+    dg, db = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
+    dx = HF.ln_backward(dy.to(DEV), xg, mean, rstd, gg, None, dg, db)
+    assert rel_err(dx.float().cpu(), xr.grad) < _tol(dt)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d", [192, 768])
+def test_ln_mean_pool_new_widths(dt, d):
+    g = torch.Generator().manual_seed(d + 1)
+    B, n_tok = 3, 200
+    x = torch.randn(B, n_tok, d, generator=g).to(dt)
+    gm, bt = 1 + 0.1 * torch.randn(d, generator=g), 0.1 * torch.randn(d, generator=g)
+    df = torch.randn(B, d, generator=g)
+    xr = x.double().requires_grad_(True)
+    fr = torch.nn.functional.layer_norm(xr, (d,), gm.double(), bt.double(), 1e-5).mean(1)
+    fr.backward(df.double())
+    for det in (False, True):
+        xg = x.to(DEV).requires_grad_(True)
+        f = HF.ln_mean_pool(xg, gm.to(DEV), bt.to(DEV), deterministic=det)
+        f.backward(df.to(DEV))
+        assert rel_err(f.detach().cpu(), fr.detach()) < _tol(dt)
+        assert rel_err(xg.grad.float().cpu(), xr.grad) < _tol(dt)
+        if det:
+            f2 = HF.ln_mean_pool(x.to(DEV), gm.to(DEV), bt.to(DEV), deterministic=True)
+            assert torch.equal(f.detach(), f2)
+
+
+# ------------------------------------------------------------------ whole models vs the reference's fixtures
+FIXTURES = ["width_d64.npz", "width_d64_w8.npz", "width_d192.npz"]
+
+
+def _model_from_fixture(fx, dtype=torch.float32):
+    T, K, C, d0, nc, B, seed, W = [int(v) for v in fx["cfg"]]
+    hp = hw.HWGATEParams({"src_len": T, "num_class": nc}, C, None, num_kps=K)
+    hp.window_size, hp.num_heads, hp.drop_rate, hp.embed_dim = W, [int(h) for h in fx["heads"]], 0.0, d0
+    hp.edges = [edge_list(W, w) for w in range(K // W)]
+    hp.adj_mat = torch.tensor(hp.get_adj_mat(), dtype=torch.float32)
+    model = hw.Model(*hp.get_model_params())
+    cfg = dict(kp_dim=C, temporal_dim=T, num_classes=nc, embed_dim=d0, depths=tuple(hp.depths), ff_ratio=hp.ff_ratio,
+               use_pe=hp.pe, num_kps=K, tp=2)
+    model.load_state_dict(O.synth_params(seed, weight_std=0.08, **cfg), strict=False)
+    return model.to(DEV).set_activation_dtype(dtype)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_model_matches_reference_fixture(name):
+    fx = load_fixture(name)
+    model = _model_from_fixture(fx)
+    x = torch.from_numpy(fx["x"]).to(DEV)
+    y = torch.from_numpy(fx["y"]).to(DEV)
+    crit = train.SmoothedCrossEntropyLoss()
+    model.eval()
+    with torch.no_grad():
+        assert rel_err(model(x).cpu(), fx["eval.logits"]) < 1e-4
+    model.zero_grad()
+    loss = crit(model(x), y)
+    loss.backward()
+    assert abs(loss.item() - float(fx["evalbwd.loss"])) < 1e-4
+    grad_digest_check({k: p.grad for k, p in model.named_parameters() if p.grad is not None}, fx, "evalbwd.", 1e-3)
+    model.train()
+    model.threshold_override = [float(t) for t in fx["train.thr"]]
+    model.zero_grad()
+    out = model(x)
+    loss = crit(out, y)
+    loss.backward()
+    assert rel_err(out.detach().cpu(), fx["train.logits"]) < 1e-4
+    assert abs(loss.item() - float(fx["train.loss"])) < 1e-4
+    grad_digest_check({k: p.grad for k, p in model.named_parameters() if p.grad is not None}, fx, "train.", 1e-3)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_model_bf16_matches_reference_fixture(name):
+    fx = load_fixture(name)
+    model = _model_from_fixture(fx, torch.bfloat16)
+    x = torch.from_numpy(fx["x"]).to(DEV)
+    y = torch.from_numpy(fx["y"]).to(DEV)
+    crit = train.SmoothedCrossEntropyLoss()
+    model.eval()
+    with torch.no_grad():
+        assert rel_err(model(x).float().cpu(), fx["eval.logits"]) < 1e-2
+    model.zero_grad()
+    loss = crit(model(x).float(), y)
+    loss.backward()
+    assert abs(loss.item() - float(fx["evalbwd.loss"])) < 1e-2 * max(1.0, abs(float(fx["evalbwd.loss"])))
+    grad_digest_check({k: p.grad for k, p in model.named_parameters() if p.grad is not None}, fx, "evalbwd.", 5e-2)
+    model.train()
+    model.threshold_override = [float(t) for t in fx["train.thr"]]
+    model.zero_grad()
+    out = model(x).float()
+    loss = crit(out, y)
+    loss.backward()
+    assert rel_err(out.detach().cpu(), fx["train.logits"]) < 2e-2
+    assert abs(loss.item() - float(fx["train.loss"])) < 2e-2 * max(1.0, abs(float(fx["train.loss"])))
+
+
+# ------------------------------------------------------------------ model modes
+def _small(d0, W=16, dtype=torch.float32, attn_drop=0.0):
+    torch.manual_seed(13)
+    K = 64
+    heads = (2, 4, 8) if d0 == 64 else (3, 6, 12)
+    hp = hw.HWGATEParams({"src_len": 32, "num_class": 7}, 2, DEV, num_kps=K)
+    hp.window_size, hp.num_heads, hp.embed_dim = W, list(heads), d0
+    hp.edges = [edge_list(W, w) for w in range(K // W)]
+    hp.adj_mat = torch.tensor(hp.get_adj_mat(), dtype=torch.float32)
+    hp.attn_drop_rate = attn_drop
+    model = hw.Model(*hp.get_model_params()).to(DEV)
+    model.set_activation_dtype(dtype)
+    return model
+
+
+MODES = [(64, 16), (64, 8), (192, 16)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d0,W", MODES)
+def test_deterministic_eval_repeats(d0, W, dtype):
+    model = _small(d0, W, dtype).eval()
+    x = torch.rand(6, 32, 64, 2, device=DEV)
+    with torch.no_grad():
+        a = model(x)
+        junk = torch.randn(1 << 20, device=DEV).sum()
+        b = model(x)
+    assert junk.isfinite() and torch.equal(a, b)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d0,W", MODES)
+def test_deterministic_train_repeats_every_weight(d0, W, dtype):
+    model = _small(d0, W, dtype, attn_drop=0.1).train()
+    model.deterministic_train = True
+    g = torch.Generator(device=DEV).manual_seed(4)
+    x = torch.rand(8, 32, 64, 2, device=DEV, generator=g)
+    y = torch.randint(0, 7, (8,), device=DEV, generator=g)
+    w0 = {k: v.clone() for k, v in model.state_dict().items()}
+    runs = []
+    for _ in range(2):
+        model.load_state_dict(w0)
+        model._drop_calls = 5
+        torch.manual_seed(99)
+        opt = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=5e-4, fused=True)
+        step = train.TrainStep(model, opt, None)
+        losses = [step(x, y).clone() for _ in range(3)]
+        runs.append((losses, {n: p.detach().clone() for n, p in model.named_parameters()}))
+    (l1, w1), (l2, w2) = runs
+    assert all(torch.isfinite(v) for v in l1)
+    assert all(torch.equal(a, b) for a, b in zip(l1, l2))
+    for n in w1:
+        assert torch.equal(w1[n], w2[n]), n
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d0,W", MODES)
+def test_graphed_eval_is_bit_equal_to_eager(d0, W, dtype):
+    model = _small(d0, W, dtype).eval()
+    x = torch.rand(4, 32, 64, 2, device=DEV)
+    fast = serve.GraphedEval(model, x)
+    with torch.no_grad():
+        want = model(x)
+    assert torch.equal(fast(x), want)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d0,W", MODES)
+def test_graphed_train_step_matches_eager_deterministic(d0, W, dtype):
+    steps, c0 = 3, 17
+    g = torch.Generator(device=DEV).manual_seed(3)
+    x = torch.rand(8, 32, 64, 2, device=DEV, generator=g)
+    y = torch.randint(0, 7, (8,), device=DEV, generator=g)
+    res = []
+    for graphed in (False, True):
+        m = _small(d0, W, dtype).train()
+        m.deterministic_train = True
+        m.threshold_override = THR
+        o = torch.optim.AdamW([p for p in m.parameters() if p.requires_grad], lr=5e-4, fused=True, capturable=True)
+        m._drop_calls = c0
+        s = train.GraphedTrainStep(m, o, x, y) if graphed else train.TrainStep(m, o, None)
+        losses = [s(x, y).clone() for _ in range(steps)]
+        res.append((losses, [p.detach().clone() for p in m.parameters()]))
+    (l1, w1), (l2, w2) = res
+    for a, b in zip(l1, l2):
+        assert torch.equal(a, b), (float(a), float(b))
+    for a, b in zip(w1, w2):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("d0,W", MODES)
+def test_attention_dropout_trains_and_eval_ignores_it(d0, W):
+    x = torch.rand(4, 32, 64, 2, device=DEV)
+    y = torch.randint(0, 7, (4,), device=DEV)
+    plain = _small(d0, W).eval()
+    dropped = _small(d0, W, attn_drop=0.1).eval()
+    with torch.no_grad():
+        assert torch.equal(plain(x), dropped(x))                  # eval: no attention dropout
+    dropped.train()
+    dropped.threshold_override = THR
+    plain.train()
+    plain.threshold_override = THR
+    plain.drop_rate = dropped.drop_rate = 0.0
+    la = train.SmoothedCrossEntropyLoss()(dropped(x), y)
+    lb = train.SmoothedCrossEntropyLoss()(plain(x), y)
+    la.backward()
+    assert torch.isfinite(la) and float(la.detach()) != float(lb.detach())
+    assert all(torch.isfinite(p.grad).all() for p in dropped.parameters() if p.grad is not None)
