@@ -49,8 +49,10 @@ extern "C" {
  *   4001  hwgat_aug_hand_fill(_ws_bytes), hwgat_aug_resample: device-side train / eval transforms (additions only)
  *   4002  hwgat_pwin_attn_{fwd,bwd}(_drop): HWGATE part-window attention for window sizes 1..32 (additions only)
  *   4003  widths that are odd multiples of 64 (additions only): the NT linears take N % 64 == 0, the TN linears
- *         N % 64 == K % 64 == 0, the LayerNorm family every d = 64 n <= 1024 */
-#define HWGAT_ABI_VERSION 4003
+ *         N % 64 == K % 64 == 0, the LayerNorm family every d = 64 n <= 1024
+ *   4004  the Transformer baseline (additions only): hwgat_seq_attn_{fwd,bwd}, hwgat_seq_embed_{fwd,bwd}(_bytes),
+ *         hwgat_seq_maxpool_{fwd,bwd}; NT epilogues 7 / 8 (ReLU + dropout and its backward) */
+#define HWGAT_ABI_VERSION 4004
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -306,6 +308,8 @@ int hwgat_unmerge_masked(const void* in, void* out, void* out_masked, int B, int
  *        5  C2 = gelu'(acc + bias) * dropmask ; C = dropout(gelu(acc + bias))   (training form of epi 2: the factor the
  *           backward needs is stored instead of the pre-activation)
  *        6  C = acc * aux                             (backward of epi 5; aux = its saved C2)
+ *        7  C = dropout(relu(acc + bias))             (ABI 4004; pro 0 only)
+ *        8  C = acc * (aux > 0) / (1 - epi_p)         (backward of epi 7; aux = its output C, epi_p = its p; pro 0 only)
  *   bias may be NULL (treated as 0).  For dX pass W = transposed weight. */
 int hwgat_linear_nt_f32(const float* A, const float* W, const float* bias, float* C, int64_t M, int N,
                         int K, int pro, const float* mean, const float* rstd, const float* gamma,
@@ -464,6 +468,44 @@ int hwgat_aug_hand_fill(float* x, const int32_t* clip_off, const uint8_t* masked
 int hwgat_aug_resample(const float* x, const int32_t* clip_off, const int32_t* src, const double* prm,
                        const int32_t* gather, float* out, int n_clips, int src_len, int J, int J_out, int C,
                        void* stream);
+
+/* ---- Transformer baseline (ABI 4004; reference hwgat/models/Transformer.py).  Activations (B, T, d) with d = nH * 64.
+ *
+ * hwgat_seq_attn_fwd: multi-head attention of nn.MultiheadAttention(batch_first=True) with a key-padding mask over the
+ *   T <= 512 frames of each clip, head_dim 64 (else HWGAT_ESHAPE).
+ *   qkv  (B, T, 3d) in the in_proj layout (q | k | v, head h at columns h*64 .. h*64+63 of each third), `dtype`
+ *   o    (B, T, d) out: softmax(q k^T / 8 + mask) v per head, head h at columns h*64 ..
+ *   lse  (B, nH, T) fp32 out (may be NULL in eval): log-sum-exp of each query row, -inf for a query without a visible key
+ *   pad  (B, ceil(T / 32)) uint32: bit t % 32 of word t / 32 set = frame t of the clip is padding (hwgat_seq_embed_fwd)
+ *   A query whose keys are ALL padded gets o = 0 (torch 2.10 semantics).  Attention dropout (p in [0, 1)): the keep mask
+ *   of probability (b, h, i, j) is the common hash of seed + *seed_base at index ((b nH + h) T + i) T + j, i.e. what
+ *   hwgat_dropout_mask_f32 writes for a (B, nH, T, T) tensor.
+ * hwgat_seq_attn_bwd: dqkv (B, T, 3d) of the same attention from o, dout = dL/do and the forward's lse; every element of
+ *   dqkv is written (zero for padded keys and for queries without a visible key).  D: (B, nH, T) fp32 workspace.  Two
+ *   launches, no atomics: bit-reproducible. */
+int hwgat_seq_attn_fwd(const void* qkv, void* o, float* lse, const uint32_t* pad, int B, int T, int n_heads,
+                       int head_dim, int dtype, uint32_t seed, float p, const uint32_t* seed_base, void* stream);
+int hwgat_seq_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, const uint32_t* pad,
+                       void* dqkv, float* D, int B, int T, int n_heads, int head_dim, int dtype, uint32_t seed,
+                       float p, const uint32_t* seed_base, void* stream);
+
+/* hwgat_seq_embed_fwd: out (B, T, d) `dtype` = dropout((x Wt + bias) * sqrt(d) + pe[t]) (reference Transformer.py:
+ *   encoder, * sqrt(d_model), PositionalEncoding) and pad (B, ceil(T / 32)) uint32 key-padding words, bit set iff
+ *   x[b, t, 0] == pad_index (exact compare), in one launch.  x (B, T, F) fp32 with F <= 512 any width, Wt (F, d) fp32 =
+ *   the encoder weight transposed, bias (d) or NULL, pe (T, d) fp32 or NULL; dropout mask index (b T + t) d + n.
+ * hwgat_seq_embed_bwd: dW (d, F) += g^T x, db (d) += column sums of g (db may be NULL), g = dout * mask * sqrt(d)
+ *   with the forward's (seed, p) over M = B T rows; ws: >= hwgat_seq_embed_bwd_bytes(F, d) bytes of device memory (need
+ *   not be zeroed).  Fixed-order split sums, no atomics: bit-reproducible.
+ * hwgat_seq_maxpool_fwd: out (B, d) fp32 = max over T of x (B, T, d) `dtype`, idx (B, d) int32 = first index of the
+ *   maximum (torch.max).  hwgat_seq_maxpool_bwd: dx (B, T, d) `dtype` = dout at idx, 0 elsewhere. */
+int hwgat_seq_embed_fwd(const float* x, const float* Wt, const float* bias, const float* pe, void* out, uint32_t* pad,
+                        int B, int T, int F, int d, float pad_index, int dtype, uint32_t seed, float p,
+                        const uint32_t* seed_base, void* stream);
+int64_t hwgat_seq_embed_bwd_bytes(int F, int d);
+int hwgat_seq_embed_bwd(const void* dout, const float* x, float* dW, float* db, int64_t M, int F, int d, int dtype,
+                        uint32_t seed, float p, const uint32_t* seed_base, float* ws, int64_t ws_bytes, void* stream);
+int hwgat_seq_maxpool_fwd(const void* x, float* out, int32_t* idx, int B, int T, int d, int dtype, void* stream);
+int hwgat_seq_maxpool_bwd(const float* dout, const int32_t* idx, void* dx, int B, int T, int d, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

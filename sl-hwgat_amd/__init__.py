@@ -15,7 +15,9 @@ from .parts import part_table
 from .models.HWGATE import Model
 from .models.HGATE import Model as HGATEModel
 from .models.WGATE import Model as WGATEModel
-from .models.model_params import HWGATEParams, HGATEParams, WGATEParams
+from .models.Transformer import Model as TransformerModel
+from .models.model_params import HWGATEParams, HGATEParams, WGATEParams, TransformerParams
 
-__all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "functional",
+__all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "TransformerModel",
+           "TransformerParams", "functional",
            "part_table", "_lib", "checkpoint", "augment"]

@@ -79,6 +79,13 @@ _SIGS = {
     "hwgat_aug_hand_fill_ws_bytes": [_L],
     "hwgat_aug_hand_fill": [_P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _L, _P, _P],
     "hwgat_aug_resample": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "hwgat_seq_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _U, _F, _P, _P],
+    "hwgat_seq_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _U, _F, _P, _P],
+    "hwgat_seq_embed_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _U, _F, _P, _P],
+    "hwgat_seq_embed_bwd_bytes": [_I, _I],
+    "hwgat_seq_embed_bwd": [_P, _P, _P, _P, _L, _I, _I, _I, _U, _F, _P, _P, _L, _P],
+    "hwgat_seq_maxpool_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "hwgat_seq_maxpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _P],
 }
 _lib = None
 

@@ -13,11 +13,16 @@ enum { X_NONE = 0, X_STAT = 1, X_STAT_MERGE = 2, X_LNFOLD = 3 };
 // Phi(x) and phi(x) in hand anyway, so it stores  gelu'(x) * mask  (C2) instead of the pre-activation, and the backward
 // dX launch only multiplies by it -- no erf / exp / mask hash in the backward epilogue, where nothing hides them
 // (EPI_GELU_BWD cost its launch +130 us at stage 2, fp32 and bf16 alike).
+// EPI_BIAS_RELU_DROP / EPI_RELU_BWD: the same pair for a ReLU MLP (the Transformer baseline).  The stored output
+// u = relu(x) * keep / (1 - p) is positive exactly where relu'(x) * mask is non-zero, and that factor is then 1 / (1 - p):
+// the backward epilogue multiplies by (u > 0) / (1 - p) with u passed as `aux` -- no second output, no mask hash.
 enum { EPI_BIAS = 0, EPI_BIAS_DROP_RES = 1, EPI_BIAS_GELU_DROP = 2, EPI_GELU_BWD = 3, EPI_NONE = 4,
-       EPI_BIAS_GELU_DROP_G = 5, EPI_MUL_AUX = 6 };
-constexpr bool epi_has_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_DROP_RES || e == EPI_BIAS_GELU_DROP || e == EPI_BIAS_GELU_DROP_G; }
-constexpr bool epi_reads_extra(int e) { return e == EPI_BIAS_DROP_RES || e == EPI_GELU_BWD || e == EPI_MUL_AUX; }   // res, else aux
-constexpr bool epi_drops(int e) { return e == EPI_BIAS_DROP_RES || e == EPI_BIAS_GELU_DROP || e == EPI_BIAS_GELU_DROP_G || e == EPI_GELU_BWD; }
+       EPI_BIAS_GELU_DROP_G = 5, EPI_MUL_AUX = 6, EPI_BIAS_RELU_DROP = 7, EPI_RELU_BWD = 8 };
+constexpr bool epi_has_bias(int e) { return e == EPI_BIAS || e == EPI_BIAS_DROP_RES || e == EPI_BIAS_GELU_DROP || e == EPI_BIAS_GELU_DROP_G || e == EPI_BIAS_RELU_DROP; }
+constexpr bool epi_reads_extra(int e) { return e == EPI_BIAS_DROP_RES || e == EPI_GELU_BWD || e == EPI_MUL_AUX || e == EPI_RELU_BWD; }   // res, else aux
+constexpr bool epi_drops(int e) { return e == EPI_BIAS_DROP_RES || e == EPI_BIAS_GELU_DROP || e == EPI_BIAS_GELU_DROP_G || e == EPI_GELU_BWD || e == EPI_BIAS_RELU_DROP; }
+// the ReLU epilogues run on the 128-row tile kernels of gemm_f32.hip / gemm_bf16.hip only (not the 256-wide ones)
+inline bool epi_is_relu(int e) { return e == EPI_BIAS_RELU_DROP || e == EPI_RELU_BWD; }
 
 // Dropout mask: a counter-based hash of (seed, element index).  One 32-bit hash serves an
 // aligned PAIR of elements (16 bits each): keep iff its 16 bits >= p * 65536 (p is thereby

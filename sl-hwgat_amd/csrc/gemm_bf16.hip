@@ -265,6 +265,14 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_nt
                         unpack8(ex[ps], h);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) o8[e] *= h[e];
+                    } else if constexpr (EPI == EPI_BIAS_RELU_DROP) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) o8[e] = fmaxf(o8[e], 0.f) * dk[e];
+                    } else if constexpr (EPI == EPI_RELU_BWD) {
+                        float u[8];
+                        unpack8(ex[ps], u);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) o8[e] *= u[e] > 0.f ? epi_sc : 0.f;
                     } else if constexpr (EPI == EPI_GELU_BWD) {
                         float h[8];
                         unpack8(ex[ps], h);
@@ -527,6 +535,12 @@ int launch_nt_b(const NtArgsB& a, int epi, hipStream_t st, bool fold = false) {
         case EPI_BIAS_GELU_DROP_G: gemm_nt_bf16_k<PRO, EPI_BIAS_GELU_DROP_G, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
         case EPI_MUL_AUX: gemm_nt_bf16_k<PRO, EPI_MUL_AUX, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
         case EPI_NONE: gemm_nt_bf16_k<PRO, EPI_NONE, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
+        case EPI_BIAS_RELU_DROP:
+            if constexpr (PRO == PRO_NONE) { gemm_nt_bf16_k<PRO_NONE, EPI_BIAS_RELU_DROP, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
+            return HWGAT_EINVAL;
+        case EPI_RELU_BWD:
+            if constexpr (PRO == PRO_NONE) { gemm_nt_bf16_k<PRO_NONE, EPI_RELU_BWD, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
+            return HWGAT_EINVAL;
         default: return HWGAT_EINVAL;
     }
     HWGAT_LAUNCH_CHECK();
@@ -586,9 +600,10 @@ extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float
     }
     if (epi == EPI_BIAS_DROP_RES && !res) return HWGAT_EINVAL;
     if ((epi == EPI_BIAS_GELU_DROP || epi == EPI_BIAS_GELU_DROP_G) && !C2) return HWGAT_EINVAL;
-    if ((epi == EPI_GELU_BWD || epi == EPI_MUL_AUX) && !aux) return HWGAT_EINVAL;
+    if ((epi == EPI_GELU_BWD || epi == EPI_MUL_AUX || epi == EPI_RELU_BWD) && !aux) return HWGAT_EINVAL;
     if (pro_p < 0.f || pro_p >= 1.f || epi_p < 0.f || epi_p >= 1.f) return HWGAT_EINVAL;
     if (pro == PRO_DROP && pro_p == 0.f) pro = PRO_NONE;          // eval mode: no mask to hash
+    if (epi_is_relu(epi) && pro != PRO_NONE) return HWGAT_EINVAL;
     const bool stat = stat_sum != nullptr || stat_sq != nullptr || merge_K > 0;
     if (stat) {
         if (!stat_sum || !stat_sq || pro != PRO_NONE || epi != EPI_BIAS_DROP_RES) return HWGAT_EINVAL;
@@ -623,7 +638,7 @@ extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float
     static const bool nt_old = [] { const char* e = lab_env("HWGAT_NT_KERNEL"); return e && e[0] == 'o'; }();
     static const int nt256_min_k = [] { const char* e = lab_env("HWGAT_NT256_MINK"); return e ? atoi(e) : 128; }();
     // (fewer than 128 such tiles: the 128 x 128 kernel spreads a serving-size launch over four times as many CUs)
-    if (!nt_old && N % 256 == 0 && K >= nt256_min_k && M >= 256 &&
+    if (!nt_old && !epi_is_relu(epi) && N % 256 == 0 && K >= nt256_min_k && M >= 256 &&
         ((M / 256) * (N / 256) >= 128 || a.stat_sum != nullptr)) {     // (the row statistics of the 256-wide kernels are the order-fixed ones: eval determinism)
         const int64_t m256 = M / 256 * 256;
         NtArgsB b = a;

@@ -279,6 +279,13 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_nt
                             *reinterpret_cast<f32x4*>(p.C2 + off) = gq;
                         } else if constexpr (EPI == EPI_MUL_AUX) {
                             v *= ex[ps];
+                        } else if constexpr (EPI == EPI_BIAS_RELU_DROP) {
+                            v.x = fmaxf(v.x, 0.f) * dk.x; v.y = fmaxf(v.y, 0.f) * dk.y;
+                            v.z = fmaxf(v.z, 0.f) * dk.z; v.w = fmaxf(v.w, 0.f) * dk.w;
+                        } else if constexpr (EPI == EPI_RELU_BWD) {
+                            const f32x4 u = ex[ps];
+                            v.x *= u.x > 0.f ? epi_sc : 0.f; v.y *= u.y > 0.f ? epi_sc : 0.f;
+                            v.z *= u.z > 0.f ? epi_sc : 0.f; v.w *= u.w > 0.f ? epi_sc : 0.f;
                         } else if constexpr (EPI == EPI_GELU_BWD) {
                             const f32x4 h = ex[ps];
                             v.x *= dk.x * gelu_grad(h.x); v.y *= dk.y * gelu_grad(h.y);
@@ -535,6 +542,12 @@ int launch_nt(const NtArgs& a, int epi, hipStream_t st, bool fold = false) {
         case EPI_BIAS_GELU_DROP_G: gemm_nt_k<PRO, EPI_BIAS_GELU_DROP_G, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
         case EPI_MUL_AUX: gemm_nt_k<PRO, EPI_MUL_AUX, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
         case EPI_NONE: gemm_nt_k<PRO, EPI_NONE, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
+        case EPI_BIAS_RELU_DROP:
+            if constexpr (PRO == PRO_NONE) { gemm_nt_k<PRO_NONE, EPI_BIAS_RELU_DROP, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
+            return HWGAT_EINVAL;
+        case EPI_RELU_BWD:
+            if constexpr (PRO == PRO_NONE) { gemm_nt_k<PRO_NONE, EPI_RELU_BWD, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
+            return HWGAT_EINVAL;
         default: return HWGAT_EINVAL;
     }
     HWGAT_LAUNCH_CHECK();
@@ -641,8 +654,9 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
     }
     if (epi == EPI_BIAS_DROP_RES && !res) return HWGAT_EINVAL;
     if ((epi == EPI_BIAS_GELU_DROP || epi == EPI_BIAS_GELU_DROP_G) && !C2) return HWGAT_EINVAL;
-    if ((epi == EPI_GELU_BWD || epi == EPI_MUL_AUX) && !aux) return HWGAT_EINVAL;
+    if ((epi == EPI_GELU_BWD || epi == EPI_MUL_AUX || epi == EPI_RELU_BWD) && !aux) return HWGAT_EINVAL;
     if (pro_p < 0.f || pro_p >= 1.f || epi_p < 0.f || epi_p >= 1.f) return HWGAT_EINVAL;
+    if (epi_is_relu(epi) && pro != PRO_NONE) return HWGAT_EINVAL;
     const bool stat = stat_sum != nullptr || stat_sq != nullptr || merge_K > 0;
     if (stat) {
         if (!stat_sum || !stat_sq || pro != PRO_NONE || epi != EPI_BIAS_DROP_RES) return HWGAT_EINVAL;
@@ -692,7 +706,7 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
     static const int nt256_min_k = [] { const char* e = lab_env("HWGAT_NT256_MINK"); return e ? atoi(e) : 128; }();
     // (serving batches: fewer than 128 tiles of 256 x 256 leave most of the 256 CUs without a tile -- the 128 x 128 kernel
     //  has four times as many; B = 1 eval forward 3.96 -> see profiles/r03_serve_lab.txt)
-    if (!nt_old && tile_override() == 0 && N % 256 == 0 && K >= nt256_min_k && M >= 256 &&
+    if (!nt_old && !epi_is_relu(epi) && tile_override() == 0 && N % 256 == 0 && K >= nt256_min_k && M >= 256 &&
         ((M / 256) * (N / 256) >= 128 || a.stat_sum != nullptr)) {     // (the row statistics of the 256-wide kernels are the order-fixed ones: eval determinism)
         const int64_t m256 = M / 256 * 256;
         NtArgs b = a;
@@ -711,7 +725,8 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
             default: return HWGAT_EINVAL;
         }
     }
-    const bool heavy = epi == EPI_BIAS_DROP_RES || epi == EPI_BIAS_GELU_DROP || epi == EPI_GELU_BWD || epi == EPI_BIAS_GELU_DROP_G || epi == EPI_MUL_AUX;
+    const bool heavy = epi == EPI_BIAS_DROP_RES || epi == EPI_BIAS_GELU_DROP || epi == EPI_GELU_BWD || epi == EPI_BIAS_GELU_DROP_G || epi == EPI_MUL_AUX ||
+                       epi_is_relu(epi);
     const bool big = tile_override() == 2 && (M % 256 == 0) && (N % 256 == 0);
     const bool k16 = tile_override() == 3 || (tile_override() == 0 && heavy);
 #define NT_GO(P) return big ? launch_nt<P, NtBig>(a, epi, st) : (k16 ? launch_nt<P, NtK16>(a, epi, st) : launch_nt<P, NtSmall>(a, epi, st))

@@ -168,7 +168,7 @@ def embed(x, idx, bmat, pe, K, out_dtype=torch.float32, drop_p=0.0, seed=0, seed
 # ---------------------------------------------------------------- LayerNorm
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta):
+    def forward(ctx, x, gamma, beta, deterministic=False):
         d = x.shape[-1]
         n = x.numel() // d
         y = torch.empty_like(x)
@@ -177,6 +177,7 @@ class _LayerNorm(torch.autograd.Function):
         call("hwgat_ln_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd),
              n, d, dtype_code(x), stream())
         ctx.save_for_backward(x, gamma, mean, rstd)
+        ctx.deterministic = bool(deterministic)
         return y
 
     @staticmethod
@@ -184,15 +185,19 @@ class _LayerNorm(torch.autograd.Function):
         x, gamma, mean, rstd = ctx.saved_tensors
         d = x.shape[-1]
         dy = dy.contiguous()
-        dx = torch.empty_like(x)
         dg = torch.zeros(2, d, device=x.device, dtype=torch.float32)
+        if ctx.deterministic:          # dgamma / dbeta through per-block images added in a fixed order (hwgat_ln_bwd_det)
+            dx = ln_backward(dy, x, mean, rstd, gamma, None, dg[0], dg[1], deterministic=True)
+            return dx, dg[0], dg[1], None
+        dx = torch.empty_like(x)
         call("hwgat_ln_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), None, ptr(dx),
              ptr(dg[0]), ptr(dg[1]), x.numel() // d, d, dtype_code(x), stream())
-        return dx, dg[0], dg[1]
+        return dx, dg[0], dg[1], None
 
 
-def layer_norm(x, gamma, beta):
-    return _LayerNorm.apply(x.contiguous(), gamma, beta)
+def layer_norm(x, gamma, beta, deterministic=False):
+    """LayerNorm over the last dim; `deterministic`: a bit-reproducible backward (no float atomics)"""
+    return _LayerNorm.apply(x.contiguous(), gamma, beta, bool(deterministic))
 
 
 # ---------------------------------------------------------------- attention
@@ -809,3 +814,102 @@ def seed_set(state, counter, initial, salt):
 def seed_advance(state):
     """counter += 1 and the new base, on the device: the form a captured train step replays"""
     call("hwgat_seed_advance", ptr(state), stream())
+
+
+# ---------------------------------------------------------------- Transformer baseline (models/Transformer.py)
+EPI_BIAS_RELU_DROP, EPI_RELU_BWD = 7, 8
+SEQ_MAX_LEN = 512
+
+
+def seq_embed(x, Wt, bias, pe, out_dtype, pad_index, drop_p=0.0, seed=0, seed_base=None):
+    """frames (B, T, F) fp32 -> (drop((x W^T + b) sqrt(d) + pe[:T]) (B, T, d) in `out_dtype`, key-padding words
+    (B, ceil(T/32)) int32 with bit t set iff x[b, t, 0] == pad_index), one launch (hwgat_seq_embed_fwd).  Wt = W^T (F, d)."""
+    B, T, F = x.shape
+    d = Wt.shape[1]
+    out = torch.empty(B, T, d, device=x.device, dtype=out_dtype)
+    pad = torch.empty(B, (T + 31) // 32, device=x.device, dtype=torch.int32)
+    call("hwgat_seq_embed_fwd", ptr(x), ptr(Wt), ptr(bias), ptr(pe), ptr(out), ptr(pad), B, T, F, d, float(pad_index),
+         dtype_code(out), seed & 0xFFFFFFFF, float(drop_p), ptr(seed_base), stream())
+    return out, pad
+
+
+def seq_embed_backward(dout, x, dW, db, drop_p=0.0, seed=0, seed_base=None):
+    """dW (d, F) += g^T x, db (d) += colsum(g), g = dout * mask * sqrt(d): fixed-order split sums (bit-reproducible)"""
+    F = x.shape[-1]
+    d = dout.shape[-1]
+    need = _lib.lib().hwgat_seq_embed_bwd_bytes(F, d)
+    if need <= 0:
+        raise NotImplementedError(f"the frame embedding takes at most 512 input features, got {F}")
+    ws = torch.empty(need // 4, device=x.device, dtype=torch.float32)
+    call("hwgat_seq_embed_bwd", ptr(dout), ptr(x), ptr(dW), ptr(db), x.numel() // F, F, d, dtype_code(dout),
+         seed & 0xFFFFFFFF, float(drop_p), ptr(seed_base), ptr(ws), need, stream())
+
+
+def seq_attn_forward(qkv, pad, n_heads, drop=None, want_lse=True):
+    """qkv (B, T, 3d) -> (o (B, T, d), lse (B, nH, T) fp32 or None); `drop` = (seed, p[, seed_base]) or None"""
+    B, T, d3 = qkv.shape
+    d = d3 // 3
+    o = torch.empty(B, T, d, device=qkv.device, dtype=qkv.dtype)
+    lse = torch.empty(B, n_heads, T, device=qkv.device, dtype=torch.float32) if want_lse else None
+    seed, p, base = (int(drop[0]) & 0xFFFFFFFF, float(drop[1]), drop[2] if len(drop) > 2 else None) if drop else (0, 0.0, None)
+    call("hwgat_seq_attn_fwd", ptr(qkv), ptr(o), ptr(lse), ptr(pad), B, T, n_heads, d // n_heads, dtype_code(qkv),
+         seed, p, ptr(base), stream())
+    return o, lse
+
+
+def seq_attn_backward(qkv, o, do, lse, pad, n_heads, drop=None):
+    """dqkv (B, T, 3d) of seq_attn_forward; no atomics (two launches), bit-reproducible"""
+    B, T, d3 = qkv.shape
+    d = d3 // 3
+    dqkv = torch.empty_like(qkv)
+    D = torch.empty(B, n_heads, T, device=qkv.device, dtype=torch.float32)
+    seed, p, base = (int(drop[0]) & 0xFFFFFFFF, float(drop[1]), drop[2] if len(drop) > 2 else None) if drop else (0, 0.0, None)
+    call("hwgat_seq_attn_bwd", ptr(qkv), ptr(o), ptr(do.contiguous()), ptr(lse), ptr(pad), ptr(dqkv), ptr(D), B, T,
+         n_heads, d // n_heads, dtype_code(qkv), seed, p, ptr(base), stream())
+    return dqkv
+
+
+class _SeqAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, pad, n_heads, drop):
+        o, lse = seq_attn_forward(qkv, pad, n_heads, drop, want_lse=True)
+        ctx.save_for_backward(qkv, o, lse, pad)
+        ctx.cfg = (n_heads, drop)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, pad = ctx.saved_tensors
+        n_heads, drop = ctx.cfg
+        return seq_attn_backward(qkv, o, do, lse, pad, n_heads, drop), None, None, None
+
+
+def seq_attention(qkv, pad, n_heads, drop=None):
+    """dense key-padded multi-head attention over the frames of each clip (hwgat_seq_attn_*): qkv (B, T, 3d) in the
+    in_proj layout -> o (B, T, d); `pad` from seq_embed; `drop` = (seed, p[, seed_base]) on the probabilities"""
+    return _SeqAttn.apply(qkv.contiguous(), pad, int(n_heads), drop if drop and float(drop[1]) > 0.0 else None)
+
+
+class _SeqMaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        B, T, d = x.shape
+        out = torch.empty(B, d, device=x.device, dtype=torch.float32)
+        idx = torch.empty(B, d, device=x.device, dtype=torch.int32)
+        call("hwgat_seq_maxpool_fwd", ptr(x), ptr(out), ptr(idx), B, T, d, dtype_code(x), stream())
+        ctx.save_for_backward(idx)
+        ctx.shape, ctx.dtype = (B, T, d), x.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (idx,) = ctx.saved_tensors
+        B, T, d = ctx.shape
+        dx = torch.empty(B, T, d, device=dout.device, dtype=ctx.dtype)
+        call("hwgat_seq_maxpool_bwd", ptr(dout.float().contiguous()), ptr(idx), ptr(dx), B, T, d, dtype_code(dx), stream())
+        return dx
+
+
+def seq_max_pool(x):
+    """max over the frames of (B, T, d) -> (B, d) fp32 (first index of the maximum, as torch.max)"""
+    return _SeqMaxPool.apply(x.contiguous())

@@ -21,6 +21,7 @@ from torch import nn
 
 from .. import functional as HF
 from ..block import fused_block
+from ..seeding import DeviceSeeds
 
 _SUPPORTED_WIDTHS = (128, 256, 512, 1024)         # HGATE / WGATE: the widths their kernels take
 MAX_WIDTH = 1024                                 # HWGATE: every multiple of 64 up to this (width_problem)
@@ -72,7 +73,7 @@ def _last_slot_mask(frames, n_windows, window_size=16):
     return m.view(f * n_windows, n, n)
 
 
-class Model(nn.Module):
+class Model(DeviceSeeds, nn.Module):
     _attn_kind = "win"          # part-window attention (hwgat_win_attn_*); HGATE overrides with "blk", WGATE with "band";
                                 # an HWGATE with window_size != 16 sets "pwin" on the instance (hwgat_pwin_attn_*)
 
@@ -157,13 +158,7 @@ class Model(nn.Module):
         self.part_index: Optional[torch.Tensor] = None           # set by use_part_table()
         self.activation_dtype = torch.float32
         self.threshold_override: Optional[List[float]] = None    # tests: inject train thresholds
-        self._drop_calls = 0
-        # the dropout seed lives on the DEVICE: {step counter, base seed of the step, initial seed, rank salt}; every
-        # seeded kernel adds word 1 to its (host, per-site) seed when it runs, see include/hwgat_hip.h "dropout seeds"
-        self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)
-        self.device_seed_counter = False                          # True: a captured train step advances the counter itself
-        self.deterministic_eval = True                            # eval(): fixed-order sums, bit-reproducible logits
-        self.deterministic_train = False                          # train(): the same for the whole step (slower: no float atomics anywhere)
+        self._init_device_seeds()
         if device is not None:
             self.to(device)
 
@@ -183,43 +178,6 @@ class Model(nn.Module):
 
     # ------------------------------------------------------------ forward
     attn_drop_rate = 0.0      # set by every constructor (HWGATE / HGATE / WGATE)
-
-    def _site_seeds(self, k):
-        """four dropout-SITE seeds of block k (host integers that never change): proj, fc1, fc2 outputs
-        (HWGATE.py:116,133,135) and the attention probabilities (HWGATE.py:112).  A kernel hashes with
-        site seed + the base seed of the step, which it reads from `_seed_state[1]` on the device."""
-        return [((k * 4 + s) * HF.SEED_SITE) & 0xFFFFFFFF for s in range(4)]
-
-    def _seeds(self, k):
-        """the four EFFECTIVE seeds of block k for the step whose counter is `_drop_calls` (host mirror of the device
-        word: site seed + base; what hwgat_dropout_mask_f32 needs to reproduce a mask in a test)"""
-        # rank_salt: data-parallel ranks share torch's seed (identical initial weights) but must not share
-        # dropout masks (SURVEY 8e); dist.broadcast_parameters() sets it to the rank
-        base = HF.seed_base_value(torch.initial_seed(), self._drop_calls, getattr(self, "rank_salt", 0))
-        return [(base + s) & 0xFFFFFFFF for s in self._site_seeds(k)]
-
-    def _seed_base(self):
-        """the 1-element device view the kernels read the step's base seed from"""
-        return self._seed_state[1:2]
-
-    def _next_step_seed(self):
-        """once per train-mode forward.  Eager: the host counter goes up and the four state words are rewritten from host
-        integers (kernel arguments -- no copy, no sync).  `device_seed_counter` (a captured train step, train.GraphedTrainStep):
-        the device increments its own counter, so a graph replay draws fresh masks; the host counter is then only a mirror
-        that the step object keeps in step."""
-        if self.device_seed_counter:
-            HF.seed_advance(self._seed_state)
-        else:
-            self._drop_calls += 1
-            HF.seed_set(self._seed_state, self._drop_calls, torch.initial_seed(), getattr(self, "rank_salt", 0))
-
-    deterministic_train = False
-
-    def _deterministic(self):
-        """bit-reproducible arithmetic for this call: eval() by default (`deterministic_eval`); train() on request
-        (`deterministic_train = True`: fixed-order row statistics, pooled sum and parameter gradients -- the reference's
-        single-device training repeats itself bit for bit with fixed seeds, this is the mode that does the same)"""
-        return bool(self.deterministic_train if self.training else self.deterministic_eval)
 
     def block_list(self):
         """every PartAttentionBlock container in execution order (what functional.weight_prep derives the copies of)"""

@@ -158,3 +158,25 @@ class WGATEParams:
         return (self.kp_dim, self.num_kps, self.temporal_dim, self.num_classes, self.embed_dim, self.pe,
                 self.depths, self.num_heads, self.window_size, self.ff_ratio, self.adj_mat, self.drop_rate,
                 self.attn_drop_rate, self.norm_layer, self.device)
+
+
+class TransformerParams:
+    """the reference's TransformerParams (hwgat/models/model_params.py:590-605): same attributes, same defaults, same
+    positional tuple (input_dim is the per-joint feature count; the model gets input_dim * num_kp features per frame)"""
+
+    def __init__(self, dataset_params, input_dim, device=None) -> None:
+        self.input_dim = input_dim
+        self.num_kp = 29
+        self.nclass = dataset_params['num_class']
+        self.pad_index = -1
+        self.d_model = 512
+        self.nhead = 8
+        self.dim_feedforward = 2048
+        self.num_encoder_layers = 3
+        self.dropout = 0.1
+        self.max_len = dataset_params['src_len']
+        self.pool = 'mean'
+
+    def get_model_params(self):
+        return (self.input_dim * self.num_kp, self.nclass, self.pad_index, self.d_model, self.nhead, self.dim_feedforward,
+                self.num_encoder_layers, self.dropout, self.max_len, self.pool)

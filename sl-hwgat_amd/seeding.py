@@ -1,0 +1,59 @@
+"""The device-resident dropout seed of a model (shared by HWGATE / HGATE / WGATE and the Transformer baseline).
+
+Every seeded kernel hashes with  site seed + the step's base seed, which it reads from `_seed_state[1]` on the device when
+it runs (include/hwgat_hip.h, "dropout seeds"), so a train step captured in a HIP graph (train.GraphedTrainStep) replays
+with fresh masks.  A model class mixes DeviceSeeds in front of nn.Module and calls `_init_device_seeds()` in its
+constructor; train.TrainStep, train.GraphedTrainStep and serve.GraphedEval use `_seed_state`, `_drop_calls`, `_seeds`
+and `device_seed_counter`.
+"""
+import torch
+
+from . import functional as HF
+
+
+class DeviceSeeds:
+    def _init_device_seeds(self):
+        self._drop_calls = 0
+        # the dropout seed lives on the DEVICE: {step counter, base seed of the step, initial seed, rank salt}; every
+        # seeded kernel adds word 1 to its (host, per-site) seed when it runs, see include/hwgat_hip.h "dropout seeds"
+        self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)
+        self.device_seed_counter = False                          # True: a captured train step advances the counter itself
+        self.deterministic_eval = True                            # eval(): fixed-order sums, bit-reproducible logits
+        self.deterministic_train = False                          # train(): the same for the whole step (slower: no float atomics anywhere)
+
+    def _site_seeds(self, k):
+        """four dropout-SITE seeds of block k (host integers that never change): proj, fc1, fc2 outputs
+        (HWGATE.py:116,133,135) and the attention probabilities (HWGATE.py:112).  A kernel hashes with
+        site seed + the base seed of the step, which it reads from `_seed_state[1]` on the device."""
+        return [((k * 4 + s) * HF.SEED_SITE) & 0xFFFFFFFF for s in range(4)]
+
+    def _seeds(self, k):
+        """the four EFFECTIVE seeds of block k for the step whose counter is `_drop_calls` (host mirror of the device
+        word: site seed + base; what hwgat_dropout_mask_f32 needs to reproduce a mask in a test)"""
+        # rank_salt: data-parallel ranks share torch's seed (identical initial weights) but must not share
+        # dropout masks; dist.broadcast_parameters() sets it to the rank
+        base = HF.seed_base_value(torch.initial_seed(), self._drop_calls, getattr(self, "rank_salt", 0))
+        return [(base + s) & 0xFFFFFFFF for s in self._site_seeds(k)]
+
+    def _seed_base(self):
+        """the 1-element device view the kernels read the step's base seed from"""
+        return self._seed_state[1:2]
+
+    def _next_step_seed(self):
+        """once per train-mode forward.  Eager: the host counter goes up and the four state words are rewritten from host
+        integers (kernel arguments -- no copy, no sync).  `device_seed_counter` (a captured train step, train.GraphedTrainStep):
+        the device increments its own counter, so a graph replay draws fresh masks; the host counter is then only a mirror
+        that the step object keeps in step."""
+        if self.device_seed_counter:
+            HF.seed_advance(self._seed_state)
+        else:
+            self._drop_calls += 1
+            HF.seed_set(self._seed_state, self._drop_calls, torch.initial_seed(), getattr(self, "rank_salt", 0))
+
+    deterministic_train = False
+
+    def _deterministic(self):
+        """bit-reproducible arithmetic for this call: eval() by default (`deterministic_eval`); train() on request
+        (`deterministic_train = True`: fixed-order row statistics, pooled sum and parameter gradients -- the reference's
+        single-device training repeats itself bit for bit with fixed seeds, this is the mode that does the same)"""
+        return bool(self.deterministic_train if self.training else self.deterministic_eval)

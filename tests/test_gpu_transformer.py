@@ -1,0 +1,301 @@
+"""GPU: the Transformer baseline -- hwgat_seq_attn_* against the fp64 restatement (padding patterns, dropout, ragged T,
+both dtypes, run-to-run bit-identical backward), the frame embed and its weight gradient, the ReLU epilogues, the max
+pool, the whole model against the reference fixtures (tests/golden/transformer_*.npz), train-mode dropout, the
+deterministic / graphed modes and a short AdamW trajectory against the fp64 restatement."""
+import importlib
+import math
+
+import pytest
+import torch
+
+import transformer_helpers as TH
+from helpers import grad_digest_check, load_fixture
+
+pytestmark = pytest.mark.gpu
+
+hw = importlib.import_module("sl-hwgat_amd")
+HF = hw.functional
+train = importlib.import_module("sl-hwgat_amd.train")
+serve = importlib.import_module("sl-hwgat_amd.serve")
+DEV = torch.device("cuda:0")
+TOL = {torch.float32: 2e-5, torch.bfloat16: 1e-2}
+
+
+def _pad_pattern(kind, B, T):
+    pad = torch.zeros(B, T, dtype=torch.bool)
+    if kind == "tail":
+        pad[0, T - max(1, T // 3):] = True
+    elif kind == "scattered":
+        pad[0, 1::3] = True
+    elif kind == "allpad":
+        pad[1] = True
+        pad[0, T // 2:] = True
+    return pad
+
+
+def _pad_words(pad):
+    B, T = pad.shape
+    nw = (T + 31) // 32
+    w = torch.zeros(B, nw, dtype=torch.int64)
+    for t in range(T):
+        w[:, t // 32] |= pad[:, t].to(torch.int64) << (t % 32)
+    w = torch.where(w >= 2 ** 31, w - 2 ** 32, w)
+    return w.to(torch.int32).to(DEV)
+
+
+def _rel(a, b, floor=1e-30):
+    """|a - b| / max(|b|, floor)"""
+    a, b = a.double().cpu(), b.double().cpu()
+    return ((a - b).norm() / b.norm().clamp_min(floor)).item()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("T", [1, 7, 64, 192, 193, 512])
+def test_seq_attn_against_fp64(T, dtype):
+    B, nH, d = 2, 2, 128
+    g = torch.Generator().manual_seed(T)
+    for kind in ("none", "tail", "scattered", "allpad"):
+        for p in (0.0, 0.2):
+            qkv = torch.randn(B, T, 3 * d, generator=g)
+            do = torch.randn(B, T, d, generator=g)
+            pad = _pad_pattern(kind, B, T)
+            words = _pad_words(pad)
+            qkv_d = qkv.to(DEV, dtype)
+            seed = 1234 + T
+            drop = (seed, p) if p > 0 else None
+            o, lse = HF.seq_attn_forward(qkv_d, words, nH, drop)
+            dq1 = HF.seq_attn_backward(qkv_d, o, do.to(DEV, dtype), lse, words, nH, drop)
+            dq2 = HF.seq_attn_backward(qkv_d, o, do.to(DEV, dtype), lse, words, nH, drop)
+            assert torch.equal(dq1, dq2), "seq_attn backward is not bit-reproducible"
+            keep = HF.dropout_mask((B, nH, T, T), seed, p, DEV).double().cpu() if p > 0 else None
+            qr = qkv_d.double().cpu().requires_grad_(True)
+            ref = TH.attention(qr, pad, nH, keep)
+            ref.backward(do.to(dtype).double())
+            tol = TOL[dtype]
+            assert _rel(o, ref.detach()) < tol, (kind, p, "o", _rel(o, ref.detach()))
+            for part, sl in (("dq", slice(0, d)), ("dk", slice(d, 2 * d)), ("dv", slice(2 * d, 3 * d))):
+                # (T = 1: dq, dk are analytically 0 and what is left is rounding -- measured against the whole gradient)
+                floor = qr.grad.norm().item() if (T == 1 and part != "dv") else 0.0
+                e = _rel(dq1[..., sl], qr.grad[..., sl], max(floor, 1e-30))
+                assert e < tol, (kind, p, part, e)
+            if kind == "allpad":
+                assert float(o[1].abs().max()) == 0.0 and float(dq1[1].abs().max()) == 0.0
+
+
+def test_seq_attn_refuses_other_shapes():
+    qkv = torch.zeros(1, 8, 3 * 256, device=DEV)
+    words = torch.zeros(1, 1, dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError, match="ESHAPE"):
+        HF.seq_attn_forward(qkv, words, 2)                   # head_dim 128
+    qkv = torch.zeros(1, 513, 3 * 128, device=DEV)
+    with pytest.raises(RuntimeError, match="ESHAPE"):
+        HF.seq_attn_forward(qkv, torch.zeros(1, 17, dtype=torch.int32, device=DEV), 2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_seq_embed_and_weight_gradient(dtype):
+    B, T, Fd, d, p, seed = 3, 37, 87, 128, 0.1, 99
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(B, T, Fd, generator=g)
+    x[0, 30:] = -1.0
+    x[2, ::4, 0] = -1.0
+    W, b = torch.randn(d, Fd, generator=g) * 0.1, torch.randn(d, generator=g) * 0.1
+    pe = TH.positional(d, T).float()
+    out, words = HF.seq_embed(x.to(DEV), HF.transpose(W.to(DEV)), b.to(DEV), pe.to(DEV), dtype, -1.0, p, seed)
+    keep = HF.dropout_mask((B, T, d), seed, p, DEV).double().cpu()
+    assert abs(float((keep == 0).double().mean()) - p) < 0.01
+    Wr, br = W.double().requires_grad_(True), b.double().requires_grad_(True)
+    ref = ((x.double() @ Wr.T + br) * math.sqrt(d) + pe.double()) * keep
+    assert _rel(out, ref.detach()) < TOL[dtype]
+    assert torch.equal(words.cpu(), _pad_words(x[:, :, 0] == -1.0).cpu())
+    dout = torch.randn(B, T, d, generator=g)
+    ref.backward(dout.to(dtype).double())
+    dW = torch.zeros(d, Fd, device=DEV)
+    db = torch.zeros(d, device=DEV)
+    HF.seq_embed_backward(dout.to(DEV, dtype), x.to(DEV), dW, db, p, seed)
+    assert _rel(dW, Wr.grad) < 2e-5 and _rel(db, br.grad) < 2e-5
+    dW2 = torch.zeros(d, Fd, device=DEV)
+    db2 = torch.zeros(d, device=DEV)
+    HF.seq_embed_backward(dout.to(DEV, dtype), x.to(DEV), dW2, db2, p, seed)
+    assert torch.equal(dW, dW2) and torch.equal(db, db2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 128), (74, 192, 128), (12288 // 8, 2048, 512)])
+def test_relu_epilogues(M, N, K, dtype):
+    p, seed = 0.1, 77
+    g = torch.Generator().manual_seed(M + N)
+    A, W, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.1, torch.randn(N, generator=g)
+    u = HF.linear_nt(A.to(DEV, dtype), W.to(DEV, dtype), b.to(DEV), epi=HF.EPI_BIAS_RELU_DROP, epi_seed=seed, epi_p=p)
+    keep = HF.dropout_mask((M, N), seed, p, DEV).double().cpu()
+    h = A.to(dtype).double() @ W.to(dtype).double().T + b.double()
+    ref = torch.relu(h) * keep
+    assert _rel(u, ref) < TOL[dtype]
+    G = torch.randn(M, K, generator=g)
+    W2T = torch.randn(N, K, generator=g) * 0.1
+    dh = HF.linear_nt(G.to(DEV, dtype), W2T.to(DEV, dtype), None, epi=HF.EPI_RELU_BWD, aux=u, epi_p=p)
+    fac = (u.double().cpu() > 0).double() / (1 - p)
+    ref_dh = (G.to(dtype).double() @ W2T.to(dtype).double().T) * fac
+    assert _rel(dh, ref_dh) < TOL[dtype]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_max_pool(dtype):
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(3, 37, 128, generator=g).to(dtype)
+    x[1, 5:9] = x[1, 4]                                       # ties: the first index wins
+    xr = x.double().requires_grad_(True)
+    ref = xr.max(dim=1).values
+    xd = x.to(DEV).requires_grad_(True)
+    out = HF.seq_max_pool(xd)
+    assert torch.equal(out.cpu().double(), ref.detach())
+    dout = torch.randn(3, 128, generator=g)
+    out.backward(dout.to(DEV))
+    ref.backward(dout.double())
+    assert torch.equal(xd.grad.double().cpu(), xr.grad.to(dtype).double())
+
+
+def _model(name, dtype=torch.float32):
+    cfg = TH.CONFIGS[name]
+    m = hw.TransformerModel(*TH.model_args(cfg))
+    w = TH.recipe_weights(m.state_dict(), cfg["seed"])
+    m.load_state_dict(w, strict=False)
+    return m.to(DEV).set_activation_dtype(dtype), w, cfg
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", ["a", "b", "c"])
+def test_model_against_fixture(name, dtype):
+    fx = load_fixture(f"transformer_{name}.npz")
+    m, w, cfg = _model(name, dtype)
+    m.eval()
+    x, y = torch.from_numpy(fx["x"]), torch.from_numpy(fx["y"]).long()
+    logits = m(x.to(DEV))
+    ref = torch.from_numpy(fx["logits"])
+    tol = 2e-4 if dtype == torch.float32 else 3e-2
+    assert _rel(logits, ref) < tol, _rel(logits, ref)
+    loss = train.SmoothedCrossEntropyLoss()(logits, y.to(DEV))
+    assert abs(loss.item() - float(fx["loss"])) < (1e-4 if dtype == torch.float32 else 2e-2)
+    loss.backward()
+    grads = {n: p.grad for n, p in m.named_parameters() if p.grad is not None}
+    # bf16: the first layer's gradients have passed through three layers of bf16 activations (measured 0.063)
+    grad_digest_check(grads, fx, "", 2e-3 if dtype == torch.float32 else 1e-1)
+
+
+def test_train_dropout_reproducible_and_active():
+    m, _, cfg = _model("b")
+    x, y = TH.make_input(cfg)
+    x = x.to(DEV)
+    m.eval()
+    ev = m(x).detach()
+    m.train()
+    torch.manual_seed(0)
+    m._drop_calls = 0
+    a = m(x).detach()
+    m._drop_calls = 0
+    b = m(x).detach()
+    assert torch.equal(a, b)
+    c = m(x).detach()
+    assert not torch.equal(a, c) and not torch.equal(a, ev)
+    for dt in (torch.float32, torch.bfloat16):           # the default (atomic) train backward with every dropout site on
+        m.set_activation_dtype(dt)
+        opt = torch.optim.AdamW(m.parameters(), lr=1e-4)
+        loss = train.TrainStep(m, opt)(x, y.to(DEV))
+        assert torch.isfinite(loss).item()
+        assert all(torch.isfinite(q.grad).all().item() for q in m.parameters())
+
+
+@pytest.mark.parametrize("name", ["a", "b", "c"])
+def test_train_dropout_sites_against_fp64(name):
+    """train mode, p = 0.1 at every site: each site's mask rebuilt with functional.dropout_mask from the model's effective
+    seeds (site seed + the step's base) -- the fp64 restatement with those masks must give the GPU logits and gradients
+    (a site hashed with another site's seed, or a backward that masks with the wrong seed, fails here), and the observed
+    keep rate of every site is 1 - p"""
+    m, w, cfg = _model(name)
+    m.train()
+    x, y = TH.make_input(cfg)
+    torch.manual_seed(11)
+    logits = m(x.to(DEV))
+    train.SmoothedCrossEntropyLoss()(logits, y.to(DEV)).backward()
+    B, T, d, nH, ff, p = cfg["B"], cfg["T"], cfg["d"], cfg["nhead"], cfg["ff"], m.drop_rate
+    mask = lambda shape, seed: HF.dropout_mask(shape, seed, p, DEV).double().cpu()
+    masks = {"embed": mask((B, T, d), m._seeds(63)[0])}
+    for k in range(cfg["layers"]):
+        s = m._seeds(k)
+        masks[(k, "drop1")], masks[(k, "ff")] = mask((B, T, d), s[0]), mask((B, T, ff), s[1])
+        masks[(k, "drop2")], masks[(k, "attn")] = mask((B, T, d), s[2]), mask((B, nH, T, T), s[3])
+    for key, mk in masks.items():
+        keep = float((mk != 0).double().mean())
+        assert abs(keep - (1 - p)) < 0.02, (key, keep)
+    ref_p = {k: v.double().requires_grad_(True) for k, v in w.items()}
+    ref = TH.restate(ref_p, x, cfg, masks=masks)
+    assert _rel(logits.detach(), ref.detach()) < 1e-4, _rel(logits.detach(), ref.detach())
+    TH.smoothed_ce(ref, y).backward()
+    for n, q in m.named_parameters():
+        e = _rel(q.grad, ref_p[n].grad, 1e-3 * ref_p[n].grad.norm().item() + 1e-30)
+        assert e < 1e-3, (n, e)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name,B", [("a", 4), ("b", 32), ("c", 32)])
+def test_deterministic_train_and_graphed_step(name, B, dtype):
+    cfg = dict(TH.CONFIGS[name], B=B)          # (deterministic weight gradients: B T a multiple of 32)
+    res = []
+    for _ in range(2):
+        m, _, _ = _model(name, dtype)
+        m.deterministic_train = True
+        m.train()
+        opt = torch.optim.AdamW(m.parameters(), lr=1e-4, fused=True, capturable=True)
+        x, y = TH.make_input(cfg)
+        step = train.TrainStep(m, opt)
+        step(x.to(DEV), y.to(DEV))
+        res.append([p.detach().clone() for p in m.parameters()])
+    assert all(torch.equal(p, q) for p, q in zip(*res))
+    # graphed step == eager step, step by step
+    m_e, _, _ = _model(name, dtype)
+    m_g, _, _ = _model(name, dtype)
+    for m in (m_e, m_g):
+        m.deterministic_train = True
+        m.train()
+    o_e = torch.optim.AdamW(m_e.parameters(), lr=1e-4, fused=True, capturable=True)
+    o_g = torch.optim.AdamW(m_g.parameters(), lr=1e-4, fused=True, capturable=True)
+    x, y = TH.make_input(cfg)
+    x, y = x.to(DEV), y.to(DEV)
+    eager = train.TrainStep(m_e, o_e)
+    graphed = train.GraphedTrainStep(m_g, o_g, x, y)
+    for _ in range(2):
+        le = eager(x, y)
+        lg = graphed(x, y)
+        assert torch.equal(le, lg)
+    assert all(torch.equal(p, q) for p, q in zip(m_e.parameters(), m_g.parameters()))
+
+
+def test_graphed_eval_bit_equal():
+    m, _, cfg = _model("a")
+    m.eval()
+    x, _ = TH.make_input(cfg)
+    x = x.to(DEV)
+    fast = serve.GraphedEval(m, x)
+    with torch.no_grad():
+        ref = m(x)
+    assert torch.equal(fast(x), ref)
+
+
+def test_adamw_trajectory_tracks_fp64():
+    cfg = TH.CONFIGS["b"]
+    m, w, _ = _model("b")
+    m.drop_rate = 0.0
+    m.train()
+    x, y = TH.make_input(cfg)
+    opt = torch.optim.AdamW(m.parameters(), lr=3e-4)
+    ref_p = {k: v.double().clone().requires_grad_(True) for k, v in w.items()}
+    names = [n for n, _ in m.named_parameters()]
+    ref_opt = torch.optim.AdamW([ref_p[n] for n in names], lr=3e-4)
+    step = train.TrainStep(m, opt)
+    for i in range(20):
+        loss = step(x.to(DEV), y.to(DEV)).item()
+        ref_opt.zero_grad()
+        rl = TH.smoothed_ce(TH.restate(ref_p, x, cfg), y)
+        rl.backward()
+        ref_opt.step()
+        assert abs(loss - rl.item()) < 2e-3 * max(1.0, abs(rl.item())), (i, loss, rl.item())
