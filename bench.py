@@ -6,11 +6,16 @@ joints -> 5 part windows (K=80), C=2, d_model=128, depths [2,2,4], 2002 classes,
 fp32, train mode with the reference defaults (dropout 0.1, stochastic attention
 drop).  Inputs are synthetic, resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 `--steps K` is the number of timed steps; the result line's `ms_per_step` is their mean wall time.  With
 `--dump-outputs DIR` the last timed step's results are written to DIR as .npy files (`dump_outputs`); every input --
 weights, clips, labels, dropout seeds -- is seeded, so two runs with the same arguments start from the same data.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps (with per-launch HIP events on every
+`--timer-every`-th of them, the `kernels` / `roofline` objects), `--dump-outputs`, the JSON line.  `--full` adds the
+measurements that take runs of their own (`extra_legs`): the same K steps again without events, the eager kernel timing
+of a `--graph` run, the `secondary` configs of the default run and the CPU baseline.
 
 N>1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), and as a plain `python bench.py --gpus N`,
@@ -577,6 +582,27 @@ def dump_outputs(model, step, out_dir):
         np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
+def extra_legs(args, world):
+    """What this run measures beyond its headline, each leg after the timed steps: nothing without --full.  With it,
+    "timer_free" = the same K steps again without per-launch HIP events (`value_without_kernel_timers`), "graph_timers" =
+    two eager steps with events after a --graph run (the replayed graph cannot carry them), "secondary" = BASELINE
+    configs[2] / [4] after the default headline on one GPU, "cpu_baseline" = the oracle on the host cores.  Call with
+    the final args (after --config 3 has set the dtype)."""
+    if not args.full:
+        return set()
+    legs = set()
+    if not args.no_kernel_timers:
+        legs.add("graph_timers" if args.graph else "timer_free")
+    default_run = (args.config == 2 and args.dtype == "f32" and args.model == "hwgate" and not args.eval_mode
+                   and not args.from_host and args.batch is None and args.micro_batch is None and not args.graph
+                   and not args.deterministic)
+    if world == 1 and default_run and not args.no_secondary:
+        legs.add("secondary")
+    if world == 1 and not args.no_cpu_baseline and args.config != 5:
+        legs.add("cpu_baseline")
+    return legs
+
+
 def dry_run(args, json_fd):
     """HWGAT_BENCH_DRYRUN=1: the launcher / rendezvous / max-over-ranks / one-JSON-line plumbing on the gloo
     backend with no model and no GPU (tests/test_dist_cpu.py); `value` is meaningless."""
@@ -616,9 +642,12 @@ def main():
                          "at the headline batch / frames / width")
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default: the config's)")
     ap.add_argument("--micro-batch", type=int, default=None, help="gradient-accumulation slice (clips)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what it does not need (see extra_legs): the same K steps without "
+                         "per-launch HIP events, the secondary configs of the default run, the CPU baseline; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary.config3_bf16 / config5_bf16 measurements the default run appends (same process, after the headline)")
+                    help="with --full: skip the secondary.config3_bf16 / config5_bf16 measurements the default run appends (same process, after the headline)")
     ap.add_argument("--no-kernel-timers", action="store_true", help="skip the per-launch HIP events (A/B runs)")
     ap.add_argument("--timer-every", type=int, default=10,
                     help="record the per-launch HIP events on every N-th step of the timed region (1 = every step).  The "
@@ -690,6 +719,7 @@ def main():
     K = c["K"] if (hgate or wgate) else c["nW"] * 16
     if args.config == 5 and args.micro_batch is None:
         args.micro_batch = 16 if args.dtype == "f32" else 32      # activation memory, DESIGN.md section 3
+    legs = extra_legs(args, world)
     torch.manual_seed(1001)                                       # reference configs.py:55-59
     if hgate:
         hp = hw.HGATEParams({"src_len": c["T"], "num_class": c["nc"]}, c["C"], dev, embed_dim=c["d0"])
@@ -743,7 +773,7 @@ def main():
     # of the timed region, not on all of them: an event pair costs ~3 us of stream time and 5-10 us of host time, and a
     # step has ~190-400 launches
     store, n_timed = {}, 0
-    graph_timers = args.graph and not args.no_kernel_timers      # per-launch events cannot sit inside a graph replay:
+    graph_timers = "graph_timers" in legs                        # per-launch events cannot sit inside a graph replay:
     if args.graph:                                               # the kernel durations come from eager steps AFTER the timed region
         args.no_kernel_timers = True
     if not args.no_kernel_timers:
@@ -778,9 +808,9 @@ def main():
     n_timed = max(n_timed, 1)
     loss = float(step.loss)
     # the same K steps once more WITHOUT any per-launch HIP events: what the event recording still costs is the
-    # difference between the two rates
+    # difference between the two rates (--full)
     elapsed_plain = None
-    if not args.no_kernel_timers:
+    if "timer_free" in legs:
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -898,10 +928,7 @@ def main():
             "hip_kernel_ms_per_step": round(hip_ms / n_timed, 3), "kernel_timer_steps": n_timed,
             "loss": round(loss, 4),
         }
-        default_run = (args.config == 2 and args.dtype == "f32" and args.model == "hwgate" and not args.eval_mode
-                       and not args.from_host and args.batch is None and args.micro_batch is None and not args.graph
-                       and not args.deterministic)
-        if world == 1 and default_run and not args.no_secondary:
+        if "secondary" in legs:
             # the headline's model / optimizer / saved activations go first; its numbers above are final
             del step, opt, model
             torch.cuda.empty_cache()
@@ -912,7 +939,7 @@ def main():
                 except Exception as exc:                    # noqa: BLE001 -- the headline above is final and must be printed
                     out["secondary"][name] = {"error": repr(exc)}
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline and args.config != 5:
+        if "cpu_baseline" in legs:
             # after the timed regions; the GPU is idle meanwhile
             out["cpu_baseline"] = cpu_baseline_wgate() if wgate else cpu_baseline(hgate=hgate)
         os.write(json_fd, (json.dumps(out) + "\n").encode())

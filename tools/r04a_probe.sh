@@ -3,9 +3,9 @@ set -o pipefail
 O=gpurun_out/r04a
 mkdir -p $O
 python sl-hwgat_amd/build.py > $O/build.log 2>&1; echo "build rc $?"
-python bench.py --no-cpu-baseline > $O/bench_default_nocpu.json 2> $O/bench_default.err; echo "default rc $?"
+python bench.py --full --no-cpu-baseline > $O/bench_default_nocpu.json 2> $O/bench_default.err; echo "default rc $?"
 for mb in 32 16 8; do
-  python bench.py --config 3 --no-cpu-baseline --micro-batch $mb > $O/bench_c3_mb$mb.json 2> $O/bench_c3_mb$mb.err; echo "c3 mb$mb rc $?"
+  python bench.py --full --config 3 --no-cpu-baseline --micro-batch $mb > $O/bench_c3_mb$mb.json 2> $O/bench_c3_mb$mb.err; echo "c3 mb$mb rc $?"
 done
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp

@@ -4,7 +4,7 @@ O=gpurun_out/r04d
 mkdir -p $O
 python sl-hwgat_amd/build.py > $O/build.log 2>&1; echo "build rc $?"
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -4 $O/pytest_gpu.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default rc $?"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default rc $?"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r04d/bench_default.json"))

@@ -6,7 +6,7 @@ python sl-hwgat_amd/build.py > $O/build.log 2>&1; echo "build rc $?"
 run() {  # tag
   NT_LAB_DTYPE=bf16 NT_LAB_STATS=1 python tools/nt_lab.py > $O/ntlab_$1.txt 2>&1; echo "ntlab $1 rc $?"
   NT_LAB_DTYPE=bf16 python tools/tn_lab.py > $O/tnlab_$1.txt 2>&1; echo "tnlab $1 rc $?"
-  python bench.py --config 3 --no-cpu-baseline > $O/bench_c3_$1.json 2> $O/bench_c3_$1.err; echo "c3 $1 rc $?"
+  python bench.py --full --config 3 --no-cpu-baseline > $O/bench_c3_$1.json 2> $O/bench_c3_$1.err; echo "c3 $1 rc $?"
 }
 run base
 cp tools/lab/nt8w_nolds.hip.txt sl-hwgat_amd/csrc/gemm_bf16_nt8w.hip

@@ -6,7 +6,7 @@ python sl-hwgat_amd/build.py > $O/build.log 2>&1; echo "build rc $?"
 timeout -k 10 900 python -m pytest tests/test_gpu_hgate.py tests/test_gpu_wgate.py -m gpu -q > $O/pytest_siblings.log 2>&1; rc=$?; echo "pytest rc $rc"; tail -4 $O/pytest_siblings.log
 [ $rc -eq 0 ] || exit $rc
 for m in hgate wgate; do for dt in f32 bf16; do
-  timeout -k 10 300 python bench.py --model $m --dtype $dt --no-cpu-baseline --no-secondary > $O/bench_${m}_${dt}.json 2> $O/bench_${m}_${dt}.err; echo "$m $dt rc $?"
+  timeout -k 10 300 python bench.py --full --model $m --dtype $dt --no-cpu-baseline --no-secondary > $O/bench_${m}_${dt}.json 2> $O/bench_${m}_${dt}.err; echo "$m $dt rc $?"
 done; done
 python - <<'PY'
 import json

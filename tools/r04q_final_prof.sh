@@ -5,15 +5,15 @@ O=gpurun_out/r04p
 R=$GRAFT_REPO_ROOT
 mkdir -p $O
 python sl-hwgat_amd/build.py > $O/build2.log 2>&1; echo "build rc $?"
-python bench.py --config 5 --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_config5_bf16.json 2> $O/bench_config5_bf16.err; echo "c5 bf16 rc $?"
-python bench.py --config 5 --dtype f32 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_config5_f32.json 2> $O/bench_config5_f32.err; echo "c5 f32 rc $?"
+python bench.py --full --config 5 --dtype bf16 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_config5_bf16.json 2> $O/bench_config5_bf16.err; echo "c5 bf16 rc $?"
+python bench.py --full --config 5 --dtype f32 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_config5_f32.json 2> $O/bench_config5_f32.err; echo "c5 f32 rc $?"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d /tmp/prof_f32 -o f32 --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-secondary --steps 10 > $R/$O/bench_under_rocprof_f32.json 2>/dev/null; echo "rocprof f32 rc $?"
+rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_f32 -o f32 --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary --steps 10 > $R/$O/bench_under_rocprof_f32.json 2>/dev/null; echo "rocprof f32 rc $?"
 cp /tmp/prof_f32/f32_kernel_stats.csv $R/$O/f32_kernel_stats.csv
-rocprofv3 --kernel-trace --stats -d /tmp/prof_c3 -o c3 --output-format csv -- python3 $R/bench.py --config 3 --no-cpu-baseline --steps 10 > $R/$O/bench_under_rocprof_config3.json 2>/dev/null; echo "rocprof c3 rc $?"
+rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_c3 -o c3 --output-format csv -- python3 $R/bench.py --full --config 3 --no-cpu-baseline --steps 10 > $R/$O/bench_under_rocprof_config3.json 2>/dev/null; echo "rocprof c3 rc $?"
 cp /tmp/prof_c3/c3_kernel_stats.csv $R/$O/config3_bf16_kernel_stats.csv
 for m in hgate wgate; do
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_$m -o $m --output-format csv -- python3 $R/bench.py --model $m --no-cpu-baseline --no-secondary --steps 10 > $R/$O/bench_under_rocprof_${m}_f32.json 2>/dev/null; echo "rocprof $m rc $?"
+  rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_$m -o $m --output-format csv -- python3 $R/bench.py --full --model $m --no-cpu-baseline --no-secondary --steps 10 > $R/$O/bench_under_rocprof_${m}_f32.json 2>/dev/null; echo "rocprof $m rc $?"
   cp /tmp/prof_$m/${m}_kernel_stats.csv $R/$O/${m}_f32_kernel_stats.csv
 done
 for c in FETCH_SIZE WRITE_SIZE; do
