@@ -39,19 +39,35 @@ def get_scheduler(optimizer, scheduler: Optional[str] = "CosineAnnealingLR"):
     return None
 
 
+def _plain(v):
+    """a 1-element tensor hyper-parameter (torch optimizers accept a tensor lr) as the Python float the reference writes;
+    lists, tuples and dicts element-wise, everything else as it is"""
+    if torch.is_tensor(v) and v.numel() == 1:
+        return float(v.item())
+    if isinstance(v, (list, tuple)):
+        return type(v)(_plain(e) for e in v)
+    if isinstance(v, dict):
+        return {k: _plain(e) for k, e in v.items()}
+    return v
+
+
 def save_checkpoint(path, model, optimizer, scheduler, train_acc_list, train_loss_list, val_acc_list, val_loss_list,
                     epoch, lr):
-    """same argument order and the same dict layout as utils.py:164-176"""
+    """same argument order and the same dict layout as utils.py:164-176.  Learning rates are written as floats even when
+    the optimizer holds them as tensors: the reference's AdamW(foreach=True) refuses a tensor lr."""
+    opt_state = optimizer.state_dict()
+    opt_state["param_groups"] = [{k: (v if k == "params" else _plain(v)) for k, v in g.items()}
+                                 for g in opt_state["param_groups"]]
     torch.save({
         "model_state_dict": model.state_dict(),
-        "optimizer_state_dict": optimizer.state_dict(),
+        "optimizer_state_dict": opt_state,
         "train_loss_list": train_loss_list,
         "val_loss_list": val_loss_list,
         "train_acc_list": train_acc_list,
         "val_acc_list": val_acc_list,
         "epoch": epoch,
         "learning_rate": lr,
-        "scheduler": scheduler.state_dict(),
+        "scheduler": _plain(scheduler.state_dict()),
     }, path)
 
 

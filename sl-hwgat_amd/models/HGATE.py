@@ -105,6 +105,7 @@ class Model(_base.Model):
         self._drop_calls = 0
         self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)   # see HWGATE.Model
         self.device_seed_counter = False
+        self._call_base = None
         self.deterministic_eval = True
         if device is not None:
             self.to(device)

@@ -216,11 +216,10 @@ class Model(DeviceSeeds, nn.Module):
             idx = self.part_index
         x = x.contiguous().float()
         pe = self.pos_encoder.pe.view(self.temporal_dim, self.embed_dim) if self.pe else None
-        if self.training:
-            self._next_step_seed()
+        seed_base = self._next_step_seed() if self.training else None     # this call's base seed: _call_base
         p_pe = self.drop_rate if (self.training and self.pe) else 0.0     # Dropout lives in PositionalEncoding
         return HF.embed(x, idx, self.B, pe, self.num_kps, self.activation_dtype, p_pe, self._site_seeds(63)[0],
-                        seed_base=self._seed_base() if self.training else None)
+                        seed_base=seed_base)
 
     def forward_features(self, x):
         h = self._embed(x)
@@ -228,7 +227,7 @@ class Model(DeviceSeeds, nn.Module):
         hand = HF.HandOver(last_block=n_blocks - 1, deterministic=self._deterministic())
         # every derived copy of the block weights this call needs (LayerNorm folds, bf16 copies, transposes for the backward)
         hand.prep = HF.weight_prep(self, self.block_list(), self.activation_dtype, torch.is_grad_enabled())
-        hand.seed_base = self._seed_base() if self.training else None
+        hand.seed_base = self._call_base if self.training else None       # the copy _embed took (DeviceSeeds._next_step_seed)
         kk = 0
         for i, stage in enumerate(self.layers):          # every block but the last feeds a LayerNorm; stage ends merge
             for j in range(len(stage.blocks)):

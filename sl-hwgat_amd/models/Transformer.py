@@ -118,13 +118,12 @@ class Model(DeviceSeeds, nn.Module):
         return self
 
     def _embed(self, x):
-        if self.training:
-            self._next_step_seed()
+        seed_base = self._next_step_seed() if self.training else None     # this call's base seed: _call_base
         p = self.drop_rate if self.training else 0.0
         T = x.shape[1]
         pe = self.pos_encoder.pe[0, :T]
         return _Embed.apply(x, self.encoder.weight, self.encoder.bias, pe, self.activation_dtype, self.pad_index, p,
-                            self._site_seeds(EMBED_SITE)[0], self._seed_base() if self.training else None)
+                            self._site_seeds(EMBED_SITE)[0], seed_base)
 
     def forward_features(self, src):
         B, T = src.shape[0], src.shape[1]
@@ -139,7 +138,7 @@ class Model(DeviceSeeds, nn.Module):
         h, pad = self._embed(x)
         det = self._deterministic()
         p = self.drop_rate if self.training else 0.0
-        seed_base = self._seed_base() if self.training else None
+        seed_base = self._call_base if self.training else None         # the copy _embed took (DeviceSeeds._next_step_seed)
         for k, layer in enumerate(self.transformer_encoder.layers):
             h = encoder_layer(h, pad, layer, self.nhead, p, p, self._site_seeds(k), seed_base, det and self.training)
         norm = self.transformer_encoder.norm

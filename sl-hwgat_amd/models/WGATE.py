@@ -85,6 +85,7 @@ class Model(_base.Model):
         self._drop_calls = 0
         self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)   # see HWGATE.Model
         self.device_seed_counter = False
+        self._call_base = None
         self.deterministic_eval = True
         if device is not None:
             self.to(device)
@@ -96,7 +97,7 @@ class Model(_base.Model):
         h = self._embed(x)
         hand = HF.HandOver(last_block=self.depths - 1, deterministic=self._deterministic())
         hand.prep = HF.weight_prep(self, self.block_list(), self.activation_dtype, torch.is_grad_enabled())
-        hand.seed_base = self._seed_base() if self.training else None
+        hand.seed_base = self._call_base if self.training else None       # the copy _embed took (DeviceSeeds._next_step_seed)
         for k in range(self.depths):                   # every block but the last feeds the next block's LayerNorm
             hand.plan[k] = (k < self.depths - 1, False)
         for k, blk in enumerate(self.layers):          # PartAttentionBlock.forward, WGATE.py:150-160

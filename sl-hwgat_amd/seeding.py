@@ -1,10 +1,11 @@
 """The device-resident dropout seed of a model (shared by HWGATE / HGATE / WGATE and the Transformer baseline).
 
-Every seeded kernel hashes with  site seed + the step's base seed, which it reads from `_seed_state[1]` on the device when
-it runs (include/hwgat_hip.h, "dropout seeds"), so a train step captured in a HIP graph (train.GraphedTrainStep) replays
-with fresh masks.  A model class mixes DeviceSeeds in front of nn.Module and calls `_init_device_seeds()` in its
-constructor; train.TrainStep, train.GraphedTrainStep and serve.GraphedEval use `_seed_state`, `_drop_calls`, `_seeds`
-and `device_seed_counter`.
+Every seeded kernel hashes with  site seed + the call's base seed, which it reads on the device when it runs
+(include/hwgat_hip.h, "dropout seeds") from the per-call copy of `_seed_state[1]` that `_next_step_seed` takes, so a train
+step captured in a HIP graph (train.GraphedTrainStep) replays with fresh masks and a backward regenerates its own
+forward's masks whatever train forwards ran in between.  A model class mixes DeviceSeeds in front of nn.Module and calls
+`_init_device_seeds()` in its constructor; train.TrainStep, train.GraphedTrainStep and serve.GraphedEval use
+`_seed_state`, `_drop_calls`, `_seeds` and `device_seed_counter`.
 """
 import torch
 
@@ -18,6 +19,7 @@ class DeviceSeeds:
         # seeded kernel adds word 1 to its (host, per-site) seed when it runs, see include/hwgat_hip.h "dropout seeds"
         self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)
         self.device_seed_counter = False                          # True: a captured train step advances the counter itself
+        self._call_base = None                                    # the latest train forward's copy of the base seed
         self.deterministic_eval = True                            # eval(): fixed-order sums, bit-reproducible logits
         self.deterministic_train = False                          # train(): the same for the whole step (slower: no float atomics anywhere)
 
@@ -36,19 +38,28 @@ class DeviceSeeds:
         return [(base + s) & 0xFFFFFFFF for s in self._site_seeds(k)]
 
     def _seed_base(self):
-        """the 1-element device view the kernels read the step's base seed from"""
+        """the 1-element device view of the base seed NOW (the latest train forward's); a forward hands its kernels the
+        per-call copy `_next_step_seed` returns instead"""
         return self._seed_state[1:2]
 
     def _next_step_seed(self):
-        """once per train-mode forward.  Eager: the host counter goes up and the four state words are rewritten from host
-        integers (kernel arguments -- no copy, no sync).  `device_seed_counter` (a captured train step, train.GraphedTrainStep):
-        the device increments its own counter, so a graph replay draws fresh masks; the host counter is then only a mirror
-        that the step object keeps in step."""
+        """once per train-mode forward; returns the base-seed word of THIS call.  Eager: the four state words are rewritten
+        from host integers (kernel arguments -- no copy, no sync).  `device_seed_counter` (a captured train step,
+        train.GraphedTrainStep): the device increments its own counter, so a graph replay draws fresh masks.  Either way
+        the host counter `_drop_calls` goes up with the device one (its mirror, what `_seeds()` reads).
+
+        Per-call rule: every kernel of one forward -- and of its backward, which regenerates the masks instead of storing
+        them -- reads the base seed from `_call_base`, a device copy of word 1 taken here (one 4-byte copy, ordered on the
+        stream; inside a capture a graph node that every replay refreshes).  `_seed_state[1]` itself is rewritten by the
+        next train forward, so a backward that read it would draw that later call's masks when two forwards run before
+        their backwards (`loss(model(a)) + loss(model(b))`)."""
         if self.device_seed_counter:
             HF.seed_advance(self._seed_state)
         else:
-            self._drop_calls += 1
-            HF.seed_set(self._seed_state, self._drop_calls, torch.initial_seed(), getattr(self, "rank_salt", 0))
+            HF.seed_set(self._seed_state, self._drop_calls + 1, torch.initial_seed(), getattr(self, "rank_salt", 0))
+        self._drop_calls += 1
+        self._call_base = self._seed_state[1:2].clone()
+        return self._call_base
 
     deterministic_train = False
 

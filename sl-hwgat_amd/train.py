@@ -62,24 +62,31 @@ class TrainStep:
 
 
 class GraphedTrainStep:
-    """The whole train step -- seed advance, forward, loss, backward, fused AdamW -- captured ONCE in a HIP graph and
-    replayed per call: one graph launch instead of ~400 kernel launches issued one by one from Python (reference loop:
-    hwgat/utils.py:93-116, which issues its ~40 ATen ops per block the same way).  Why it matters here: the bf16 steps
+    """The train step -- seed advance, forward, loss, backward -- captured ONCE in a HIP graph and replayed per call, the
+    fused AdamW step issued right after the replay: a few launches instead of ~400 issued one by one from Python
+    (reference loop: hwgat/utils.py:93-116, which issues its ~40 ATen ops per block the same way).  Why it matters here: the bf16 steps
     of the sibling models are 10-17 ms, within 10 % of what one Python thread can issue, and a node runs 8 such ranks
     (SURVEY 8e); a replay needs no host work between kernels.
 
     What makes the capture possible (round 4): nothing in a step depends on a host value that changes between steps.
     The dropout seed lives on the device (`model._seed_state`; every seeded kernel adds the step's base seed, which
     hwgat_seed_advance -- the first node of the graph -- rewrites), the train-mode thresholds of HWGATE.py:96 are drawn
-    by torch's graph-safe device generator, the optimizer is AdamW(fused=True, capturable=True) (its step counter is a
-    device tensor), and every C-ABI launch goes to torch's current stream, so HIP stream capture records it like
-    torch's own kernels.  Capture follows the torch.cuda.graphs recipe (warm-up on a side stream, then
+    by torch's graph-safe device generator, and every C-ABI launch goes to torch's current stream, so HIP stream capture
+    records it like torch's own kernels.  Capture follows the torch.cuda.graphs recipe (warm-up on a side stream, then
     `torch.cuda.graph`), in THIS process: nothing is re-launched or exec'ed.
+
+    The optimizer step stays out of the graph so that it reads the param groups' hyper-parameters when it runs: a float
+    lr captured in the graph would be frozen there (an lr scheduler would change nothing), and a tensor lr is read by
+    torch's fused AdamW as float32 -- the float lr rounded, updates that differ from the eager step's.  Out of the graph
+    it is the eager step's own call on the gradients the replay wrote, so a replay and an eager TrainStep step agree bit
+    for bit under `deterministic_train`, with any scheduler.  The optimizer must be AdamW / Adam(fused=True,
+    capturable=True): its step counts live on the device, and nothing in the step waits on the host.
 
     Inputs are copied into static buffers; `loss` / `correct` are static device tensors rewritten by every replay.
     Shapes are fixed at capture.  Parameters must not be reallocated afterwards (same rule as serve.GraphedEval).
     With `model._drop_calls = c` before construction, replay k (1-based) draws exactly the masks the eager TrainStep
-    draws in its k-th step from the same `c` (tests/test_gpu_graph.py)."""
+    draws in its k-th step from the same `c` (tests/test_gpu_graph.py).  Each forward hands its kernels a per-call copy of
+    the base seed (seeding.DeviceSeeds._next_step_seed); in the graph that copy is a node after the seed advance."""
 
     def __init__(self, model, optimizer, x, y, criterion=None, warmup=2, reducer=None):
         import importlib
@@ -121,26 +128,32 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
         with torch.cuda.graph(self.graph):
-            self.loss, self.correct = self._one()
+            self.loss, self.correct = self._one(step=False)
         # capture executed nothing: put the device counter where the host mirror says the caller left it
         model._drop_calls = start
         HF.seed_set(model._seed_state, start, torch.initial_seed(), getattr(model, "rank_salt", 0))
         self._addr = self._addresses()
+        # the static gradients every replay writes: what the optimizer step after a replay reads (put back on the
+        # parameters per call, in case something -- an eager step's zero_grad(set_to_none=True) -- detached them)
+        self._grads = [(p, p.grad) for p in model.parameters() if p.grad is not None]
 
-    def _one(self):
+    def _one(self, step=True):
         self.opt.zero_grad(set_to_none=True)
         out = self.model(self.x)
         loss = self.criterion(out, self.y)
         loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
-        self.opt.step()
+        if step:
+            self.opt.step()
         return loss.detach(), (out.detach().argmax(-1) == self.y).sum()
 
     def _addresses(self):
         return tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
 
     def __call__(self, x, y):
+        if not self.model.training:
+            raise ValueError("GraphedTrainStep replays the train() step: call model.train() first")
         if x.shape != self.x.shape or y.shape != self.y.shape:
             raise ValueError(f"captured for {tuple(self.x.shape)} / {tuple(self.y.shape)}, got {tuple(x.shape)} / {tuple(y.shape)}")
         if self._addresses() != self._addr:
@@ -151,4 +164,8 @@ class GraphedTrainStep:
             self.y.copy_(y, non_blocking=True)
         self.graph.replay()
         self.model._drop_calls += 1                      # host mirror of the device counter (model._seeds() in tests)
+        for p, g in self._grads:
+            if p.grad is not g:
+                p.grad = g
+        self.opt.step()                                  # on the gradients the replay wrote, with the current lr
         return self.loss

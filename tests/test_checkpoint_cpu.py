@@ -144,6 +144,45 @@ def test_resume_restores_optimizer_scheduler_epoch_and_lists(fx, tmp_path):
     assert all(torch.equal(x, y) for x, y in zip(a.state_dict().values(), b.state_dict().values()))
 
 
+def test_checkpoint_of_a_tensor_lr_optimizer_loads_into_the_reference_foreach_adamw(fx, tmp_path):
+    """an optimizer whose lr is a tensor (what a captured optimizer step needs to follow a schedule) under the cosine schedule: the file
+    holds every learning rate as a Python float -- optimizer param groups and scheduler state -- and loads into the
+    reference's AdamW(foreach=True), which refuses a tensor lr ("lr as a Tensor is not supported for capturable=False
+    and foreach=True"), and that optimizer takes a step"""
+    ref, mine = _pair(fx)
+    opt = torch.optim.AdamW(mine.parameters(), lr=torch.tensor(5e-4))
+    sch = ck.get_scheduler(opt)
+    for p in mine.parameters():
+        if p.requires_grad:
+            p.grad = torch.full_like(p, 1e-3)
+    for _ in range(3):
+        opt.step()
+        sch.step()
+    assert torch.is_tensor(opt.param_groups[0]["lr"]) and torch.is_tensor(sch.get_last_lr()[0])
+    path = str(tmp_path / "tensor_lr.pt")
+    ck.save_checkpoint(path, mine, opt, sch, [], [], [], [], 2, float(opt.param_groups[0]["lr"]))
+    raw = torch.load(path, map_location="cpu", weights_only=True)
+    for grp, live in zip(raw["optimizer_state_dict"]["param_groups"], opt.param_groups):
+        for key in ("lr", "initial_lr"):
+            assert type(grp[key]) is float and grp[key] == float(live[key]), key
+    st = raw["scheduler"]
+    assert all(type(v) is float for v in st["base_lrs"] + st["_last_lr"])
+    assert st["_last_lr"] == [float(opt.param_groups[0]["lr"])] and st["last_epoch"] == 3
+    assert torch.is_tensor(opt.param_groups[0]["lr"])                           # saving left the live optimizer alone
+    opt_r = torch.optim.AdamW(ref.parameters(), lr=5e-4, foreach=True)
+    sch_r = torch.optim.lr_scheduler.CosineAnnealingLR(opt_r, T_max=20, last_epoch=-1)
+    opt_r.load_state_dict(raw["optimizer_state_dict"])
+    sch_r.load_state_dict(raw["scheduler"])
+    for p in ref.parameters():
+        if p.requires_grad:
+            p.grad = torch.full_like(p, 1e-3)
+    w0 = [p.detach().clone() for p in ref.parameters()]
+    opt_r.step()
+    sch_r.step()
+    assert any(not torch.equal(a, p) for a, p in zip(w0, ref.parameters()))
+    assert abs(sch_r.get_last_lr()[0] - 5e-4 * (1 + math.cos(math.pi * 4 / 20)) / 2) < 1e-6 * 5e-4
+
+
 @pytest.mark.timeout(600)
 def test_twenty_adamw_cosine_steps_reference_equals_oracle(fx):
     """the reference's run (make_fixtures_checkpoint.py::trajectory: same parameters, clips, thresholds, optimizer and

@@ -110,6 +110,30 @@ def test_graphed_train_step_equals_the_eager_step(dtype, kind):
         s2(x, y)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("kind", ["hwgate", "hgate", "wgate"])
+def test_graphed_train_step_is_bit_equal_to_the_eager_step_when_deterministic(dtype, kind):
+    """`deterministic_train`: no float atomics anywhere in the step, so replay k and eager step k must agree bit for bit
+    -- losses and every weight -- for each GATE model (attention kinds 'win', 'blk', 'band')."""
+    steps, c0 = 5, 17
+    runs = []
+    for graphed in (False, True):
+        m = _build(dtype, kind)
+        m.deterministic_train = True
+        x, y = _batch(m)
+        o = torch.optim.AdamW([p for p in m.parameters() if p.requires_grad], lr=5e-4, fused=True, capturable=True)
+        m._drop_calls = c0
+        s = train.GraphedTrainStep(m, o, x, y) if graphed else train.TrainStep(m, o, None)
+        losses = [s(x, y).clone() for _ in range(steps)]
+        runs.append((losses, {n: p.detach().clone() for n, p in m.named_parameters()}))
+    (le, we), (lg, wg) = runs
+    for k in range(steps):
+        assert torch.equal(le[k], lg[k]), (k, float(le[k]), float(lg[k]))
+    assert float(lg[-1]) < float(lg[0])
+    for n in we:
+        assert torch.equal(we[n], wg[n]), n
+
+
 def test_graphed_step_needs_a_capturable_optimizer_and_train_mode():
     m = _build(torch.float32)
     x, y = _batch(m)

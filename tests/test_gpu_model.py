@@ -175,11 +175,24 @@ def test_dropout_train_mode_runs_and_is_stochastic():
     fx = load_fixture("cfg1.npz")
     model, cfg = build(fx, drop=0.1)
     model.train()
+    model.deterministic_train = True
+    model.threshold_override = [0.3, 0.1, 0.5, 0.2, 0.07, 0.4, 0.25, 0.6]     # HWGATE.py:96 draws these at random
     x = torch.from_numpy(fx["x"]).to(DEV)
+    model._drop_calls = 5
     a, b = model(x), model(x)
     assert torch.isfinite(a).all() and not torch.equal(a, b)
     a.sum().backward()
     assert all(torch.isfinite(p.grad).all() for p in model.parameters() if p.grad is not None)
+    if FUSED:
+        # `b`'s forward ran between `a`'s forward and backward: a's backward must still regenerate a's masks, i.e. give
+        # what a single call at the same counter gives.  (The library-GEMM formulation draws its block masks from torch's
+        # generator, not from the model's seed; the fused path is the one whose backward regenerates them.)
+        got = named_grads(model)
+        model.zero_grad(set_to_none=True)
+        model._drop_calls = 5
+        model(x).sum().backward()
+        want = named_grads(model)
+        assert got.keys() == want.keys() and all(torch.equal(got[k], want[k]) for k in want)
 
 
 @pytest.mark.parametrize("attn_p", [0.0, 0.15])
