@@ -49,6 +49,53 @@ def rel_err(a, b):
     return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
+def entrywise(a, b):
+    """largest entry-wise error relative to the largest reference entry"""
+    a, b = torch.as_tensor(a, dtype=torch.float64), torch.as_tensor(b, dtype=torch.float64)
+    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+
+
+ATTN_PARTS = ("o", "dq", "dk", "dv")
+
+
+def attn_parity(out, ref_out, dqkv, ref_dqkv, d, tol_norm, tol_entry, what="", floor=None):
+    """Parity of one attention forward + backward against its fp64 reference, part by part: the output o and the three
+    gradient parts dq, dk, dv (columns [0, d), [d, 2d), [2d, 3d) of dqkv) are each checked
+      - in norm, against that part's own reference norm (< tol_norm), and
+      - entry by entry, relative to that part's largest reference entry (< tol_entry),
+    so an error confined to one part, one head, one tile or one frame segment cannot hide in a norm over everything.
+    tol_norm / tol_entry: a number, or a {part: bound} dict.  floor: {part: tensor} whose norm / largest entry is the
+    smallest scale of that part (for parts that are analytically zero).  Returns {part: (norm error, entry error)}."""
+    def bound(tol, part):
+        return tol[part] if isinstance(tol, dict) else tol
+
+    refs = {"o": ref_out}
+    outs = {"o": out}
+    for i, part in enumerate(ATTN_PARTS[1:]):
+        outs[part] = dqkv[..., i * d:(i + 1) * d]
+        refs[part] = ref_dqkv[..., i * d:(i + 1) * d]
+    errs = {}
+    for part in ATTN_PARTS:
+        a = torch.as_tensor(outs[part].detach().cpu(), dtype=torch.float64)
+        b = torch.as_tensor(refs[part].detach().cpu(), dtype=torch.float64)
+        assert a.shape == b.shape, (what, part, tuple(a.shape), tuple(b.shape))
+        norm_scale, entry_scale = b.norm().item(), b.abs().max().item()
+        if floor is not None and part in floor:
+            fl = torch.as_tensor(floor[part].detach().cpu(), dtype=torch.float64)
+            norm_scale, entry_scale = max(norm_scale, fl.norm().item()), max(entry_scale, fl.abs().max().item())
+        diff = (a - b).abs()
+        e_norm = diff.norm().item() / max(norm_scale, 1e-30)
+        flat = int(diff.argmax())
+        e_entry = diff.flatten()[flat].item() / max(entry_scale, 1e-30)
+        errs[part] = (e_norm, e_entry)
+        where = tuple(int(i) for i in np.unravel_index(flat, tuple(a.shape)))
+        worst = f"worst entry {where}: {a.flatten()[flat].item():.6g} vs {b.flatten()[flat].item():.6g}"
+        tn, te = bound(tol_norm, part), bound(tol_entry, part)
+        assert e_norm < tn, f"{what} {part}: norm error {e_norm:.3g} >= {tn:.3g} ({worst})"
+        assert e_entry < te, f"{what} {part}: entry-wise error {e_entry:.3g} >= {te:.3g} ({worst})"
+    return errs
+
+
 def tie_free_threshold(p0, nominal, span=1.25):
     """A train-mode threshold (reference HWGATE.py:94-100) near `nominal` that no entry of the unmasked softmax `p0`
     (the fp64 oracle's, any shape) comes close to: the geometric centre of the widest relative gap between neighbouring

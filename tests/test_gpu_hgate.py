@@ -10,13 +10,19 @@ import torch
 
 from oracle import hgat_oracle as OH
 from libgemm_path import use_library_linears
-from helpers import load_fixture, hgate_oracle_from_fixture, sub, rel_err, grad_digest_check
+from helpers import load_fixture, hgate_oracle_from_fixture, sub, rel_err, grad_digest_check, attn_parity
 
 pytestmark = pytest.mark.gpu
 hw = importlib.import_module("sl-hwgat_amd")
 HF = hw.functional
 DEV = "cuda:0"
 F32_TOL, BF16_TOL = 2e-5, 1e-2
+BF16_NORM = dict(o=BF16_TOL, dq=2 * BF16_TOL, dk=2 * BF16_TOL, dv=2 * BF16_TOL)
+# entry-wise bounds of attn_parity (the worst error relative to the part's largest reference entry): about 3x the
+# worst value observed on an MI355X over this module's cases (o / dq / dk / dv in the comments), capped at 1e-4 (fp32)
+# and 2e-2 (bf16)
+BLK_ENTRY_F32 = dict(o=1e-6, dq=1.2e-6, dk=1.3e-6, dv=1e-6)             # observed 3.4e-7 / 3.7e-7 / 4.2e-7 / 3.2e-7
+BLK_ENTRY_BF16 = dict(o=1.7e-2, dq=2e-2, dk=2e-2, dv=1.6e-2)           # observed 5.5e-3 / 6.7e-3 / 7.6e-3 / 5.3e-3
 
 
 def _adj(KJ, g):
@@ -25,6 +31,18 @@ def _adj(KJ, g):
         return OH.block_adjacency()
     a = (torch.rand(KJ, KJ, generator=g) < 0.3).float()
     a = ((a + a.t() + torch.eye(KJ)) > 0).float()
+    return OH.block_adjacency(a)
+
+
+def _tile_sparse_adj(KJ, g):
+    """joints 0-15 and 16..KJ-2 form two groups without an edge between them and joint KJ-1 sees only itself: every
+    16-query tile of a frame then sees keys of two of the four 16-slot key tiles only (cross-frame links join a joint
+    to itself), so whole 16 x 16 tiles of S and of P are empty"""
+    a = torch.zeros(KJ, KJ)
+    for lo, hi in ((0, 16), (16, KJ - 1)):
+        a[lo:hi, lo:hi] = (torch.rand(hi - lo, hi - lo, generator=g) < 0.5).float()
+    a = ((a + a.t() + torch.eye(KJ)) > 0).float()
+    assert a[:16, 16:].sum() == 0 and a[KJ - 1].sum() == 1
     return OH.block_adjacency(a)
 
 
@@ -42,7 +60,10 @@ def _oracle_attn(qkv, adj, n_heads, shifted, attn_keep=None):
 
 
 @pytest.mark.parametrize("hd,nH,KJ,F,B", [(64, 2, 29, 8, 2), (64, 4, 32, 4, 3), (32, 4, 29, 6, 2), (32, 2, 17, 4, 1),
-                                          (64, 1, 1, 2, 2), (64, 2, 5, 2, 1)])
+                                          (64, 1, 1, 2, 2), (64, 2, 5, 2, 1),
+                                          # KJ 16: slots 16-31 of each frame are all padding (key tiles 1, 3 empty);
+                                          # KJ 31: one pad slot per frame; an odd head count above 1
+                                          (64, 3, 16, 4, 2), (64, 3, 31, 4, 1), (32, 3, 16, 6, 1), (32, 3, 31, 4, 2)])
 @pytest.mark.parametrize("shifted", [False, True])
 def test_block_attention_fwd_bwd(hd, nH, KJ, F, B, shifted):
     g = torch.Generator().manual_seed(hd + KJ + F)
@@ -61,6 +82,7 @@ def test_block_attention_fwd_bwd(hd, nH, KJ, F, B, shifted):
     out.backward(do.to(DEV))
     assert rel_err(out.detach().cpu(), ref.detach()) < F32_TOL
     assert rel_err(x.grad.cpu(), ref_in.grad) < F32_TOL
+    attn_parity(out, ref, x.grad, ref_in.grad, d, F32_TOL, BLK_ENTRY_F32, "block fp32")
 
     xb = qkv.to(DEV, torch.bfloat16).requires_grad_(True)
     refb_in = xb.detach().cpu().double().requires_grad_(True)
@@ -70,9 +92,39 @@ def test_block_attention_fwd_bwd(hd, nH, KJ, F, B, shifted):
     outb.backward(do.to(DEV, torch.bfloat16))
     assert rel_err(outb.detach().float().cpu(), refb.detach()) < BF16_TOL
     assert rel_err(xb.grad.float().cpu(), refb_in.grad) < 2 * BF16_TOL
+    attn_parity(outb, refb, xb.grad, refb_in.grad, d, BF16_NORM, BLK_ENTRY_BF16, "block bf16")
 
 
-@pytest.mark.parametrize("hd,nH,KJ,F,B", [(64, 2, 29, 8, 2), (64, 4, 32, 4, 3), (32, 4, 29, 6, 2), (64, 2, 5, 2, 1)])
+@pytest.mark.parametrize("hd", [32, 64])
+@pytest.mark.parametrize("KJ", [24, 31])
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("p_drop", [0.0, 0.2])
+def test_block_attention_tile_sparse(hd, KJ, shifted, p_drop):
+    """an adjacency that empties whole 16 x 16 tiles of S and of P: the ballot skip branches of blk_attn_f32.hip (hd 64,
+    fp32) for S tiles and for P / dS tiles, and the same masks in the hd-32 kernels and the bf16 16 x 16-tile kernels,
+    with and without attention dropout"""
+    g = torch.Generator().manual_seed(11 * hd + KJ + int(shifted))
+    B, F, nH, seed = 2, 4, 2, 0xBEEF03
+    d = nH * hd
+    qkv = torch.randn(B, F, KJ, 3 * d, generator=g) * 0.8
+    do = torch.randn(B, F, KJ, d, generator=g)
+    adj = _tile_sparse_adj(KJ, g)
+    bits = HF.blk_mask_bits(adj, KJ).to(DEV)
+    drop = (seed, p_drop) if p_drop > 0 else None
+    keep = HF.dropout_mask((B, F // 2, nH, 2 * KJ, 2 * KJ), seed, p_drop, DEV).cpu().double() if drop else None
+    for dtype, norm_tol, entry_tol in ((torch.float32, F32_TOL, BLK_ENTRY_F32),
+                                       (torch.bfloat16, BF16_NORM, BLK_ENTRY_BF16)):
+        x = qkv.to(DEV, dtype).requires_grad_(True)
+        ref_in = x.detach().cpu().double().requires_grad_(True)
+        ref = _oracle_attn(ref_in, adj, nH, shifted, keep)
+        ref.backward(do.to(dtype).double())
+        out = HF.block_attention(x, bits, nH, shifted, drop=drop)
+        out.backward(do.to(DEV, dtype))
+        attn_parity(out, ref, x.grad, ref_in.grad, d, norm_tol, entry_tol, f"block tile-sparse {dtype}")
+
+
+@pytest.mark.parametrize("hd,nH,KJ,F,B", [(64, 2, 29, 8, 2), (64, 4, 32, 4, 3), (32, 4, 29, 6, 2), (64, 2, 5, 2, 1),
+                                          (64, 3, 31, 4, 1), (32, 3, 16, 4, 2)])     # odd head count, 1 / 16 pad slots
 @pytest.mark.parametrize("shifted", [False, True])
 def test_block_attention_with_attention_dropout(hd, nH, KJ, F, B, shifted):
     """attn_drop_rate > 0 (reference HGATE.py:78,106): the kernels' mask is the library's hash over the element index of the
@@ -97,6 +149,7 @@ def test_block_attention_with_attention_dropout(hd, nH, KJ, F, B, shifted):
     out.backward(do.to(DEV))
     assert rel_err(out.detach().cpu(), ref.detach()) < F32_TOL
     assert rel_err(x.grad.cpu(), ref_in.grad) < F32_TOL
+    attn_parity(out, ref, x.grad, ref_in.grad, d, F32_TOL, BLK_ENTRY_F32, "block fp32 dropout")
     # a different seed is a different mask; p = 0 is the plain kernel, bit for bit; the seed may come from the device word
     other = HF.block_attention(x.detach(), bits, nH, shifted, drop=(seed + 1, p_drop))
     assert rel_err(other.cpu(), ref.detach()) > 0.05
@@ -112,6 +165,7 @@ def test_block_attention_with_attention_dropout(hd, nH, KJ, F, B, shifted):
     outb.backward(do.to(DEV, torch.bfloat16))
     assert rel_err(outb.detach().float().cpu(), refb.detach()) < BF16_TOL
     assert rel_err(xb.grad.float().cpu(), refb_in.grad) < 2 * BF16_TOL
+    attn_parity(outb, refb, xb.grad, refb_in.grad, d, BF16_NORM, BLK_ENTRY_BF16, "block bf16 dropout")
     L = hw._lib
     o = torch.empty(B, F, KJ, d, device=DEV)
     assert L.lib().hwgat_blk_attn_fwd_drop(L.ptr(x), L.ptr(o), L.ptr(bits), B, F, KJ, nH, hd, int(shifted), 0, seed, 1.0, None, None) < 0
@@ -137,6 +191,7 @@ def test_block_attention_edge_rows():
         out.sum().backward()
         assert rel_err(out.detach().cpu(), ref.detach()) < F32_TOL, shifted
         assert (x.grad.cpu() - ref_in.grad).abs().max() < 1e-5, shifted
+        attn_parity(out, ref, x.grad, ref_in.grad, d, F32_TOL, BLK_ENTRY_F32, f"block fp32 edge rows shifted={shifted}")
         # bf16 storage: the 16x16-tile backward (blk_attn_bf16.hip) has its own copy of the masks / fill / pad logic
         xb = qkv.to(DEV, torch.bfloat16).requires_grad_(True)
         refb_in = xb.detach().cpu().double().requires_grad_(True)
@@ -147,6 +202,7 @@ def test_block_attention_edge_rows():
         assert rel_err(outb.detach().float().cpu(), refb.detach()) < BF16_TOL, shifted
         assert rel_err(xb.grad.float().cpu(), refb_in.grad) < BF16_TOL, shifted
         assert bool(torch.isfinite(xb.grad).all())
+        attn_parity(outb, refb, xb.grad, refb_in.grad, d, BF16_NORM, BLK_ENTRY_BF16, f"block bf16 edge rows shifted={shifted}")
     out = HF.block_attention(qkv.to(DEV), bits, nH, False).cpu()
     v = qkv[0, 0:2, :, 2 * d:].reshape(58, d)
     assert torch.allclose(out[0, 0, 3], v.mean(0), atol=1e-5)

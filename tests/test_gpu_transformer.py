@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import transformer_helpers as TH
-from helpers import grad_digest_check, load_fixture
+from helpers import attn_parity, grad_digest_check, load_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -19,6 +19,11 @@ train = importlib.import_module("sl-hwgat_amd.train")
 serve = importlib.import_module("sl-hwgat_amd.serve")
 DEV = torch.device("cuda:0")
 TOL = {torch.float32: 2e-5, torch.bfloat16: 1e-2}
+# entry-wise bounds of attn_parity on hwgat_seq_attn_* (the worst error relative to the part's largest reference
+# entry): about 3x the worst value observed on an MI355X over this module's cases (o / dq / dk / dv in the
+# comments), capped at 1e-4 (fp32) and 2e-2 (bf16)
+SEQ_ENTRY = {torch.float32: dict(o=4e-6, dq=5.5e-6, dk=4e-6, dv=3.3e-6),        # observed 1.2e-6 / 1.8e-6 / 1.3e-6 / 1.1e-6
+             torch.bfloat16: dict(o=1.1e-2, dq=1.9e-2, dk=2e-2, dv=1.5e-2)}    # observed 3.6e-3 / 6.3e-3 / 6.5e-3 / 5.0e-3
 
 
 def _pad_pattern(kind, B, T):
@@ -30,6 +35,10 @@ def _pad_pattern(kind, B, T):
     elif kind == "allpad":
         pad[1] = True
         pad[0, T // 2:] = True
+    elif kind == "mixed":            # B = 3: tail-padded, fully padded (the middle clip), scattered
+        pad[0, T - max(1, T // 3):] = True
+        pad[1] = True
+        pad[2, 1::3] = True
     return pad
 
 
@@ -49,37 +58,59 @@ def _rel(a, b, floor=1e-30):
     return ((a - b).norm() / b.norm().clamp_min(floor)).item()
 
 
+def _seq_case(B, T, nH, dtype, kind, p, g):
+    """one hwgat_seq_attn_* forward + backward against TH.attention, in norm and entry by entry per part"""
+    d = 64 * nH
+    qkv = torch.randn(B, T, 3 * d, generator=g)
+    do = torch.randn(B, T, d, generator=g)
+    pad = _pad_pattern(kind, B, T)
+    words = _pad_words(pad)
+    qkv_d = qkv.to(DEV, dtype)
+    seed = 1234 + T
+    drop = (seed, p) if p > 0 else None
+    o, lse = HF.seq_attn_forward(qkv_d, words, nH, drop)
+    dq1 = HF.seq_attn_backward(qkv_d, o, do.to(DEV, dtype), lse, words, nH, drop)
+    dq2 = HF.seq_attn_backward(qkv_d, o, do.to(DEV, dtype), lse, words, nH, drop)
+    assert torch.equal(dq1, dq2), "seq_attn backward is not bit-reproducible"
+    keep = HF.dropout_mask((B, nH, T, T), seed, p, DEV).double().cpu() if p > 0 else None
+    qr = qkv_d.double().cpu().requires_grad_(True)
+    ref = TH.attention(qr, pad, nH, keep)
+    ref.backward(do.to(dtype).double())
+    tol = TOL[dtype]
+    assert _rel(o, ref.detach()) < tol, (kind, p, "o", _rel(o, ref.detach()))
+    for part, sl in (("dq", slice(0, d)), ("dk", slice(d, 2 * d)), ("dv", slice(2 * d, 3 * d))):
+        # (T = 1: dq, dk are analytically 0 and what is left is rounding -- measured against the whole gradient)
+        floor = qr.grad.norm().item() if (T == 1 and part != "dv") else 0.0
+        e = _rel(dq1[..., sl], qr.grad[..., sl], max(floor, 1e-30))
+        assert e < tol, (kind, p, part, e)
+    attn_parity(o, ref, dq1, qr.grad, d, tol, SEQ_ENTRY[dtype], f"seq {dtype} {kind} p={p}",
+                floor={"dq": qr.grad, "dk": qr.grad} if T == 1 else None)
+    return o, dq1
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("T", [1, 7, 64, 192, 193, 512])
+@pytest.mark.parametrize("T", [1, 7, 32, 33, 64, 192, 193, 512])
 def test_seq_attn_against_fp64(T, dtype):
-    B, nH, d = 2, 2, 128
+    B, nH = 2, 2
     g = torch.Generator().manual_seed(T)
     for kind in ("none", "tail", "scattered", "allpad"):
         for p in (0.0, 0.2):
-            qkv = torch.randn(B, T, 3 * d, generator=g)
-            do = torch.randn(B, T, d, generator=g)
-            pad = _pad_pattern(kind, B, T)
-            words = _pad_words(pad)
-            qkv_d = qkv.to(DEV, dtype)
-            seed = 1234 + T
-            drop = (seed, p) if p > 0 else None
-            o, lse = HF.seq_attn_forward(qkv_d, words, nH, drop)
-            dq1 = HF.seq_attn_backward(qkv_d, o, do.to(DEV, dtype), lse, words, nH, drop)
-            dq2 = HF.seq_attn_backward(qkv_d, o, do.to(DEV, dtype), lse, words, nH, drop)
-            assert torch.equal(dq1, dq2), "seq_attn backward is not bit-reproducible"
-            keep = HF.dropout_mask((B, nH, T, T), seed, p, DEV).double().cpu() if p > 0 else None
-            qr = qkv_d.double().cpu().requires_grad_(True)
-            ref = TH.attention(qr, pad, nH, keep)
-            ref.backward(do.to(dtype).double())
-            tol = TOL[dtype]
-            assert _rel(o, ref.detach()) < tol, (kind, p, "o", _rel(o, ref.detach()))
-            for part, sl in (("dq", slice(0, d)), ("dk", slice(d, 2 * d)), ("dv", slice(2 * d, 3 * d))):
-                # (T = 1: dq, dk are analytically 0 and what is left is rounding -- measured against the whole gradient)
-                floor = qr.grad.norm().item() if (T == 1 and part != "dv") else 0.0
-                e = _rel(dq1[..., sl], qr.grad[..., sl], max(floor, 1e-30))
-                assert e < tol, (kind, p, part, e)
+            o, dq1 = _seq_case(B, T, nH, dtype, kind, p, g)
             if kind == "allpad":
                 assert float(o[1].abs().max()) == 0.0 and float(dq1[1].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("nH", [1, 3, 8])
+@pytest.mark.parametrize("T", [1, 32, 33, 97])
+def test_seq_attn_heads_and_batch(T, nH, dtype):
+    """head counts 1, 3 and 8 (grid.y), three clips with the fully padded one in the middle (grid.z), T on and one past a
+    32-frame padding word and a 64-row tile"""
+    g = torch.Generator().manual_seed(100 * nH + T)
+    for p in (0.0, 0.2):
+        o, dq1 = _seq_case(3, T, nH, dtype, "mixed", p, g)
+        assert float(o[1].abs().max()) == 0.0 and float(dq1[1].abs().max()) == 0.0
+        assert float(o[2].abs().max()) > 0.0 and (T == 1 or float(o[0].abs().max()) > 0.0)   # (T = 1: clip 0 is all pad)
 
 
 def test_seq_attn_refuses_other_shapes():
