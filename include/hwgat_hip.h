@@ -51,7 +51,10 @@ extern "C" {
  *   4003  widths that are odd multiples of 64 (additions only): the NT linears take N % 64 == 0, the TN linears
  *         N % 64 == K % 64 == 0, the LayerNorm family every d = 64 n <= 1024
  *   4004  the Transformer baseline (additions only): hwgat_seq_attn_{fwd,bwd}, hwgat_seq_embed_{fwd,bwd}(_bytes),
- *         hwgat_seq_maxpool_{fwd,bwd}; NT epilogues 7 / 8 (ReLU + dropout and its backward) */
+ *         hwgat_seq_maxpool_{fwd,bwd}; NT epilogues 7 / 8 (ReLU + dropout and its backward)
+ *         later additions under the same number (no existing signature changed): hwgat_wband_attn_{fwd,bwd}(_drop), the
+ *         band attention for windows of 1..32 joints (GATE, WGATE with window_size != 16); hwgat_lnwpool_fwd(_det) /
+ *         hwgat_lnwpool_bwd_masked, LayerNorm + weighted token pool (GATE) */
 #define HWGAT_ABI_VERSION 4004
 int hwgat_abi_version(void);
 
@@ -256,6 +259,27 @@ int hwgat_band_attn_bwd_drop(const void* qkv, const void* dO, void* dqkv, const 
                              int nH, int hd, int dtype, uint32_t drop_seed, float drop_p, const uint32_t* seed_base,
                              void* stream);
 
+/* ---- wide band attention: the same band form for windows ("frames") of W <= 32 joints -- GATE (GATE.py:40-70, one
+ * window = all K <= 32 joints, nW = 1) and WGATE with window_size != 16.  K = nW * W joints per frame.
+ *   qkv (B,F,K,3,nH,hd), o / do (B,F,K,nH,hd), dqkv as qkv, all `dtype`
+ *   maskrows (nW, 32, 3) uint32: word [w][i][t] bit j = key joint j of frame f-1+t visible to query joint i of frame f,
+ *            the same for every f; rows i >= W and bits j >= W are 0.  The diagonal need not be set; a row without any
+ *            visible key yields zeros.  functional.wband_mask_rows builds and validates them.
+ *   1 <= W <= 32, hd in {16, 32}, any F >= 1.  fp32 storage runs fp32 MFMA, bf16 storage bf16 MFMA (softmax in fp32).
+ * Results do not depend on the batch order or on how the launcher cuts a clip into frame segments, bit for bit. */
+int hwgat_wband_attn_fwd(const void* qkv, void* o, const uint32_t* maskrows, int B, int F, int nW, int W, int nH, int hd,
+                         int dtype, void* stream);
+int hwgat_wband_attn_bwd(const void* qkv, const void* dO, void* dqkv, const uint32_t* maskrows, int B, int F, int nW,
+                         int W, int nH, int hd, int dtype, void* stream);
+/* ... with attention dropout: mask over the element index of the reference's DENSE (B nW, nH, F W, F W) attention tensor
+ * (token = frame * W + joint); hwgat_dropout_mask_f32(out, B nW nH (F W)^2, drop_seed, drop_p) is the whole mask. */
+int hwgat_wband_attn_fwd_drop(const void* qkv, void* o, const uint32_t* maskrows, int B, int F, int nW, int W, int nH,
+                              int hd, int dtype, uint32_t drop_seed, float drop_p, const uint32_t* seed_base,
+                              void* stream);
+int hwgat_wband_attn_bwd_drop(const void* qkv, const void* dO, void* dqkv, const uint32_t* maskrows, int B, int F, int nW,
+                              int W, int nH, int hd, int dtype, uint32_t drop_seed, float drop_p,
+                              const uint32_t* seed_base, void* stream);
+
 /* debug: one v_mfma_f32_16x16x4_f32 with a (16x4), b (4x16) row-major -> out (64 lanes x 4 regs) */
 int hwgat_debug_mfma16x16x4(const float* a, const float* b, float* out, void* stream);
 
@@ -279,6 +303,22 @@ int hwgat_lnpool_bwd(const float* g, const void* x, const float* mean, const flo
 int hwgat_lnpool_bwd_masked(const float* g, const void* x, const float* mean, const float* rstd,
                             void* dx, int B, int n_tok, int d, int dtype, void* dx_masked, uint32_t mask_seed,
                             float mask_p, const uint32_t* seed_base, void* stream);
+
+/* ---- final LayerNorm + WEIGHTED token pool (GATE.py:181, 208-210: weightedAvg = nn.Linear(T K, 1) over the token axis):
+ *   xhat_wsum[b][c] = sum_t wtok[t] xhat[b][t][c]   (the caller applies gamma, beta sum(wtok) and the bias)
+ *   x (B, n_tok, d) `dtype`; wtok (n_tok) fp32; mean, rstd (B*n_tok) fp32 saved; d in {128, 256, 512, 1024}.
+ *   hwgat_lnwpool_fwd: fp32 atomics, xhat_wsum must be ZERO on entry.  _det: `partial` as hwgat_lnpool_fwd_det
+ *   (B * hwgat_lnpool_partial_rows(B, n_tok) * d floats), fixed summation order; partial == NULL is the atomic form. */
+int hwgat_lnwpool_fwd(const void* x, const float* wtok, float* xhat_wsum, float* mean, float* rstd,
+                      int B, int n_tok, int d, int dtype, void* stream);
+int hwgat_lnwpool_fwd_det(const void* x, const float* wtok, float* xhat_wsum, float* mean, float* rstd,
+                          int B, int n_tok, int d, int dtype, float* partial, void* stream);
+/* backward: g (B, d) fp32 = dfeat * gamma -> dx (B, n_tok, d) (token t's upstream gradient is wtok[t] g[b]) and
+ * gdot (B, n_tok) fp32 = sum_c g[b][c] xhat[b][t][c], the per-clip share of d wtok[t]; dx_masked / mask_* as
+ * hwgat_lnpool_bwd_masked (dx_masked may be NULL). */
+int hwgat_lnwpool_bwd_masked(const float* g, const float* wtok, const void* x, const float* mean, const float* rstd,
+                             void* dx, float* gdot, int B, int n_tok, int d, int dtype, void* dx_masked,
+                             uint32_t mask_seed, float mask_p, const uint32_t* seed_base, void* stream);
 
 /* ---- a-9: TemporalMerging (HWGATE.py:55-63): (B,F,K,d) -> (B,F/2,K,2d),
  * out[b,fi,k,tp*d+c] = in[b,2fi+tp,k,c]; `inverse` = 1 maps gradients back. */

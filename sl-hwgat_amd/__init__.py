@@ -15,9 +15,11 @@ from .parts import part_table
 from .models.HWGATE import Model
 from .models.HGATE import Model as HGATEModel
 from .models.WGATE import Model as WGATEModel
+from .models.GATE import Model as GATEModel
 from .models.Transformer import Model as TransformerModel
-from .models.model_params import HWGATEParams, HGATEParams, WGATEParams, TransformerParams
+from .models.model_params import HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams
 
-__all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "TransformerModel",
+__all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
+           "TransformerModel",
            "TransformerParams", "functional",
            "part_table", "_lib", "checkpoint", "augment"]

@@ -232,10 +232,13 @@ __global__ __launch_bounds__(256) void ln_bwd_k(const T* __restrict__ dy, const 
 
 // ------------------------------------------------------------------ LN + pool
 // xhat_sum[b][c] += sum over this wave's tokens of (x - mean) * rstd
-template <typename T, int D>
+// WT: the weighted token pool of GATE (GATE.py:181,210, weightedAvg over the token axis): every token's term is
+// multiplied by its weight wtok[t]
+template <typename T, int D, bool WT = false>
 __global__ __launch_bounds__(256) void lnpool_fwd_k(const T* __restrict__ x, float* __restrict__ xhat_sum,
                                                     float* __restrict__ mean_o, float* __restrict__ rstd_o,
-                                                    int n_tok, int chunks, float* __restrict__ partial) {
+                                                    int n_tok, int chunks, float* __restrict__ partial,
+                                                    const float* __restrict__ wtok = nullptr) {
     using M = RowMap<D>;
     __shared__ float red[4][D];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -254,10 +257,18 @@ __global__ __launch_bounds__(256) void lnpool_fwd_k(const T* __restrict__ x, flo
         load_row<T, D>(x + r * D, sub, v);
         float mean, rstd;
         row_stats<D>(v, mean, rstd);
+        if constexpr (WT) {
+            const float wr = wtok[t] * rstd;
 #pragma unroll
-        for (int c = 0; c < M::CPL; ++c)
+            for (int c = 0; c < M::CPL; ++c)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[c][e] += (v[c][e] - mean) * rstd;
+                for (int e = 0; e < 4; ++e) acc[c][e] += (v[c][e] - mean) * wr;
+        } else {
+#pragma unroll
+            for (int c = 0; c < M::CPL; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[c][e] += (v[c][e] - mean) * rstd;
+        }
         if (sub == 0) { mean_o[r] = mean; rstd_o[r] = rstd; }
     }
     if constexpr (M::RPW == 2) {
@@ -293,12 +304,16 @@ __global__ void lnpool_reduce_k(const float* __restrict__ partial, float* __rest
 }
 
 // the upstream gradient of every token of clip b is the same vector g[b] (fp32)
-template <typename T, int D>
+// WT (weighted token pool): token t's upstream gradient is wtok[t] g[b]; the LayerNorm backward is linear in it, so dx
+// is scaled by wtok[t], and gdot[b][t] = sum_c g[b][c] xhat[b][t][c] (the token's share of d wtok) is stored on the way
+template <typename T, int D, bool WT = false>
 __global__ __launch_bounds__(256) void lnpool_bwd_k(const float* __restrict__ g, const T* __restrict__ x,
                                                     const float* __restrict__ mean_i,
                                                     const float* __restrict__ rstd_i, T* __restrict__ dx,
                                                     int n_tok, int chunks, T* __restrict__ dxm, uint32_t mseed,
-                                                    float mp, const uint32_t* __restrict__ sbase) {
+                                                    float mp, const uint32_t* __restrict__ sbase,
+                                                    const float* __restrict__ wtok = nullptr,
+                                                    float* __restrict__ gdot = nullptr) {
     using M = RowMap<D>;
     mseed += seed_base_of(sbase);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -324,11 +339,14 @@ __global__ __launch_bounds__(256) void lnpool_bwd_k(const float* __restrict__ g,
         for (int c = 0; c < M::CPL; ++c)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[c][e] = (v[c][e] - mean) * rstd; s2 += gv[c][e] * v[c][e]; }
-        s2 = wave_sum<M::LPR>(s2) * (1.0f / D);
+        s2 = wave_sum<M::LPR>(s2);
+        if constexpr (WT) { if (sub == 0) gdot[r] = s2; }
+        s2 *= (1.0f / D);
+        const float wr = WT ? wtok[t] * rstd : rstd;
 #pragma unroll
         for (int c = 0; c < M::CPL; ++c)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[c][e] = rstd * (gv[c][e] - s1 - v[c][e] * s2);
+            for (int e = 0; e < 4; ++e) v[c][e] = wr * (gv[c][e] - s1 - v[c][e] * s2);
         store_row<T, D>(dx + r * D, sub, v);
         if (dxm != nullptr) {                                   // see ln_bwd_k<.., MASK>
             const uint32_t th = drop_thresh(mp);
@@ -605,6 +623,50 @@ extern "C" int hwgat_lnpool_bwd_masked(const float* g, const void* x, const floa
     const int ch = pool_chunks(B, n_tok);
     if (hwgat_lnw_takes(d)) return hwgat_lnw_pool_bwd(g, x, mean, rstd, dx, B, n_tok, ch, d, dtype, dxm, mseed, mp, seed_base, st);
 #define GO(T, D) lnpool_bwd_k<T, D><<<B * ch, 256, 0, st>>>(g, (const T*)x, mean, rstd, (T*)dx, n_tok, ch, (T*)dxm, mseed, mp, seed_base)
+    if (dtype == HWGAT_F32) { SW(float) }
+    else if (dtype == HWGAT_BF16) { SW(bf16_t) }
+    else return HWGAT_EDTYPE;
+#undef GO
+#undef SW
+    HWGAT_LAUNCH_CHECK();
+}
+
+// ---- LayerNorm + weighted token pool (GATE.py:208-210): xhat_wsum[b][c] = sum_t wtok[t] xhat[b][t][c]
+extern "C" int hwgat_lnwpool_fwd_det(const void* x, const float* wtok, float* xhat_wsum, float* mean, float* rstd, int B,
+                                     int n_tok, int d, int dtype, float* partial, void* stream) {
+    if (!x || !wtok || !xhat_wsum || !mean || !rstd || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = pool_chunks(B, n_tok);
+#define GO(T, D) lnpool_fwd_k<T, D, true><<<B * ch, 256, 0, st>>>((const T*)x, xhat_wsum, mean, rstd, n_tok, ch, partial, wtok)
+#define SW(T)                                  \
+    switch (d) {                               \
+        case 128: GO(T, 128); break;           \
+        case 256: GO(T, 256); break;           \
+        case 512: GO(T, 512); break;           \
+        case 1024: GO(T, 1024); break;         \
+        default: return HWGAT_ESHAPE;          \
+    }
+    if (dtype == HWGAT_F32) { SW(float) }
+    else if (dtype == HWGAT_BF16) { SW(bf16_t) }
+    else return HWGAT_EDTYPE;
+#undef GO
+    if (partial) lnpool_reduce_k<<<B, 256, 0, st>>>(partial, xhat_wsum, ch, d);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_lnwpool_fwd(const void* x, const float* wtok, float* xhat_wsum, float* mean, float* rstd, int B,
+                                 int n_tok, int d, int dtype, void* stream) {
+    return hwgat_lnwpool_fwd_det(x, wtok, xhat_wsum, mean, rstd, B, n_tok, d, dtype, nullptr, stream);
+}
+
+extern "C" int hwgat_lnwpool_bwd_masked(const float* g, const float* wtok, const void* x, const float* mean,
+                                        const float* rstd, void* dx, float* gdot, int B, int n_tok, int d, int dtype,
+                                        void* dxm, uint32_t mseed, float mp, const uint32_t* seed_base, void* stream) {
+    if (!g || !wtok || !x || !mean || !rstd || !dx || !gdot || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
+    if (dxm && (mp <= 0.f || mp >= 1.f)) return HWGAT_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = pool_chunks(B, n_tok);
+#define GO(T, D) lnpool_bwd_k<T, D, true><<<B * ch, 256, 0, st>>>(g, (const T*)x, mean, rstd, (T*)dx, n_tok, ch, (T*)dxm, mseed, mp, seed_base, wtok, gdot)
     if (dtype == HWGAT_F32) { SW(float) }
     else if (dtype == HWGAT_BF16) { SW(bf16_t) }
     else return HWGAT_EDTYPE;

@@ -152,6 +152,58 @@ def band_mask_rows(adj: torch.Tensor, frames: int) -> torch.Tensor:
     return rows.contiguous()
 
 
+def wband_mask_rows(adj: torch.Tensor, frames: int, window_size: int) -> torch.Tensor:
+    """0/1 adjacency of a band model with W = `window_size` <= 32 joints per window and frame -- WGATE's
+    (nW, T*W, T*W) (reference model_params.py:209-228) or GATE's (T*K, T*K) with W = K (model_params.py:60-73) -> the
+    (nW, 32, 3) int32 words `hwgat_wband_attn_*` consume: bit j of word [w][i][t] = key joint j of frame f-1+t visible
+    to query joint i of frame f; rows i >= W stay 0.  The kernel never forms the (T*W)^2 matrix, so the adjacency must be
+    block-tridiagonal over frames with the same three W x W blocks on every frame, and every query joint needs a visible
+    key in its own frame (its softmax row must not be empty at the clip ends).  The diagonal itself need not be set
+    (GATE has no self loops).  Anything else raises with the rule it breaks."""
+    W, T = int(window_size), int(frames)
+    if not 1 <= W <= 32:
+        raise NotImplementedError(f"window_size {W}: the wide band attention kernels take windows of at most 32 joints "
+                                  f"(one 32-bit mask word per key frame)")
+    a = adj.detach().to("cpu")
+    if a.dim() == 2:
+        a = a.unsqueeze(0)
+    if a.dim() != 3 or a.shape[1] != T * W or a.shape[2] != T * W:
+        raise ValueError(f"band adjacency must be (nW, T*W, T*W) or (T*W, T*W) with T*W = {T * W}, got {tuple(adj.shape)}")
+    nW = a.shape[0]
+    if not bool(((a == 0) | (a == 1)).all()):
+        raise ValueError("adjacency must be a 0/1 matrix")
+    blk = (a != 0).view(nW, T, W, T, W).permute(0, 1, 3, 2, 4)             # [w][fq][fk][i][j]
+    off = torch.arange(T).view(1, T) - torch.arange(T).view(T, 1)          # fk - fq
+    if bool(blk[:, off.abs() > 1].any()):
+        raise NotImplementedError("the band attention kernels need a block-tridiagonal adjacency (frames f-1, f, f+1)")
+    rows = torch.zeros(nW, 32, 3, dtype=torch.int64)
+    weights = 2 ** torch.arange(W, dtype=torch.int64)
+    for t, o in enumerate((-1, 0, 1)):
+        sel = blk[:, off == o]                                             # (nW, n, W, W)
+        if sel.shape[1] == 0:
+            continue
+        if not bool((sel == sel[:, :1]).all()):
+            raise NotImplementedError("the band attention kernels need the same adjacency blocks on every frame")
+        rows[:, :W, t] = (sel[:, 0].to(torch.int64) * weights).sum(-1)
+    if not bool(rows[:, :W, 1].ne(0).all()):
+        raise NotImplementedError("every query joint needs a visible key in its own frame")
+    return torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32).contiguous()
+
+
+def _wband_shape(o, rows, n_heads):
+    """(B, F, nW, W, head_dim) of a 'wband' launch; nW comes from the (nW, 32, 3) mask words"""
+    B, F, K, d = o.shape
+    if rows.dtype != torch.int32 or rows.dim() != 3 or tuple(rows.shape[1:]) != (32, 3):
+        raise ValueError("'wband' attention needs the (nW, 32, 3) int32 words of functional.wband_mask_rows")
+    nW = rows.shape[0]
+    if K % nW or K // nW > 32:
+        raise ValueError(f"mask words are for {nW} windows, activations have {K} joints per frame")
+    hd = d // n_heads
+    if d % n_heads or hd not in (16, 32):
+        raise NotImplementedError(f"head_dim {d / n_heads:g}: the wide band attention kernels take head_dim 16 or 32")
+    return B, F, nW, K // nW, hd
+
+
 # ---------------------------------------------------------------- embedding
 def embed(x, idx, bmat, pe, K, out_dtype=torch.float32, drop_p=0.0, seed=0, seed_base=None):
     """gather + Fourier features + PE (+ dropout) (no gradient: B is frozen, PE a buffer).
@@ -248,7 +300,8 @@ def _pwin_shape(o, bits, n_heads):
 
 def attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop=None):
     """launch the attention forward of a model family: 'win' = HWGATE part windows (W = 16), 'pwin' = HWGATE part
-    windows of any other size W <= 32 (W from `bits`, functional.pwin_mask_bits), 'blk' = HGATE blocks, 'band' = WGATE.
+    windows of any other size W <= 32 (W from `bits`, functional.pwin_mask_bits), 'blk' = HGATE blocks, 'band' = WGATE
+    (W = 16), 'wband' = GATE and WGATE with any other W <= 32 (functional.wband_mask_rows).
     `drop` = (seed, p) or (seed, p, seed_base): attention dropout ('win', train mode only)"""
     B, F, K, d = o.shape
     drop = _attn_drop(kind, thr, drop)
@@ -282,6 +335,14 @@ def attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop=None):
         else:
             call("hwgat_band_attn_fwd", ptr(qkv), ptr(o), ptr(bits), B, F, K // 16, n_heads, d // n_heads,
                  dtype_code(qkv), stream())
+    elif kind == "wband":
+        assert thr is None and not shifted, "the band models have neither threshold nor shift"
+        B_, F_, nW, W, hd = _wband_shape(o, bits, n_heads)
+        if drop is not None:
+            call("hwgat_wband_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), B_, F_, nW, W, n_heads, hd, dtype_code(qkv),
+                 drop[0], drop[1], ptr(drop[2]), stream())
+        else:
+            call("hwgat_wband_attn_fwd", ptr(qkv), ptr(o), ptr(bits), B_, F_, nW, W, n_heads, hd, dtype_code(qkv), stream())
     else:
         raise ValueError(kind)
 
@@ -317,6 +378,14 @@ def attn_bwd(kind, qkv, do, dqkv, bits, thr, n_heads, shifted, drop=None):
         else:
             call("hwgat_band_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B, F, K // 16, n_heads, d // n_heads,
                  dtype_code(qkv), stream())
+    elif kind == "wband":
+        B_, F_, nW, W, hd = _wband_shape(do, bits, n_heads)
+        if drop is not None:
+            call("hwgat_wband_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B_, F_, nW, W, n_heads, hd,
+                 dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
+        else:
+            call("hwgat_wband_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B_, F_, nW, W, n_heads, hd,
+                 dtype_code(qkv), stream())
     else:
         raise ValueError(kind)
 
@@ -343,28 +412,35 @@ class _BlkAttn(torch.autograd.Function):
 
 class _BandAttn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, rows, n_heads, drop):
+    def forward(ctx, qkv, rows, n_heads, drop, kind="band"):
         B, F, K, d3 = qkv.shape
         o = torch.empty(B, F, K, d3 // 3, device=qkv.device, dtype=qkv.dtype)
-        attn_fwd("band", qkv, o, rows, None, n_heads, False, drop)
+        attn_fwd(kind, qkv, o, rows, None, n_heads, False, drop)
         ctx.save_for_backward(qkv, rows)
-        ctx.cfg = (n_heads, drop)
+        ctx.cfg = (n_heads, drop, kind)
         return o
 
     @staticmethod
     def backward(ctx, do):
         qkv, rows = ctx.saved_tensors
-        n_heads, drop = ctx.cfg
+        n_heads, drop, kind = ctx.cfg
         do = do.contiguous()
         dqkv = torch.empty_like(qkv)
-        attn_bwd("band", qkv, do, dqkv, rows, None, n_heads, False, drop)
-        return dqkv, None, None, None
+        attn_bwd(kind, qkv, do, dqkv, rows, None, n_heads, False, drop)
+        return dqkv, None, None, None, None
 
 
 def band_attention(qkv, rows, n_heads, drop=None):
     """WGATE: qkv (B,F,K,3d) -> o (B,F,K,d); a window = one 16-joint part window over all F frames.
     `drop` = (seed, p[, seed_base]): attention dropout (reference WGATE.py:103)."""
     return _BandAttn.apply(qkv.contiguous(), rows, n_heads, _attn_drop("band", None, drop))
+
+
+def wband_attention(qkv, rows, n_heads, drop=None):
+    """GATE / WGATE with a window size other than 16: qkv (B,F,K,3d) -> o (B,F,K,d); a window = W <= 32 joints over all
+    F frames, K = nW * W; `rows` = functional.wband_mask_rows(adj, F, W) on the device.
+    `drop` = (seed, p[, seed_base]): attention dropout (reference GATE.py:65, WGATE.py:103)."""
+    return _BandAttn.apply(qkv.contiguous(), rows, n_heads, _attn_drop("wband", None, drop), "wband")
 
 
 def block_attention(qkv, bits, n_heads, shifted, drop=None):
@@ -459,6 +535,66 @@ def ln_mean_pool(x, gamma, beta, carrier=None, up=None, book=None, deterministic
     if carrier is not None and (xcont is not x or carrier.shape != x.shape or book is None):
         carrier = None
     return _LnPool.apply(xcont, gamma, beta, carrier, up, book, bool(deterministic), seed_base)
+
+
+class _LnWeightedPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w, bias, xc=None, up=None, book=None, deterministic=False, seed_base=None):
+        ctx.up = up if (xc is not None and up is not None and up[1] > 0.0 and book is not None) else None
+        ctx.book = book
+        ctx.seed_base = seed_base
+        B, d = x.shape[0], x.shape[-1]
+        n_tok = x.numel() // (B * d)
+        wt = w.detach().reshape(-1).float().contiguous()
+        if wt.numel() != n_tok:
+            raise ValueError(f"the pool has {wt.numel()} token weights, the activations have {n_tok} tokens per clip")
+        mean = torch.empty(B * n_tok, device=x.device, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        if deterministic:      # per-block partial sums added in index order: the same bits on every run
+            rows = _lib.lib().hwgat_lnpool_partial_rows(B, n_tok)
+            hat = torch.empty(B, d, device=x.device, dtype=torch.float32)
+            part = torch.empty(B * rows, d, device=x.device, dtype=torch.float32)
+            call("hwgat_lnwpool_fwd_det", ptr(x), ptr(wt), ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x),
+                 ptr(part), stream())
+        else:
+            hat = torch.zeros(B, d, device=x.device, dtype=torch.float32)
+            call("hwgat_lnwpool_fwd", ptr(x), ptr(wt), ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x), stream())
+        ctx.save_for_backward(x, gamma, beta, wt, mean, rstd, hat)
+        ctx.w_shape = w.shape
+        return hat * gamma + (beta * wt.sum() + bias.reshape(()))
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        x, gamma, beta, wt, mean, rstd, hat = ctx.saved_tensors
+        B, d = x.shape[0], x.shape[-1]
+        n_tok = x.numel() // (B * d)
+        dfeat = dfeat.float()
+        g = (dfeat * gamma).contiguous()
+        dx = torch.empty_like(x)
+        dxm = torch.empty_like(x) if ctx.up is not None else None
+        gdot = torch.empty(B, n_tok, device=x.device, dtype=torch.float32)
+        call("hwgat_lnwpool_bwd_masked", ptr(g), ptr(wt), ptr(x), ptr(mean), ptr(rstd), ptr(dx), ptr(gdot), B, n_tok, d,
+             dtype_code(x), ptr(dxm), (ctx.up[0] if ctx.up else 0) & 0xFFFFFFFF, float(ctx.up[1]) if ctx.up else 0.0,
+             ptr(ctx.seed_base), stream())
+        if dxm is not None:
+            ctx.book.register(dx, dxm)
+        dsum = dfeat.sum(0)                                                 # (d)
+        # d w[t] = sum_b sum_c dfeat[b,c] (gamma_c xhat[b,t,c] + beta_c): the kernel did the channel sums per (b, t)
+        dw = (gdot.sum(0) + (dsum * beta).sum()).reshape(ctx.w_shape)
+        return dx, (dfeat * hat).sum(0), dsum * wt.sum(), dw, dsum.sum().reshape(1), dxm, None, None, None, None
+
+
+def ln_weighted_pool(x, gamma, beta, w, bias, carrier=None, up=None, book=None, deterministic=False, seed_base=None):
+    """final LayerNorm + weighted pool over all tokens (reference GATE.py:208-210, `weightedAvg = nn.Linear(T K, 1)` applied
+    along the token axis): feat[b, c] = sum_tok w[tok] LN(x)[b, tok, c] + bias -> (B, d) fp32.  w (n_tok) or (1, n_tok),
+    bias (1).  Gradients to x, gamma, beta, w and bias.  carrier / up / book / deterministic / seed_base: as ln_mean_pool.
+    Widths 128, 256, 512 and 1024."""
+    xcont = x.contiguous()
+    if xcont.shape[-1] not in (128, 256, 512, 1024):
+        raise NotImplementedError(f"width {xcont.shape[-1]}: the weighted token pool takes d in 128, 256, 512, 1024")
+    if carrier is not None and (xcont is not x or carrier.shape != x.shape or book is None):
+        carrier = None
+    return _LnWeightedPool.apply(xcont, gamma, beta, w, bias, carrier, up, book, bool(deterministic), seed_base)
 
 
 # ---------------------------------------------------------------- fp32 MFMA linears

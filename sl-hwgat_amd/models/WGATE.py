@@ -6,12 +6,13 @@ size), has the same `forward(x: (B,T,K,C)) -> (B,num_classes)` and the same `sta
 -- `layers.{i}.<...>` directly (no stages) and the (nW, T*16, T*16) additive `adj_mask` buffer of
 WGATE.py:190-196 -- so checkpoints interchange.
 
-An attention window is one 16-joint part window over ALL T frames.  The reference forms the dense
-(T*16)^2 scores and adds 0 / -10000; its adjacency is block-tridiagonal over frames, so every masked
-probability is exactly 0 in fp32 and `hwgat_band_attn_fwd/bwd` (csrc/band_attn.hip) only ever touch the
-three neighbouring key frames.  Embedding, LayerNorms, fused linears and the final norm + pool are the
+An attention window is one W-joint part window over ALL T frames.  The reference forms the dense
+(T*W)^2 scores and adds 0 / -10000; its adjacency is block-tridiagonal over frames, so every masked
+probability is exactly 0 in fp32 and `hwgat_band_attn_fwd/bwd` (csrc/band_attn.hip, W = 16) or
+`hwgat_wband_attn_fwd/bwd` (csrc/wband_attn.hip, any other W <= 32) only ever touch the three
+neighbouring key frames.  Embedding, LayerNorms, fused linears and the final norm + pool are the
 kernels HWGATE uses, unchanged.  `adj_mask` is kept only for the state_dict contract; the kernels read
-the (nW,16) bit rows derived from `adj_mat`.
+the mask rows derived from `adj_mat`.
 """
 import torch
 from torch import nn
@@ -27,15 +28,19 @@ class Model(_base.Model):
                  depths=16, num_heads=8, window_size=16, ff_ratio=4., adj_mat=None, drop_rate=0.,
                  attn_drop_rate=0., norm_layer=nn.LayerNorm, device=None) -> None:
         nn.Module.__init__(self)
+        window_size = int(window_size)
+        if not 1 <= window_size <= 32:
+            raise NotImplementedError(f"window_size {window_size}: the WGATE HIP backend takes part windows of at most 32 "
+                                      f"joints (one 32-slot frame per window in the band attention kernels)")
         if window_size != 16:
-            raise NotImplementedError("WGATE HIP backend supports window_size == 16")
+            self._attn_kind = "wband"                  # W = 16 stays on the "band" kernels, unchanged
         if not 0.0 <= float(attn_drop_rate) < 1.0:
             raise ValueError("attn_drop_rate must be in [0, 1)")
         self.attn_drop_rate = float(attn_drop_rate)          # nn.Dropout on the attention probabilities (WGATE.py:81,103)
         if norm_layer is not nn.LayerNorm:
             raise NotImplementedError("norm_layer must be nn.LayerNorm")
         if adj_mat is None:
-            raise NotImplementedError("WGATE needs its (nW, T*16, T*16) adjacency (the reference dereferences it too)")
+            raise NotImplementedError("WGATE needs its (nW, T*W, T*W) adjacency (the reference dereferences it too)")
         assert num_kps % window_size == 0, "window size and number of kps are incompatible"
         d = embed_dim
         if d not in _base._SUPPORTED_WIDTHS or d % num_heads or (d // num_heads) not in (16, 32):
@@ -47,9 +52,13 @@ class Model(_base.Model):
         self.drop_rate, self.ff_ratio = float(drop_rate), ff_ratio
         self.window_size = window_size
         self.num_features = embed_dim
-        self.n_windows = num_kps // 16
+        self.n_windows = num_kps // window_size
 
-        rows = HF.band_mask_rows(adj_mat, temporal_dim)        # validates the structure the kernel relies on
+        # either builder validates the structure its kernel relies on
+        rows = (HF.band_mask_rows(adj_mat, temporal_dim) if window_size == 16
+                else HF.wband_mask_rows(adj_mat, temporal_dim, window_size))
+        if rows.shape[0] != self.n_windows:
+            raise ValueError(f"adjacency has {rows.shape[0]} windows, num_kps / window_size = {self.n_windows}")
         self.adj_mask_name = "adj_mask"                        # WGATE.py:190-196: 0 -> -10000, 1 -> 0
         self.register_buffer("adj_mask", adj_mat.to(torch.float32).masked_fill(adj_mat == 0, float(-10000))
                              .masked_fill(adj_mat == 1, float(0)))

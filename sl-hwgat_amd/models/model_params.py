@@ -68,6 +68,45 @@ _BODY_EDGES = [(2, 0), (1, 0), (0, 3), (0, 4), (3, 5), (4, 6), (5, 7), (6, 8), (
 _HAND_EDGES = [(0, 1), (0, 2), (2, 3), (2, 4), (4, 5), (0, 4), (4, 6), (0, 6), (6, 7), (6, 8), (0, 8), (8, 9)]
 
 
+class GATEParams:
+    """Drop-in for `GATEParams` of the reference (model_params.py:5-76): same attributes, defaults and positional
+    14-tuple.  The adjacency is the dense (T*K, T*K) block-tridiagonal matrix the reference builds: the symmetric joint
+    graph inside a frame, the same joint in the neighbouring frames -- and NO identity: a joint does not see itself."""
+
+    def __init__(self, dataset_params, input_dim, device=None):
+        self.kp_dim = input_dim
+        self.num_kps = 29
+        self.temporal_dim = dataset_params['src_len']
+        self.num_classes = dataset_params['num_class']
+        self.embed_dim = 128
+        self.pe = True
+        self.depths = 8
+        self.num_heads = 8
+        self.ff_ratio = 2.
+        self.drop_rate = 0.1
+        self.attn_drop_rate = 0.0
+        self.norm_layer = nn.LayerNorm
+        self.device = device
+        self.edges = ([list(e) for e in _BODY_EDGES[:-1]] + [[9 + a, 9 + b] for a, b in _HAND_EDGES]
+                      + [list(_BODY_EDGES[-1])] + [[19 + a, 19 + b] for a, b in _HAND_EDGES])
+        self.adj_mat = torch.tensor(self.get_adj(self.edges, self.temporal_dim, self.num_kps), dtype=torch.float32)
+
+    def get_adj(self, spatial_links, num_fr, num_kp):
+        """(T*K, T*K): same frame -> the symmetric joint graph (no self loops), next / previous frame -> same joint."""
+        e = np.asarray(spatial_links)
+        frame = np.zeros((num_kp, num_kp))
+        frame[e[:, 0], e[:, 1]] = 1
+        frame[e[:, 1], e[:, 0]] = 1
+        gap = np.abs(np.arange(num_fr)[:, None] - np.arange(num_fr)[None, :])
+        blocks = np.where(gap[:, :, None, None] == 0, frame, np.where(gap[:, :, None, None] == 1, np.eye(num_kp), 0.0))
+        return blocks.transpose(0, 2, 1, 3).reshape(num_fr * num_kp, num_fr * num_kp)
+
+    def get_model_params(self):
+        return (self.kp_dim, self.num_kps, self.temporal_dim, self.num_classes, self.embed_dim, self.pe, self.depths,
+                self.num_heads, self.ff_ratio, self.adj_mat, self.drop_rate, self.attn_drop_rate, self.norm_layer,
+                self.device)
+
+
 class HGATEParams:
     """Drop-in for `HGATEParams` of the reference (model_params.py:405-486): same attributes, defaults and
     positional tuple (no window_size: an attention block is all joints of 2 frames)."""
