@@ -54,8 +54,11 @@ extern "C" {
  *         hwgat_seq_maxpool_{fwd,bwd}; NT epilogues 7 / 8 (ReLU + dropout and its backward)
  *         later additions under the same number (no existing signature changed): hwgat_wband_attn_{fwd,bwd}(_drop), the
  *         band attention for windows of 1..32 joints (GATE, WGATE with window_size != 16); hwgat_lnwpool_fwd(_det) /
- *         hwgat_lnwpool_bwd_masked, LayerNorm + weighted token pool (GATE) */
-#define HWGAT_ABI_VERSION 4004
+ *         hwgat_lnwpool_bwd_masked, LayerNorm + weighted token pool (GATE)
+ *   4005  the ST-GCN baseline (additions only): hwgat_stgcn_weight_prep, hwgat_stgcn_conv, hwgat_stgcn_conv_dw(_bytes),
+ *         hwgat_stgcn_colsum, hwgat_stgcn_red_bytes, hwgat_stgcn_bn_{stats,eval_stats,apply,bwd},
+ *         hwgat_stgcn_agg_{fwd,bwd}(_bytes), hwgat_stgcn_pool_{fwd,bwd}, hwgat_stgcn_copy_cols */
+#define HWGAT_ABI_VERSION 4005
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -546,6 +549,73 @@ int hwgat_seq_embed_bwd(const void* dout, const float* x, float* dW, float* db, 
                         uint32_t seed, float p, const uint32_t* seed_base, float* ws, int64_t ws_bytes, void* stream);
 int hwgat_seq_maxpool_fwd(const void* x, float* out, int32_t* idx, int B, int T, int d, int dtype, void* stream);
 int hwgat_seq_maxpool_bwd(const float* dout, const int32_t* idx, void* dx, int B, int T, int d, int dtype, void* stream);
+
+/* ---- ST-GCN baseline (ABI 4005; reference hwgat/models/STGCN.py).  fp32 only.  Activations are channels-last
+ * (N, T, V, C): M = N T V rows of C floats, a BatchNorm channel is a column.  No kernel of this group uses an atomic:
+ * every cross-block sum goes through partial images added in a fixed order, so every result is bit-reproducible.
+ *
+ * Convolutions.  All three convolutions of a block (1x1 graph-conv projection, 9x1 temporal, strided 1x1 residual) are
+ * one implicit GEMM: output row (n, t, v), reduction over taps x Cin, tap k reading input frame stride * t + k - pad of
+ * the same clip and joint, zero outside [0, Tin).  Cin (as passed) a multiple of 32, Cout a multiple of 32, taps 1..9,
+ * stride 1 or 2, Tout = (Tin + 2 pad - taps) / stride + 1 (else HWGAT_ESHAPE).
+ * hwgat_stgcn_weight_prep: W (Cout, Cin, taps, 1) master -> out, mode 0: [tap][ci < CinP][co] (rows ci >= Cin zero),
+ *   mode 1: [tap][co][ci < CinP].
+ * hwgat_stgcn_conv: mode 0: out (Nc, Tout, V, Cout) = conv(in (Nc, Tin, V, Cin); wk = mode-0 image) + bias.
+ *   mode 1: the input gradient: in = dL/dy (Nc, Tin = frames of y, V, Cin = channels of y), wk = mode-1 image,
+ *   out (Nc, Tout = frames of x, V, Cout = channels of x, padded).  bias, add, mask may be NULL;
+ *   out += add, or += add * [mask > 0] when mask is given (both shaped like out).
+ * hwgat_stgcn_conv_dw: dW (Cout, Cin, taps, 1) = sum_m dy[m][co] in[src(m, tap)][ci] (written, not accumulated);
+ *   in has CinP >= Cin channels per row (CinP a multiple of 32); ws >= hwgat_stgcn_conv_dw_bytes(Nc Tout V, CinP, Cout,
+ *   taps) bytes, need not be zeroed. */
+int hwgat_stgcn_weight_prep(const float* W, float* out, int Cout, int Cin, int taps, int CinP, int mode, void* stream);
+int hwgat_stgcn_conv(const float* in, const float* wk, const float* bias, const float* add, const float* mask,
+                     float* out, int Nc, int Tin, int Tout, int V, int Cin, int Cout, int taps, int stride, int pad,
+                     int mode, void* stream);
+int64_t hwgat_stgcn_conv_dw_bytes(int64_t M, int CinP, int Cout, int taps);
+int hwgat_stgcn_conv_dw(const float* in, const float* dy, float* dW, int Nc, int Tin, int Tout, int V, int CinP, int Cin,
+                        int Cout, int taps, int stride, int pad, float* ws, int64_t ws_bytes, void* stream);
+
+/* Column reductions and BatchNorm over M rows of C columns.  ws: >= hwgat_stgcn_red_bytes(C) bytes, need not be zeroed.
+ * hwgat_stgcn_colsum: out (C) = column sums of x (a convolution's bias gradient).
+ * hwgat_stgcn_bn_stats: mean, rstd = 1 / sqrt(biased variance + eps) of every column (shifted sums: exact for a mean far
+ *   above the deviation); running_mean / running_var (both or neither) <- (1 - momentum) old + momentum (mean, unbiased
+ *   variance), *num_batches += 1 (int64, may be NULL), all on the device.  M < 2: HWGAT_ESHAPE.
+ * hwgat_stgcn_bn_eval_stats: mean = running_mean, rstd = 1 / sqrt(running_var + eps).
+ * hwgat_stgcn_bn_apply: out = (x - mean) rstd gamma + beta (+ res, itself normalised with the res_* set when res_mean is
+ *   given), then max(., 0) if relu.
+ * hwgat_stgcn_bn_bwd: g = dy, or dy [y > 0] when y (the forward's ReLU output) is given; dbeta = sum g, dgamma = sum g xhat
+ *   (written); dx = gamma rstd (g - (dbeta + xhat dgamma) / M) with train != 0, gamma rstd g with running statistics. */
+int64_t hwgat_stgcn_red_bytes(int C);
+int hwgat_stgcn_colsum(const float* x, float* out, int64_t M, int C, float* ws, int64_t ws_bytes, void* stream);
+int hwgat_stgcn_bn_stats(const float* x, int64_t M, int C, float eps, float momentum, float* mean, float* rstd,
+                         float* running_mean, float* running_var, int64_t* num_batches, float* ws, int64_t ws_bytes,
+                         void* stream);
+int hwgat_stgcn_bn_eval_stats(const float* rm, const float* rv, float eps, float* mean, float* rstd, int C, void* stream);
+int hwgat_stgcn_bn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const float* res, const float* res_mean, const float* res_rstd, const float* res_gamma,
+                         const float* res_beta, float* out, int64_t M, int C, int relu, void* stream);
+int hwgat_stgcn_bn_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd,
+                       const float* gamma, float* dx, float* dgamma, float* dbeta, int64_t M, int C, int train, float* ws,
+                       int64_t ws_bytes, void* stream);
+
+/* Graph aggregation over the V <= 32 joints of each of NT frames, Ae = A o E ((3, V, V) each; E NULL = ones).
+ * hwgat_stgcn_agg_fwd: out (NT, V, C)[f, w, c] = sum_{k, v} Ae[k, v, w] y[f, v, k C + c], y (NT, V, 3 C).
+ * hwgat_stgcn_agg_bwd: dy (NT, V, 3 C) from d = dL/dout, and, when dE is not NULL, dE[k, v, w] = A[k, v, w] sum_{f, c}
+ *   y[f, v, k C + c] d[f, w, c] (written; C a multiple of 32; ws >= hwgat_stgcn_agg_bwd_bytes(NT) bytes).
+ * hwgat_stgcn_pool_fwd: out (N, C) = mean over the R rows of each clip of x (N, R, C), times the head-dropout factor of
+ *   (seed + *seed_base, index n C + c) -- what hwgat_dropout_mask_f32 writes for an (N, C) tensor; p = 0: no dropout.
+ * hwgat_stgcn_pool_bwd: dx (N, R, C) = dout[n, c] factor / R.
+ * hwgat_stgcn_copy_cols: dst (rows, ld_dst)[r, c] = src (rows, ld_src)[r, c] for c < ld_src, 0 beyond (pads or crops
+ *   the channel dimension of the 2- or 3-channel input to a GEMM-able width and back). */
+int hwgat_stgcn_agg_fwd(const float* y, const float* A, const float* E, float* out, int64_t NT, int V, int C, void* stream);
+int64_t hwgat_stgcn_agg_bwd_bytes(int64_t NT);
+int hwgat_stgcn_agg_bwd(const float* y, const float* d, const float* A, const float* E, float* dy, float* dE, int64_t NT,
+                        int V, int C, float* ws, int64_t ws_bytes, void* stream);
+int hwgat_stgcn_pool_fwd(const float* x, float* out, int N, int R, int C, uint32_t seed, float p,
+                         const uint32_t* seed_base, void* stream);
+int hwgat_stgcn_pool_bwd(const float* dout, float* dx, int N, int R, int C, uint32_t seed, float p,
+                         const uint32_t* seed_base, void* stream);
+int hwgat_stgcn_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, int64_t rows, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,9 +17,10 @@ from .models.HGATE import Model as HGATEModel
 from .models.WGATE import Model as WGATEModel
 from .models.GATE import Model as GATEModel
 from .models.Transformer import Model as TransformerModel
-from .models.model_params import HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams
+from .models.STGCN import Model as STGCNModel
+from .models.model_params import HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams, STGCNParams
 
 __all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
            "TransformerModel",
-           "TransformerParams", "functional",
+           "TransformerParams", "STGCNModel", "STGCNParams", "functional",
            "part_table", "_lib", "checkpoint", "augment"]

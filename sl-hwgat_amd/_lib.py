@@ -93,6 +93,22 @@ _SIGS = {
     "hwgat_seq_embed_bwd": [_P, _P, _P, _P, _L, _I, _I, _I, _U, _F, _P, _P, _L, _P],
     "hwgat_seq_maxpool_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
     "hwgat_seq_maxpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "hwgat_stgcn_weight_prep": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "hwgat_stgcn_conv": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "hwgat_stgcn_conv_dw_bytes": [_L, _I, _I, _I],
+    "hwgat_stgcn_conv_dw": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
+    "hwgat_stgcn_red_bytes": [_I],
+    "hwgat_stgcn_colsum": [_P, _P, _L, _I, _P, _L, _P],
+    "hwgat_stgcn_bn_stats": [_P, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P, _L, _P],
+    "hwgat_stgcn_bn_eval_stats": [_P, _P, _F, _P, _P, _I, _P],
+    "hwgat_stgcn_bn_apply": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P],
+    "hwgat_stgcn_bn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _L, _P],
+    "hwgat_stgcn_agg_fwd": [_P, _P, _P, _P, _L, _I, _I, _P],
+    "hwgat_stgcn_agg_bwd_bytes": [_L],
+    "hwgat_stgcn_agg_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _L, _P],
+    "hwgat_stgcn_pool_fwd": [_P, _P, _I, _I, _I, _U, _F, _P, _P],
+    "hwgat_stgcn_pool_bwd": [_P, _P, _I, _I, _I, _U, _F, _P, _P],
+    "hwgat_stgcn_copy_cols": [_P, _I, _P, _I, _L, _P],
 }
 _lib = None
 

@@ -1049,3 +1049,158 @@ class _SeqMaxPool(torch.autograd.Function):
 def seq_max_pool(x):
     """max over the frames of (B, T, d) -> (B, d) fp32 (first index of the maximum, as torch.max)"""
     return _SeqMaxPool.apply(x.contiguous())
+
+
+# ---------------------------------------------------------------- ST-GCN baseline (models/STGCN.py, stgcn_block.py)
+# fp32, channels-last (N, T, V, C).  Thin launchers of csrc/stgcn_conv.hip / stgcn_ops.hip; nothing here is differentiable
+# by itself (the autograd nodes are in stgcn_block.py).
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+STGCN_MAX_NODES = 32
+
+
+def _ws(nbytes, device):
+    if nbytes <= 0:
+        raise NotImplementedError("shape not supported by the ST-GCN kernels")
+    return torch.empty(nbytes // 4, device=device, dtype=torch.float32), nbytes
+
+
+def pad32(c):
+    return (c + 31) // 32 * 32
+
+
+def stgcn_weight_image(W, mode, cin_pad=None):
+    """the k-major image of a conv master weight (C_out, C_in, taps, 1): mode 0 (taps, CinP, C_out) for the forward,
+    mode 1 (taps, C_out, CinP) for the input gradient; rows / columns C_in .. CinP are zero"""
+    Cout, Cin, taps = W.shape[0], W.shape[1], W.shape[2]
+    CinP = cin_pad or Cin
+    out = torch.empty((taps, CinP, Cout) if mode == 0 else (taps, Cout, CinP), device=W.device, dtype=torch.float32)
+    call("hwgat_stgcn_weight_prep", ptr(W), ptr(out), Cout, Cin, taps, CinP, mode, stream())
+    return out
+
+
+def stgcn_conv(x, wk, bias, stride=1, pad=0):
+    """(N, T, V, Cin) -> (N, T_out, V, Cout) with the mode-0 image wk (taps, Cin, Cout)"""
+    N, T, V, Cin = x.shape
+    taps, _, Cout = wk.shape
+    To = (T + 2 * pad - taps) // stride + 1
+    out = torch.empty(N, To, V, Cout, device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_conv", ptr(x), ptr(wk), ptr(bias), None, None, ptr(out), N, T, To, V, Cin, Cout, taps, stride, pad, 0,
+         stream())
+    return out
+
+
+def stgcn_conv_dx(dy, wkt, t_x, stride=1, pad=0, add=None, mask=None):
+    """input gradient (N, t_x, V, CxP) of a convolution from dy (N, T_y, V, Cy) and the mode-1 image wkt (taps, Cy, CxP);
+    `add` (+ `mask`): out += add [mask > 0]"""
+    N, Ty, V, Cy = dy.shape
+    taps, _, Cx = wkt.shape
+    out = torch.empty(N, t_x, V, Cx, device=dy.device, dtype=torch.float32)
+    call("hwgat_stgcn_conv", ptr(dy), ptr(wkt), None, ptr(add), ptr(mask), ptr(out), N, Ty, t_x, V, Cy, Cx, taps, stride, pad,
+         1, stream())
+    return out
+
+
+def stgcn_conv_dw(x, dy, w_shape, stride=1, pad=0):
+    """weight gradient in the master layout `w_shape` = (C_out, C_in, taps, 1); x may carry padded channels"""
+    N, T, V, CinP = x.shape
+    Cout, Cin, taps = w_shape[0], w_shape[1], w_shape[2]
+    To = dy.shape[1]
+    ws, nbytes = _ws(_lib.lib().hwgat_stgcn_conv_dw_bytes(N * To * V, CinP, Cout, taps), x.device)
+    dW = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_conv_dw", ptr(x), ptr(dy), ptr(dW), N, T, To, V, CinP, Cin, Cout, taps, stride, pad, ptr(ws), nbytes,
+         stream())
+    return dW
+
+
+def stgcn_colsum(x):
+    C = x.shape[-1]
+    M = x.numel() // C
+    ws, nbytes = _ws(_lib.lib().hwgat_stgcn_red_bytes(C), x.device)
+    out = torch.empty(C, device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_colsum", ptr(x), ptr(out), M, C, ptr(ws), nbytes, stream())
+    return out
+
+
+def stgcn_bn_stats(x, running_mean=None, running_var=None, num_batches=None, eps=BN_EPS, momentum=BN_MOMENTUM):
+    """batch (mean, rstd) of the columns of x (..., C); the running values are updated on the device"""
+    C = x.shape[-1]
+    M = x.numel() // C
+    if M < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    ws, nbytes = _ws(_lib.lib().hwgat_stgcn_red_bytes(C), x.device)
+    st = torch.empty(2, C, device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_bn_stats", ptr(x), M, C, float(eps), float(momentum), ptr(st[0]), ptr(st[1]), ptr(running_mean),
+         ptr(running_var), ptr(num_batches), ptr(ws), nbytes, stream())
+    return st[0], st[1]
+
+
+def stgcn_bn_eval_stats(running_mean, running_var, eps=BN_EPS):
+    C = running_mean.shape[0]
+    st = torch.empty(2, C, device=running_mean.device, dtype=torch.float32)
+    call("hwgat_stgcn_bn_eval_stats", ptr(running_mean), ptr(running_var), float(eps), ptr(st[0]), ptr(st[1]), C, stream())
+    return st[0], st[1]
+
+
+def stgcn_bn_apply(x, mean, rstd, gamma, beta, relu, res=None, res_bn=None):
+    """relu?(bn(x) + res) ; res_bn = (mean, rstd, gamma, beta) normalises the residual operand too"""
+    C = x.shape[-1]
+    out = torch.empty_like(x)
+    rb = res_bn or (None, None, None, None)
+    call("hwgat_stgcn_bn_apply", ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(res), ptr(rb[0]), ptr(rb[1]),
+         ptr(rb[2]), ptr(rb[3]), ptr(out), x.numel() // C, C, int(bool(relu)), stream())
+    return out
+
+
+def stgcn_bn_backward(dy, y, x, mean, rstd, gamma, train):
+    """(dx, dgamma, dbeta); y = the ReLU output behind this BatchNorm (gates dy) or None"""
+    C = x.shape[-1]
+    ws, nbytes = _ws(_lib.lib().hwgat_stgcn_red_bytes(C), x.device)
+    dx = torch.empty_like(x)
+    dg = torch.empty(2, C, device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_bn_bwd", ptr(dy), ptr(y), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx), ptr(dg[0]), ptr(dg[1]),
+         x.numel() // C, C, int(bool(train)), ptr(ws), nbytes, stream())
+    return dx, dg[0], dg[1]
+
+
+def stgcn_aggregate(y, A, E):
+    """(N, T, V, 3C) -> (N, T, V, C): sum_{k,v} (A o E)[k, v, w] y[.., v, k C + c]"""
+    N, T, V, C3 = y.shape
+    out = torch.empty(N, T, V, C3 // 3, device=y.device, dtype=torch.float32)
+    call("hwgat_stgcn_agg_fwd", ptr(y), ptr(A), ptr(E), ptr(out), N * T, V, C3 // 3, stream())
+    return out
+
+
+def stgcn_aggregate_backward(y, d, A, E, want_dE):
+    """(dy, dE or None) of stgcn_aggregate"""
+    N, T, V, C3 = y.shape
+    dy = torch.empty_like(y)
+    dE = ws = None
+    nbytes = 0
+    if want_dE:
+        dE = torch.empty_like(A)
+        ws, nbytes = _ws(_lib.lib().hwgat_stgcn_agg_bwd_bytes(N * T), y.device)
+    call("hwgat_stgcn_agg_bwd", ptr(y), ptr(d), ptr(A), ptr(E), ptr(dy), ptr(dE), N * T, V, C3 // 3, ptr(ws), nbytes, stream())
+    return dy, dE
+
+
+def stgcn_pool(x, p=0.0, seed=0, seed_base=None):
+    """(N, R, C) -> (N, C): mean over R, head dropout (mask of an (N, C) tensor) fused"""
+    N, R, C = x.shape
+    out = torch.empty(N, C, device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_pool_fwd", ptr(x), ptr(out), N, R, C, seed & 0xFFFFFFFF, float(p), ptr(seed_base), stream())
+    return out
+
+
+def stgcn_pool_backward(dout, R, p=0.0, seed=0, seed_base=None):
+    N, C = dout.shape
+    dx = torch.empty(N, R, C, device=dout.device, dtype=torch.float32)
+    call("hwgat_stgcn_pool_bwd", ptr(dout), ptr(dx), N, R, C, seed & 0xFFFFFFFF, float(p), ptr(seed_base), stream())
+    return dx
+
+
+def stgcn_copy_cols(x, width):
+    """the last dimension of x padded with zeros (or cropped) to `width`"""
+    C = x.shape[-1]
+    out = torch.empty(*x.shape[:-1], width, device=x.device, dtype=torch.float32)
+    call("hwgat_stgcn_copy_cols", ptr(x), C, ptr(out), width, x.numel() // C, stream())
+    return out

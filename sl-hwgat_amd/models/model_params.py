@@ -219,3 +219,36 @@ class TransformerParams:
     def get_model_params(self):
         return (self.input_dim * self.num_kp, self.nclass, self.pad_index, self.d_model, self.nhead, self.dim_feedforward,
                 self.num_encoder_layers, self.dropout, self.max_len, self.pool)
+
+
+# the 34 skeleton links of the 29-joint upper-body graph, in the order of the reference's STGCNParams.edges_
+# (hwgat/models/model_params.py:500-535): face and arms 0-9, left hand 9-18 (wrist 9), right hand 19-28 (wrist 19)
+_STGCN_EDGES = ((2, 0), (1, 0), (0, 3), (0, 4), (3, 5), (4, 6), (5, 7), (6, 8), (7, 9),
+                (9, 10), (9, 11), (11, 12), (11, 13), (13, 14), (9, 13), (13, 15), (9, 15), (15, 16), (15, 17), (9, 17),
+                (17, 18), (8, 19),
+                (19, 27), (19, 20), (19, 21), (19, 23), (19, 25), (21, 22), (21, 23), (23, 24), (23, 25), (25, 26),
+                (25, 27), (27, 28))
+
+
+def _stgcn_edges():
+    return [list(e) for e in _STGCN_EDGES]
+
+
+class STGCNParams:
+    """the reference's STGCNParams (hwgat/models/model_params.py:490-538): same attributes, defaults, edge list and
+    positional tuple"""
+
+    def __init__(self, dataset_params, input_dim, device=None) -> None:
+        self.kp_dim = input_dim
+        self.num_kps = 29
+        self.num_classes = dataset_params['num_class']
+        self.center = 0
+        self.edge_importance_weighting = True
+        self.n_out_features = 256
+        self.dropout_ratio = 0.05
+        self.batch_norm = False
+        self.edges_ = _stgcn_edges()
+
+    def get_model_params(self):
+        return (self.kp_dim, self.num_kps, self.center, self.edges_, self.edge_importance_weighting, self.n_out_features,
+                self.num_classes, self.dropout_ratio, self.batch_norm)
