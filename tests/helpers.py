@@ -96,6 +96,97 @@ def attn_parity(out, ref_out, dqkv, ref_dqkv, d, tol_norm, tol_entry, what="", f
     return errs
 
 
+def tensor_parity(got, ref, *, tol_norm, tol_entry, tol_row=None, tol_col=None, tile=None, tol_tile=None, what=""):
+    """Parity of one 2-D result (leading dimensions are flattened) against its fp64 reference, on the reference's device:
+      - finite everywhere,
+      - in norm over the whole result, as rel_err (< tol_norm),
+      - entry by entry, relative to the largest reference entry, as entrywise (< tol_entry),
+      - row by row when tol_row is given: the L2 error of each row over the RMS row norm of the reference,
+        ref.norm() / sqrt(rows) -- a row that is analytically zero still has a scale (< tol_row),
+      - column by column when tol_col is given, in the same way (< tol_col),
+      - tile by tile when tile = (th, tw) is given: the error of each th x tw block against that block's own reference
+        norm (< tol_tile); ragged edge blocks are checked with what they hold,
+    so an error confined to one element, one row (a tail launch), one column (a bias entry) or one tile (a stale or
+    misplaced block, a dropped K or M slice) cannot hide in a norm over everything.  Prints the measured values, then
+    asserts in the order above; a failure names the metric, the worst row / column / tile / index and the two values
+    there.  Returns {"norm", "entry", "row", "col", "tile"} (None where not asked for)."""
+    b = torch.as_tensor(ref).detach().to(torch.float64)
+    a = torch.as_tensor(got).detach().to(device=b.device, dtype=torch.float64)
+    assert a.shape == b.shape, (what, tuple(a.shape), tuple(b.shape))
+    if a.dim() < 2:
+        a, b = a.reshape(1, -1), b.reshape(1, -1)
+    a, b = a.reshape(-1, a.shape[-1]), b.reshape(-1, b.shape[-1])
+    rows, cols = b.shape
+    finite = torch.isfinite(a)
+    if not bool(finite.all()):
+        flat = int((~finite).flatten().int().argmax())
+        raise AssertionError(f"{what}: not finite: {int((~finite).sum())} entries, the first at {divmod(flat, cols)}: "
+                             f"{a.flatten()[flat].item()} vs {b.flatten()[flat].item():.6g}")
+    diff = a - b
+    ref_norm = max(b.norm().item(), 1e-30)
+    flat = int(diff.abs().argmax())
+    at = divmod(flat, cols)
+    worst = f"worst entry {at}: {a[at].item():.6g} vs {b[at].item():.6g}"
+    errs = dict(norm=diff.norm().item() / ref_norm, entry=diff.abs().flatten()[flat].item() / max(b.abs().max().item(), 1e-30),
+                row=None, col=None, tile=None)
+    msgs = []
+    for key, name, dim, count, tol in (("row", "row", 1, rows, tol_row), ("col", "column", 0, cols, tol_col)):
+        if tol is None:
+            continue
+        e = diff.norm(dim=dim) / (ref_norm / count ** 0.5)
+        i = int(e.argmax())
+        errs[key] = e[i].item()
+        j = int((diff[i] if dim == 1 else diff[:, i]).abs().argmax())
+        w = (i, j) if dim == 1 else (j, i)
+        msgs.append((key, tol, f"{name} error {errs[key]:.3g} >= {tol:.3g} (worst {name} {i}, its worst entry {w}: "
+                               f"{a[w].item():.6g} vs {b[w].item():.6g})"))
+    if tile is not None:
+        th, tw = tile
+        nr, nc = -(-rows // th), -(-cols // tw)
+        pad = (0, nc * tw - cols, 0, nr * th - rows)
+
+        def blocks(t):
+            return torch.nn.functional.pad(t, pad).view(nr, th, nc, tw).norm(dim=(1, 3))
+
+        e = blocks(diff) / blocks(b).clamp_min(1e-30)
+        i = int(e.argmax())
+        ti = divmod(i, nc)
+        errs["tile"] = e.flatten()[i].item()
+        sub = diff[ti[0] * th:(ti[0] + 1) * th, ti[1] * tw:(ti[1] + 1) * tw].abs()
+        j = divmod(int(sub.argmax()), sub.shape[1])
+        w = (ti[0] * th + j[0], ti[1] * tw + j[1])
+        msgs.append(("tile", tol_tile, f"tile error {errs['tile']:.3g} >= {tol_tile:.3g} (worst {th} x {tw} tile {ti}, its worst "
+                                       f"entry {w}: {a[w].item():.6g} vs {b[w].item():.6g})"))
+    print(f"parity {what}: " + " ".join(f"{k}={v:.3g}" for k, v in errs.items() if v is not None))
+    assert errs["norm"] < tol_norm, f"{what}: norm error {errs['norm']:.3g} >= {tol_norm:.3g} ({worst})"
+    assert errs["entry"] < tol_entry, f"{what}: entry-wise error {errs['entry']:.3g} >= {tol_entry:.3g} ({worst})"
+    for key, tol, msg in msgs:
+        assert errs[key] < tol, f"{what}: {msg}"
+    return errs
+
+
+def linear_parity(got, ref, *, tol_norm, tol_entry, tol_row=None, tol_col=None, tile=None, tol_tile=None, what=""):
+    """tensor_parity for what one linear launch delivers: C or (C, C2) of an NT launch, dW or (dW, db) of a TN launch.
+    got / ref: a tensor or a tuple of them; a bound: one number, or a tuple with one per output.  A vector (db) gets the
+    norm and entry checks only.  Returns the list of tensor_parity's results."""
+    gots = got if isinstance(got, (tuple, list)) else (got,)
+    refs = ref if isinstance(ref, (tuple, list)) else (ref,)
+    assert len(gots) == len(refs), (what, len(gots), len(refs))
+
+    def pick(tol, i):
+        return tol[i] if isinstance(tol, (tuple, list)) else tol
+
+    out = []
+    for i, (g, r) in enumerate(zip(gots, refs)):
+        name = f"{what} [{i}]" if len(gots) > 1 else what
+        if torch.as_tensor(r).dim() < 2:
+            out.append(tensor_parity(g, r, tol_norm=pick(tol_norm, i), tol_entry=pick(tol_entry, i), what=name))
+        else:
+            out.append(tensor_parity(g, r, tol_norm=pick(tol_norm, i), tol_entry=pick(tol_entry, i), tol_row=pick(tol_row, i),
+                                     tol_col=pick(tol_col, i), tile=tile, tol_tile=pick(tol_tile, i), what=name))
+    return out
+
+
 def tie_free_threshold(p0, nominal, span=1.25):
     """A train-mode threshold (reference HWGATE.py:94-100) near `nominal` that no entry of the unmasked softmax `p0`
     (the fp64 oracle's, any shape) comes close to: the geometric centre of the widest relative gap between neighbouring

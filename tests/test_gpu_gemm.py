@@ -4,13 +4,76 @@ import importlib
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import linear_parity, rel_err, tensor_parity
 
 pytestmark = pytest.mark.gpu
 hw = importlib.import_module("sl-hwgat_amd")
 HF = hw.functional
 DEV = "cuda:0"
 TOL = 2e-5
+BT = 6e-3      # bf16 output rounding (2^-9) dominates; accumulation is fp32
+# Entry / row / column bounds of helpers.linear_parity per kernel family, storage type and output: 3 x the worst error
+# observed on an MI355X against the fp64 reference over this module's cases (the observed values are in the comments),
+# and at or below the caps: bf16-stored outputs entry 1.2e-2, row and column 1e-2; fp32 outputs 1e-5 each.  A path whose
+# norm bound is looser than its family's for an arithmetic reason scales its caps by the same ratio.
+NT_F32 = dict(tol_entry=6e-6, tol_row=3.8e-6, tol_col=4.7e-6)          # observed 2.0e-6 / 1.3e-6 / 1.6e-6
+# GELU backward and the stored GELU factor: erf and exp evaluated in fp32 on top of the product, norm 5e-5 against 2e-5
+NT_F32_GELU = dict(tol_entry=2.2e-5, tol_row=3e-6, tol_col=2e-6)       # observed 7.3e-6 / 9.8e-7 / 6.4e-7 (caps 2.5e-5)
+NT_BF16 = dict(tol_entry=1.1e-2, tol_row=1e-2, tol_col=1e-2)           # observed 3.6e-3 / 3.8e-3 / 5.9e-3 (row, column: the cap)
+# the bf16 folded LayerNorm cancels mean * s against the product of bf16 operands, and its weights W o gamma are rounded
+# to bf16 where the reference keeps the fp32 masters: norm 1.5e-2 against 6e-3
+NT_BF16_FOLD = dict(tol_entry=3e-2, tol_row=1.2e-2, tol_col=2e-2)      # observed 1.9e-2 / 3.9e-3 / 6.4e-3 (caps 3e-2 / 2.5e-2; entry: the cap)
+# weight gradients: entry-wise and per 128 x 128 tile of dW (db: norm and entry)
+TN_F32 = dict(tol_entry=3.6e-6, tile=(128, 128), tol_tile=1.9e-6)      # observed 1.2e-6 / 6.3e-7
+# fp32 dW / db from bf16 operands (fp32 accumulation of exact bf16 products; the reference rounds the masked operand to
+# bf16 as the kernel does): norm 1e-4 against the 2e-5 of fp32 outputs, so the entry cap is 5e-5
+TN_BF16 = dict(tol_entry=2.6e-6, tile=(128, 128), tol_tile=2e-6)       # observed 8.5e-7 / 6.6e-7
+# ... with the LayerNorm prologue the kernel rounds rstd (x - mean) gamma + beta, formed in fp32, to bf16: where that
+# lands on the other side of a rounding boundary than the fp64 reference's, one operand moves by a bf16 ulp -- norm 2e-3
+# against 2e-5, entry cap 1e-3
+TN_BF16_LN = dict(tol_entry=1.9e-4, tile=(128, 128), tol_tile=4.3e-5)  # observed 6.1e-5 / 1.4e-5
+
+
+def _fold_f32(par, mean, rstd, s, K, ref, gain=1.0):
+    """Entry / row / column bounds of the fp32 FOLDED LayerNorm (PRO_LN_FOLD): the family's bounds `par` plus what the
+    fold's cancellation costs.  The kernel forms rstd_i (acc_in - mean_i s_n) + c_n with acc_in = sum_k x_ik W'_nk
+    accumulated in fp32; for a row whose mean dwarfs its spread the partial sums grow to P = |mean_i s_n| while the result
+    is O(1).  Each of the K / 2 accumulation steps (MFMA 32x32x2) rounds its partial sum, which grows linearly to P, to
+    fp32: a rounding error of standard deviation 2^-23 / sqrt(12) relative, a random walk that ends with a standard
+    deviation of 2^-23 / sqrt(12) * sqrt(K / 2 / 3) P = 0.236 * 2^-24 sqrt(K) P.  Six of those (the largest of ~10^7
+    entries) are 1.4 * 2^-24 sqrt(K) P; mean_i and s_n are themselves fp32 values (mean to 3 ulp as measured against fp64,
+    s to 1), another 4 * 2^-24 P; rstd_i times the sum arrives in the output:
+        delta_in = (1.4 sqrt(K) + 4) 2^-24 rstd_i |mean_i| |s_n|   (x `gain` = the largest slope of what the epilogue applies),
+    a rank-one matrix whose largest entry, largest row norm and largest column norm give the three bounds.  Observed on
+    an MI355X at K = 1024, rows with |mean| up to 4.5 x 3 sigma: entry 1.8e-5 of a bound of 3.5e-5, row 1.2e-5 of 5.7e-5,
+    column 6.2e-6 of 3.3e-5; the stored GELU factor 1.2e-4 of 4.4e-4.  The normalising loader (PRO_LN) subtracts the mean
+    before the product and stays at the family's bounds (2.0e-6 entry-wise on the same kind of rows)."""
+    a, b = (rstd * mean.abs()).double().cpu(), s.abs().double().cpu()
+    r = torch.as_tensor(ref).detach().double().reshape(-1, ref.shape[-1])
+    u = 2.0 ** -24 * (1.4 * K ** 0.5 + 4.0) * gain
+    rms = r.norm().item()
+    return dict(tol_entry=par["tol_entry"] + u * a.max().item() * b.max().item() / r.abs().max().item(),
+                tol_row=par["tol_row"] + u * a.max().item() * b.norm().item() / (rms / r.shape[0] ** 0.5),
+                tol_col=par["tol_col"] + u * b.max().item() * a.norm().item() / (rms / r.shape[1] ** 0.5))
+
+
+def _nan(*shape, dtype=torch.float32):
+    return torch.full(shape, float("nan"), device=DEV, dtype=dtype)
+
+
+def _nt(A, W, bias=None, **kw):
+    """HF.linear_nt into a NaN-filled output: outputs are torch.empty inside the wrapper, and the caching allocator can hand
+    back a block that still holds a correct earlier result, so an element the kernel never stores could look right"""
+    if not kw.get("stats") and kw.get("merge") is None and kw.get("out") is None:
+        kw["out"] = _nan(*A.shape[:-1], W.shape[0], dtype=A.dtype)
+    return HF.linear_nt(A, W, bias, **kw)
+
+
+def _nt_ln(A, W, bias, ln, **kw):
+    """HF.linear_nt_ln into a NaN-filled output (see _nt)"""
+    if kw.get("out") is None:
+        kw["out"] = _nan(*A.shape[:-1], W.shape[0], dtype=A.dtype)
+    return HF.linear_nt_ln(A, W, bias, ln, **kw)
 
 
 def _data(M, N, K, seed):
@@ -25,15 +88,18 @@ def _data(M, N, K, seed):
 def test_nt_plain_and_bias(M, N, K):
     A, W, b = _data(M, N, K, M + N)
     ref = A.double() @ W.double().t()
-    got = HF.linear_nt(A.to(DEV), W.to(DEV), None, epi=HF.EPI_NONE)
+    got = _nt(A.to(DEV), W.to(DEV), None, epi=HF.EPI_NONE)
     assert rel_err(got.cpu(), ref) < TOL
-    got = HF.linear_nt(A.to(DEV), W.to(DEV), b.to(DEV), epi=HF.EPI_BIAS)
+    linear_parity(got, ref, tol_norm=TOL, **NT_F32, what="nt_f32: plain")
+    got = _nt(A.to(DEV), W.to(DEV), b.to(DEV), epi=HF.EPI_BIAS)
     assert rel_err(got.cpu(), ref + b.double()) < TOL
+    linear_parity(got, ref + b.double(), tol_norm=TOL, **NT_F32, what="nt_f32: bias")
     # persistent path: more tiles than resident blocks
     if M == 1280:
         A2 = torch.randn(128 * 700, K, generator=torch.Generator().manual_seed(1))
-        got = HF.linear_nt(A2.to(DEV), W.to(DEV), b.to(DEV))
+        got = _nt(A2.to(DEV), W.to(DEV), b.to(DEV))
         assert rel_err(got.cpu(), A2.double() @ W.double().t() + b.double()) < TOL
+        linear_parity(got, A2.double() @ W.double().t() + b.double(), tol_norm=TOL, **NT_F32, what="nt_f32: persistent bias")
 
 
 def test_nt_layernorm_prologue():
@@ -48,8 +114,9 @@ def test_nt_layernorm_prologue():
     L.call("hwgat_ln_fwd", L.ptr(Ad), L.ptr(gamma.to(DEV)), L.ptr(beta.to(DEV)), L.ptr(y), L.ptr(mean), L.ptr(rstd),
            M, K, 0, L.stream())
     ref = torch.nn.functional.layer_norm(A.double(), (K,), gamma.double(), beta.double()) @ W.double().t() + b.double()
-    got = HF.linear_nt(Ad, W.to(DEV), b.to(DEV), pro=HF.PRO_LN, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
+    got = _nt(Ad, W.to(DEV), b.to(DEV), pro=HF.PRO_LN, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
     assert rel_err(got.cpu(), ref) < TOL
+    linear_parity(got, ref, tol_norm=TOL, **NT_F32, what="nt_f32: ln")
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1, 0.5])
@@ -62,22 +129,26 @@ def test_nt_dropout_residual_gelu_epilogues(p):
     keep = (mask != 0).double().mean().item()
     assert abs(keep - (1 - p)) < 0.01 and (p == 0 or abs(mask.max().item() - 1 / (1 - p)) < 1e-6)
     lin = A.double() @ W.double().t() + b.double()
-    got = HF.linear_nt(Ad, Wd, bd, epi=HF.EPI_BIAS_DROP_RES, res=res.to(DEV), epi_seed=1234, epi_p=p)
+    got = _nt(Ad, Wd, bd, epi=HF.EPI_BIAS_DROP_RES, res=res.to(DEV), epi_seed=1234, epi_p=p)
     assert rel_err(got.cpu(), res.double() + lin * mask) < TOL
-    u, h1 = HF.linear_nt(Ad, Wd, bd, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
+    linear_parity(got, res.double() + lin * mask, tol_norm=TOL, **NT_F32, what="nt_f32: drop_res")
+    u, h1 = _nt(Ad, Wd, bd, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
     assert rel_err(h1.cpu(), lin) < TOL
     assert rel_err(u.cpu(), torch.nn.functional.gelu(lin) * mask) < TOL
+    linear_parity((u, h1), (torch.nn.functional.gelu(lin) * mask, lin), tol_norm=TOL, **NT_F32, what="nt_f32: gelu_drop")
     # backward epilogue: d_h1 = (dy . W) * mask * gelu'(h1)
     dy = torch.randn(M, K, generator=torch.Generator().manual_seed(4))      # here "A" plays dY [M,K'] and W [N,K']
     h1r = lin.clone().requires_grad_(True)
     torch.nn.functional.gelu(h1r).sum().backward()
     ref = (dy.double() @ W.double().t()) * mask * h1r.grad
-    got = HF.linear_nt(dy.to(DEV), Wd, None, epi=HF.EPI_GELU_BWD, aux=h1, epi_seed=1234, epi_p=p)
+    got = _nt(dy.to(DEV), Wd, None, epi=HF.EPI_GELU_BWD, aux=h1, epi_seed=1234, epi_p=p)
     assert rel_err(got.cpu(), ref) < 5e-5
+    linear_parity(got, ref, tol_norm=5e-5, **NT_F32_GELU, what="nt_f32_gelu: gelu_bwd")
     # dropout prologue on A (mask indexed over A's own [M,K] elements)
     maskA = HF.dropout_mask((M, K), 77, p, DEV).cpu().double()
-    got = HF.linear_nt(Ad, Wd, None, pro=HF.PRO_DROP, pro_seed=77, pro_p=p, epi=HF.EPI_NONE)
+    got = _nt(Ad, Wd, None, pro=HF.PRO_DROP, pro_seed=77, pro_p=p, epi=HF.EPI_NONE)
     assert rel_err(got.cpu(), (A.double() * maskA) @ W.double().t()) < TOL
+    linear_parity(got, (A.double() * maskA) @ W.double().t(), tol_norm=TOL, **NT_F32, what="nt_f32: drop prologue")
 
 
 @pytest.mark.parametrize("M,N,K,p", [(256, 128, 128, 0.0), (4096, 384, 128, 0.0), (32 * 301, 256, 512, 0.1), (65536, 128, 256, 0.0)])
@@ -91,9 +162,11 @@ def test_tn_weight_and_bias_grad(M, N, K, p):
     ref = (dY.double() * mask).t() @ X.double()
     assert rel_err(dW.cpu(), ref) < TOL
     assert rel_err(db.cpu(), (dY.double() * mask).sum(0)) < TOL
+    linear_parity((dW, db), (ref, (dY.double() * mask).sum(0)), tol_norm=TOL, **TN_F32, what="tn_f32: dW db")
     # accumulates into existing contents
     HF.linear_tn(dY.to(DEV), X.to(DEV), dW, None, pro_seed=5, pro_p=p)
     assert rel_err(dW.cpu(), 2 * ref) < TOL
+    linear_parity(dW, 2 * ref, tol_norm=TOL, **TN_F32, what="tn_f32: dW accumulated")
 
 
 @pytest.mark.parametrize("M,N,K", [(8192, 512, 768), (32 * 129, 256, 512), (65536, 1536, 512)])
@@ -127,6 +200,7 @@ def test_tn_f32_slab_reduction_every_tile_and_bit_reproducible(M, N, K, pro):
     err = (runs[0].double() - dW0.double() - upd).view(N // 256, 256, K // 256, 256).norm(dim=(1, 3))
     assert float((err / upd.view(N // 256, 256, K // 256, 256).norm(dim=(1, 3))).max()) < TOL
     assert rel_err(db.cpu(), A64.sum(0).cpu()) < TOL
+    linear_parity((runs[0].double() - dW0.double(), db), (upd, A64.sum(0)), tol_norm=TOL, **TN_F32, what="tn_f32: slab " + pro)
 
 
 @pytest.mark.parametrize("M", [1, 29, 127, 129, 928, 864, 128 * 5 + 17])
@@ -146,22 +220,32 @@ def test_ragged_token_counts(M):
 
     def canary():
         buf = torch.full((M + 160, N), 777.0, device=DEV)
+        buf[:M] = float("nan")                      # poisoned: every one of the M rows must be stored
         return buf, buf[:M]
 
+    # the row check isolates the M % 128 tail rows (one RAGGED launch behind the bulk launch)
     buf, out = canary()
-    HF.linear_nt(Ad, Wd, bd, epi=HF.EPI_BIAS, out=out)
+    _nt(Ad, Wd, bd, epi=HF.EPI_BIAS, out=out)
     assert rel_err(out.cpu(), lin) < TOL and bool((buf[M:] == 777.0).all())
+    linear_parity(out, lin, tol_norm=TOL, **NT_F32, what="nt_f32: ragged bias")
     buf, out = canary()
-    HF.linear_nt(Ad, Wd, bd, pro=HF.PRO_LN, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)), out=out)
+    _nt(Ad, Wd, bd, pro=HF.PRO_LN, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)), out=out)
     assert rel_err(out.cpu(), lnlin) < TOL and bool((buf[M:] == 777.0).all())
+    linear_parity(out, lnlin, tol_norm=TOL, **NT_F32, what="nt_f32: ragged ln")
     buf, out = canary()
-    HF.linear_nt(Ad, Wd, bd, epi=HF.EPI_BIAS_DROP_RES, res=res.to(DEV), epi_seed=1234, epi_p=p, out=out)
+    _nt(Ad, Wd, bd, epi=HF.EPI_BIAS_DROP_RES, res=res.to(DEV), epi_seed=1234, epi_p=p, out=out)
     assert rel_err(out.cpu(), res.double() + lin * mask) < TOL and bool((buf[M:] == 777.0).all())
-    u, h1 = HF.linear_nt(Ad, Wd, bd, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
+    linear_parity(out, res.double() + lin * mask, tol_norm=TOL, **NT_F32, what="nt_f32: ragged drop_res")
+    buf, out = canary()
+    u, h1 = _nt(Ad, Wd, bd, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p, out=out)
     assert rel_err(h1.cpu(), lin) < TOL and rel_err(u.cpu(), torch.nn.functional.gelu(lin) * mask) < TOL
+    assert bool((buf[M:] == 777.0).all())
+    linear_parity((u, h1), (torch.nn.functional.gelu(lin) * mask, lin), tol_norm=TOL, **NT_F32, what="nt_f32: ragged gelu_drop")
     maskA = HF.dropout_mask((M, K), 77, p, DEV).cpu().double()
-    got = HF.linear_nt(Ad, Wd, None, pro=HF.PRO_DROP, pro_seed=77, pro_p=p, epi=HF.EPI_NONE)
-    assert rel_err(got.cpu(), (A.double() * maskA) @ W.double().t()) < TOL
+    buf, out = canary()
+    got = _nt(Ad, Wd, None, pro=HF.PRO_DROP, pro_seed=77, pro_p=p, epi=HF.EPI_NONE, out=out)
+    assert rel_err(got.cpu(), (A.double() * maskA) @ W.double().t()) < TOL and bool((buf[M:] == 777.0).all())
+    linear_parity(got, (A.double() * maskA) @ W.double().t(), tol_norm=TOL, **NT_F32, what="nt_f32: ragged drop prologue")
     # weight gradients: small-tile kernel (N*K = 256*128), the 256x256 kernel (512x256), LayerNorm on B
     dY = torch.randn(M, N, generator=g)
     for NN, KK in ((N, K), (512, 256)):
@@ -171,16 +255,21 @@ def test_ragged_token_counts(M):
         HF.linear_tn(dYn.to(DEV), Xn.to(DEV), dW, db)
         assert rel_err(dW.cpu(), dYn.double().t() @ Xn.double()) < TOL
         assert rel_err(db.cpu(), dYn.double().sum(0)) < TOL
+        linear_parity((dW, db), (dYn.double().t() @ Xn.double(), dYn.double().sum(0)), tol_norm=TOL, **TN_F32,
+                      what="tn_f32: ragged plain")
         mk = HF.dropout_mask((M, NN), 5, p, DEV).cpu().double()
         dW.zero_()
         db.zero_()
         HF.linear_tn(dYn.to(DEV), Xn.to(DEV), dW, db, pro_seed=5, pro_p=p)
         assert rel_err(dW.cpu(), (dYn.double() * mk).t() @ Xn.double()) < TOL
         assert rel_err(db.cpu(), (dYn.double() * mk).sum(0)) < TOL
+        linear_parity((dW, db), ((dYn.double() * mk).t() @ Xn.double(), (dYn.double() * mk).sum(0)), tol_norm=TOL, **TN_F32,
+                      what="tn_f32: ragged drop")
     dW = torch.zeros(N, K, device=DEV)
     HF.linear_tn(dY.to(DEV), Ad, dW, None, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
     ref = dY.double().t() @ torch.nn.functional.layer_norm(A.double(), (K,), gamma.double(), beta.double())
     assert rel_err(dW.cpu(), ref) < TOL
+    linear_parity(dW, ref, tol_norm=TOL, **TN_F32, what="tn_f32: ragged ln")
 
 
 def test_transpose():
@@ -191,7 +280,6 @@ def test_transpose():
 
 
 # ------------------------------------------------------------------ bf16 family (config 3)
-BT = 6e-3      # bf16 output rounding (2^-9) dominates; accumulation is fp32
 
 
 def _b(x):
@@ -203,19 +291,22 @@ def test_bf16_nt_plain_bias_ln(M, N, K):
     A, W, b = _data(M, N, K, M + K)
     Ab, Wb = _b(A), _b(W)
     ref = Ab.double() @ Wb.double().t()
-    got = HF.linear_nt(Ab.to(DEV), Wb.to(DEV), None, epi=HF.EPI_NONE)
+    got = _nt(Ab.to(DEV), Wb.to(DEV), None, epi=HF.EPI_NONE)
     assert got.dtype == torch.bfloat16 and rel_err(got.float().cpu(), ref) < BT
-    got = HF.linear_nt(Ab.to(DEV), Wb.to(DEV), b.to(DEV), epi=HF.EPI_BIAS)
+    linear_parity(got, ref, tol_norm=BT, **NT_BF16, what="nt_bf16: plain")
+    got = _nt(Ab.to(DEV), Wb.to(DEV), b.to(DEV), epi=HF.EPI_BIAS)
     assert rel_err(got.float().cpu(), ref + b.double()) < BT
+    linear_parity(got, ref + b.double(), tol_norm=BT, **NT_BF16, what="nt_bf16: bias")
     if K >= 128:
         g = torch.Generator().manual_seed(9)
         gamma, beta = torch.randn(K, generator=g), torch.randn(K, generator=g)
         mean, rstd = HF.ln_stats(Ab.to(DEV), gamma.to(DEV), beta.to(DEV))
         xn = torch.nn.functional.layer_norm(Ab.double(), (K,), gamma.double(), beta.double())
-        got = HF.linear_nt(Ab.to(DEV), Wb.to(DEV), b.to(DEV), pro=HF.PRO_LN,
+        got = _nt(Ab.to(DEV), Wb.to(DEV), b.to(DEV), pro=HF.PRO_LN,
                            ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
         # the normalised operand is rounded to bf16 before the MFMA
         assert rel_err(got.float().cpu(), _b(xn.float()).double() @ Wb.double().t() + b.double()) < BT
+        linear_parity(got, _b(xn.float()).double() @ Wb.double().t() + b.double(), tol_norm=BT, **NT_BF16, what="nt_bf16: ln")
 
 
 @pytest.mark.parametrize("M", [29, 129, 928, 128 * 3 + 77])
@@ -232,15 +323,28 @@ def test_bf16_ragged_token_counts(M):
     mean, rstd = HF.ln_stats(Ab, gamma.to(DEV), beta.to(DEV))
     lin = Ar @ Wr.t() + b.double()
     mask = HF.dropout_mask((M, N), 1234, p, DEV).cpu().double()
-    buf = torch.full((M + 160, N), 777.0, device=DEV, dtype=torch.bfloat16)
-    out = buf[:M]
-    HF.linear_nt(Ab, Wb, bd, epi=HF.EPI_BIAS_DROP_RES, res=resb, epi_seed=1234, epi_p=p, out=out)
+    def canary():
+        buf = torch.full((M + 160, N), 777.0, device=DEV, dtype=torch.bfloat16)
+        buf[:M] = float("nan")                      # poisoned: every one of the M rows must be stored
+        return buf, buf[:M]
+
+    # the row check isolates the M % 128 tail rows (the RAGGED launch)
+    buf, out = canary()
+    _nt(Ab, Wb, bd, epi=HF.EPI_BIAS_DROP_RES, res=resb, epi_seed=1234, epi_p=p, out=out)
     assert rel_err(out.float().cpu(), resr + lin * mask) < BT and bool((buf[M:] == 777.0).all())
-    got = HF.linear_nt(Ab, Wb, bd, pro=HF.PRO_LN, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
+    linear_parity(out, resr + lin * mask, tol_norm=BT, **NT_BF16, what="nt_bf16: ragged drop_res")
+    buf, out = canary()
+    got = _nt(Ab, Wb, bd, pro=HF.PRO_LN, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)), out=out)
     lnref = torch.nn.functional.layer_norm(Ar, (K,), gamma.double(), beta.double()) @ Wr.t() + b.double()
-    assert rel_err(got.float().cpu(), lnref) < 2 * BT
-    u, h1 = HF.linear_nt(Ab, Wb, bd, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
-    assert rel_err(h1.float().cpu(), lin) < BT
+    assert rel_err(got.float().cpu(), lnref) < 2 * BT and bool((buf[M:] == 777.0).all())
+    # against the operand the kernel multiplies: the normalised rows rounded to bf16 (as test_bf16_nt_plain_bias_ln does)
+    lnb = _b(torch.nn.functional.layer_norm(Ar, (K,), gamma.double(), beta.double()).float()).double() @ Wr.t() + b.double()
+    linear_parity(got, lnb, tol_norm=BT, **NT_BF16, what="nt_bf16: ragged ln")
+    buf, out = canary()
+    u, h1 = _nt(Ab, Wb, bd, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p, out=out)
+    assert rel_err(h1.float().cpu(), lin) < BT and bool((buf[M:] == 777.0).all())
+    linear_parity((u, h1), (torch.nn.functional.gelu(h1.float().cpu().double()) * mask, lin), tol_norm=BT, **NT_BF16,
+                  what="nt_bf16: ragged gelu_drop")
     dY = _b(torch.randn(M, N, generator=g)).to(DEV)
     dW, db = torch.zeros(N, K, device=DEV), torch.zeros(N, device=DEV)
     HF.linear_tn(dY, Ab, dW, db, pro_seed=5, pro_p=p)
@@ -248,10 +352,13 @@ def test_bf16_ragged_token_counts(M):
     dYr = dY.float().cpu().double() * mk
     assert rel_err(dW.cpu(), _b(dYr.float()).double().t() @ Ar) < 2 * BT
     assert rel_err(db.cpu(), dYr.sum(0)) < BT
+    # the M % 32 tail of the TN kernels; fp32 accumulation of exact bf16 products
+    linear_parity((dW, db), (_b(dYr.float()).double().t() @ Ar, dYr.sum(0)), tol_norm=1e-4, **TN_BF16, what="tn_bf16: ragged drop")
     dW.zero_()
     HF.linear_tn(dY, Ab, dW, None, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
     lnA = _b(torch.nn.functional.layer_norm(Ar, (K,), gamma.double(), beta.double()).float()).double()
     assert rel_err(dW.cpu(), dY.float().cpu().double().t() @ lnA) < 2 * BT
+    linear_parity(dW, dY.float().cpu().double().t() @ lnA, tol_norm=2e-3, **TN_BF16_LN, what="tn_bf16_ln: ragged ln")
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1])
@@ -262,20 +369,26 @@ def test_bf16_nt_epilogues(p):
     res = _b(torch.randn(M, N, generator=torch.Generator().manual_seed(2)))
     mask = HF.dropout_mask((M, N), 1234, p, DEV).cpu().double()
     lin = Ab.cpu().double() @ Wb.cpu().double().t() + b.double()
-    got = HF.linear_nt(Ab, Wb, b.to(DEV), epi=HF.EPI_BIAS_DROP_RES, res=res.to(DEV), epi_seed=1234, epi_p=p)
+    got = _nt(Ab, Wb, b.to(DEV), epi=HF.EPI_BIAS_DROP_RES, res=res.to(DEV), epi_seed=1234, epi_p=p)
     assert rel_err(got.float().cpu(), res.double() + lin * mask) < BT
-    u, h1 = HF.linear_nt(Ab, Wb, b.to(DEV), epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
+    linear_parity(got, res.double() + lin * mask, tol_norm=BT, **NT_BF16, what="nt_bf16: drop_res")
+    u, h1 = _nt(Ab, Wb, b.to(DEV), epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
     assert rel_err(h1.float().cpu(), lin) < BT
     assert rel_err(u.float().cpu(), torch.nn.functional.gelu(h1.float().cpu().double()) * mask) < BT
+    linear_parity((u, h1), (torch.nn.functional.gelu(h1.float().cpu().double()) * mask, lin), tol_norm=BT, **NT_BF16,
+                  what="nt_bf16: gelu_drop")
     dy = _b(torch.randn(M, K, generator=torch.Generator().manual_seed(4)))
     h1r = h1.float().cpu().double().requires_grad_(True)
     torch.nn.functional.gelu(h1r).sum().backward()
     ref = (dy.double() @ Wb.cpu().double().t()) * mask * h1r.grad
-    got = HF.linear_nt(dy.to(DEV), Wb, None, epi=HF.EPI_GELU_BWD, aux=h1, epi_seed=1234, epi_p=p)
+    got = _nt(dy.to(DEV), Wb, None, epi=HF.EPI_GELU_BWD, aux=h1, epi_seed=1234, epi_p=p)
     assert rel_err(got.float().cpu(), ref) < BT
+    linear_parity(got, ref, tol_norm=BT, **NT_BF16, what="nt_bf16: gelu_bwd")
     maskA = HF.dropout_mask((M, K), 77, p, DEV).cpu().double()
-    got = HF.linear_nt(Ab, Wb, None, pro=HF.PRO_DROP, pro_seed=77, pro_p=p, epi=HF.EPI_NONE)
+    got = _nt(Ab, Wb, None, pro=HF.PRO_DROP, pro_seed=77, pro_p=p, epi=HF.EPI_NONE)
     assert rel_err(got.float().cpu(), _b((Ab.cpu().double() * maskA).float()).double() @ Wb.cpu().double().t()) < BT
+    linear_parity(got, _b((Ab.cpu().double() * maskA).float()).double() @ Wb.cpu().double().t(), tol_norm=BT, **NT_BF16,
+                  what="nt_bf16: drop prologue")
 
 
 # the last four: gemm_tn256_bf16_k (dW at least 256 x 256, M % 64 == 0) -- one split of two stages up to many splits
@@ -291,6 +404,7 @@ def test_bf16_tn_weight_and_bias_grad(M, N, K, p):
     dYm = _b((dY.double() * mask).float()).double() if p > 0 else dY.double()
     assert rel_err(dW.cpu(), dYm.t() @ X.double()) < 1e-4          # fp32 accumulate of exact bf16 products
     assert rel_err(db.cpu(), (dY.double() * mask).sum(0)) < 1e-4
+    linear_parity((dW, db), (dYm.t() @ X.double(), (dY.double() * mask).sum(0)), tol_norm=1e-4, **TN_BF16, what="tn_bf16: dW db")
     # LayerNorm prologue on B
     gamma, beta = torch.randn(K, generator=g), torch.randn(K, generator=g)
     mean, rstd = HF.ln_stats(X.to(DEV), gamma.to(DEV), beta.to(DEV))
@@ -298,74 +412,147 @@ def test_bf16_tn_weight_and_bias_grad(M, N, K, p):
     HF.linear_tn(dY.to(DEV), X.to(DEV), dW, None, ln=(mean, rstd, gamma.to(DEV), beta.to(DEV)))
     xn = _b(torch.nn.functional.layer_norm(X.double(), (K,), gamma.double(), beta.double()).float()).double()
     assert rel_err(dW.cpu(), dY.double().t() @ xn) < 2e-3
+    linear_parity(dW, dY.double().t() @ xn, tol_norm=2e-3, **TN_BF16_LN, what="tn_bf16_ln: dW")
 
 
 # ---- the PERSISTENT tile loop of the fp32 NT kernels (gemm_nt_k: 512 / 768 resident 128x128 blocks; gemm_nt256_k,
 # N % 256 == 0 and K >= 512: 256 resident 256x256 blocks + a 128-row remainder launch): more tiles than blocks, so each
 # block walks several tiles (cross-tile slab prefetch, LayerNorm-statistics reload on a new tile, XCD-aware tile
 # order and its un-swizzled tail when the row-block count is not a multiple of 8, `t += gridDim.x`).  The headline
-# shapes run 10-30 tiles per block through exactly this path.  Checked against fp64 on sampled 128-row blocks.
+# shapes run 10-30 tiles per block through exactly this path.  Checked against fp64 on sampled 128-row blocks on the
+# CPU, and EVERY element (every tile a block walks) against an fp64 reference computed on the device.
 _LOOP_CASES = [("none", "none"), ("none", "bias"), ("ln", "bias"), ("none", "drop_res"), ("ln", "gelu_drop"),
                ("drop", "gelu_bwd"), ("drop", "none")]
+# the headline's training forms: the LayerNorm folded into the weights and the epilogue (hwgat_ln_fold + PRO_LN_FOLD,
+# as linear_nt_ln does) with EPI_BIAS / EPI_BIAS_GELU_DROP_G forward, EPI_MUL_AUX backward.  Fold cases get rows with a
+# mean of three standard deviations and a per-row scale, so that the cancellation rstd (acc - mean s) is exercised.
+_TRAIN_CASES = [("fold", "bias"), ("fold", "gelu_drop_g"), ("none", "gelu_drop_g"), ("none", "mul_aux"), ("drop", "mul_aux")]
+_LN_WIDTHS = (64, 128, 192, 256, 384, 512, 768, 1024)       # hwgat_ln_fwd
 
 
-@pytest.mark.parametrize("pro,epi", _LOOP_CASES)
-@pytest.mark.parametrize("M,N,K", [(128 * 2003, 128, 128), (128 * 701, 384, 512),
-                                   (256 * 301, 512, 512), (256 * 150 + 128, 256, 1024)])   # the last two: gemm_nt256_k
-def test_nt_persistent_tile_loop_every_prologue_and_epilogue(M, N, K, pro, epi):
+def _gelu_grad64(x):
+    return 0.5 * (1 + torch.erf(x / 2 ** 0.5)) + x * torch.exp(-0.5 * x * x) / (2 * torch.pi) ** 0.5
+
+
+def _persistent_loop(M, N, K, pro, epi, dt, blocks):
+    """one prologue / epilogue pair through linear_nt on a shape with more tiles than resident blocks; `blocks`: the
+    128-row blocks of the sampled CPU check"""
+    f32 = dt == torch.float32
     p = 0.1
     g = torch.Generator(device=DEV).manual_seed(M + N + len(pro) * 7 + len(epi))
-    A = torch.randn(M, K, device=DEV, generator=g)
-    W = torch.randn(N, K, device=DEV, generator=g) * 0.1
+    A = torch.randn(M, K, device=DEV, generator=g).to(dt)
+    W32 = torch.randn(N, K, device=DEV, generator=g) * 0.1
+    W = W32.to(dt)
     b = torch.randn(N, device=DEV, generator=g)
-    res = torch.randn(M, N, device=DEV, generator=g)
-    aux = torch.randn(M, N, device=DEV, generator=g)
+    res = torch.randn(M, N, device=DEV, generator=g).to(dt)
+    aux = torch.randn(M, N, device=DEV, generator=g).to(dt)
     gamma, beta = torch.randn(K, device=DEV, generator=g), torch.randn(K, device=DEV, generator=g)
+    if pro == "fold":
+        A = (torch.randn(M, K, device=DEV, generator=g) * (0.5 + torch.rand(M, 1, device=DEV, generator=g))
+             + 3.0 * torch.randn(M, 1, device=DEV, generator=g)).to(dt)
+        gamma, beta = 1.0 + 0.3 * gamma, 0.3 * beta
     kw = {}
-    if pro == "ln":
-        mean, rstd = HF.ln_stats(A, gamma, beta)
+    if pro in ("ln", "fold"):
+        if K in _LN_WIDTHS:
+            mean, rstd = HF.ln_stats(A, gamma, beta)
+        else:
+            mean, rstd = A.double().mean(-1).float(), (A.double().var(-1, unbiased=False) + 1e-5).rsqrt().float()
         kw.update(pro=HF.PRO_LN, ln=(mean, rstd, gamma, beta))
     elif pro == "drop":
         kw.update(pro=HF.PRO_DROP, pro_seed=77, pro_p=p)
-    code = {"none": HF.EPI_NONE, "bias": HF.EPI_BIAS, "drop_res": HF.EPI_BIAS_DROP_RES,
-            "gelu_drop": HF.EPI_BIAS_GELU_DROP, "gelu_bwd": HF.EPI_GELU_BWD}[epi]
-    bias = None if epi in ("none", "gelu_bwd") else b
-    if epi in ("drop_res", "gelu_drop", "gelu_bwd"):
+    code = {"none": HF.EPI_NONE, "bias": HF.EPI_BIAS, "drop_res": HF.EPI_BIAS_DROP_RES, "gelu_drop": HF.EPI_BIAS_GELU_DROP,
+            "gelu_bwd": HF.EPI_GELU_BWD, "gelu_drop_g": HF.EPI_BIAS_GELU_DROP_G, "mul_aux": HF.EPI_MUL_AUX}[epi]
+    bias = None if epi in ("none", "gelu_bwd", "mul_aux") else b
+    if epi in ("drop_res", "gelu_drop", "gelu_bwd", "gelu_drop_g"):
         kw.update(epi_seed=1234, epi_p=p)
-    got = HF.linear_nt(A, W, bias, epi=code, res=res if epi == "drop_res" else None,
-                       aux=aux if epi == "gelu_bwd" else None, **kw)
+    Wk = W
+    if pro == "fold":
+        Wk, s_, c_ = HF.ln_fold(W32, b, gamma, beta, dt)
+        kw.update(pro=HF.PRO_LN_FOLD, ln=(mean, rstd, s_, c_))
+        bias = None
+    got = _nt(A, Wk, bias, epi=code, res=res if epi == "drop_res" else None,
+              aux=aux if epi in ("gelu_bwd", "mul_aux") else None, **kw)
     got2 = None
-    if epi == "gelu_drop":
+    if epi in ("gelu_drop", "gelu_drop_g"):
         got, got2 = got
-    # sampled row blocks: first, the last ones (un-swizzled tail: 2003 % 8 = 3, 701 % 8 = 5), a few inside
-    nb = M // 128
-    blocks = sorted({0, 1, 7, 8, nb // 2, nb // 3 * 2 + 1, nb - 9, nb - 3, nb - 2, nb - 1, 511, 512, 513})
-    rows = torch.cat([torch.arange(128) + 128 * bi for bi in blocks if 0 <= bi < nb]).to(DEV)
-    Ar = A[rows].double().cpu()
-    if pro == "ln":
-        Ar = torch.nn.functional.layer_norm(Ar, (K,), gamma.double().cpu(), beta.double().cpu())
-    elif pro == "drop":
-        Ar = Ar * HF.dropout_mask((M, K), 77, p, DEV)[rows].double().cpu()
-    lin = Ar @ W.double().cpu().t()
-    if bias is not None:
-        lin = lin + b.double().cpu()
-    mask = HF.dropout_mask((M, N), 1234, p, DEV)[rows].double().cpu() if "epi_p" in kw else None
-    if epi == "drop_res":
-        ref = res[rows].double().cpu() + lin * mask
-    elif epi == "gelu_drop":
-        assert rel_err(got2[rows].cpu(), lin) < TOL
-        ref = torch.nn.functional.gelu(lin) * mask
-    elif epi == "gelu_bwd":
-        h = aux[rows].double().cpu().requires_grad_(True)
-        torch.nn.functional.gelu(h).sum().backward()
-        ref = lin * mask * h.grad
+    # norm bounds: the family's; GELU backward and its stored factor 5e-5 in fp32 (erf and exp in fp32 on top of the
+    # product); the bf16 fold cancels mean * s against a product of bf16 operands (1.5e-2, its factor 2 x that)
+    if f32:
+        tol = 5e-5 if epi in ("gelu_bwd", "gelu_drop_g") else (3e-5 if pro == "fold" else TOL)
+        tol2 = tol
+        par, fam = (NT_F32_GELU, "nt_f32_gelu") if epi in ("gelu_bwd", "gelu_drop_g") else (NT_F32, "nt_f32")
+        fam = "nt_f32_fold" if pro == "fold" else fam
     else:
-        ref = lin
-    tol = 5e-5 if epi == "gelu_bwd" else TOL
-    assert rel_err(got[rows].cpu(), ref) < tol
-    worst = max(rel_err(got[rows][i * 128:(i + 1) * 128].cpu(), ref[i * 128:(i + 1) * 128]) for i in range(len(rows) // 128))
-    assert worst < 4 * tol, worst                       # no single sampled block is off
-    assert bool(torch.isfinite(got).all())
+        tol = 1.5e-2 if pro == "fold" else BT
+        tol2 = 2 * tol if pro == "fold" else tol
+        par, fam = (NT_BF16_FOLD, "nt_bf16_fold") if pro == "fold" else (NT_BF16, "nt_bf16")
+    Wref = W32.double() if pro == "fold" else W.double()    # the fold is compared with the unfolded master weights
+
+    def reference(rows, dev):
+        """fp64 reference of the rows `rows` (None: all of them) on `dev`"""
+        def take(t):
+            return (t if rows is None else t[rows]).double().to(dev)
+        Ar = take(A)
+        if pro in ("ln", "fold"):
+            Ar = torch.nn.functional.layer_norm(Ar, (K,), gamma.double().to(dev), beta.double().to(dev))
+        elif pro == "drop":
+            Ar = Ar * take(HF.dropout_mask((M, K), 77, p, DEV))
+        if not f32 and pro != "fold":
+            Ar = Ar.float().bfloat16().double()             # the MFMA operand is bf16
+        lin = Ar @ Wref.to(dev).t()
+        if epi not in ("none", "gelu_bwd", "mul_aux"):
+            lin = lin + b.double().to(dev)
+        mask = take(HF.dropout_mask((M, N), 1234, p, DEV)) if "epi_p" in kw else None
+        ref2 = None
+        if epi == "drop_res":
+            ref = take(res) + lin * mask
+        elif epi == "gelu_drop":
+            ref, ref2 = torch.nn.functional.gelu(lin if f32 else take(got2)) * mask, lin
+        elif epi == "gelu_drop_g":
+            ref, ref2 = torch.nn.functional.gelu(lin) * mask, _gelu_grad64(lin) * mask
+        elif epi == "gelu_bwd":
+            ref = lin * mask * _gelu_grad64(take(aux))
+        elif epi == "mul_aux":
+            ref = lin * take(aux)
+        else:
+            ref = lin
+        return ref, ref2
+
+    # sampled row blocks on the CPU
+    nb = M // 128
+    rows = torch.cat([torch.arange(128) + 128 * bi for bi in blocks(nb) if 0 <= bi < nb]).to(DEV)
+    ref, ref2 = reference(rows, "cpu")
+    if got2 is not None:
+        assert rel_err(got2[rows].float().cpu(), ref2) < tol2
+    assert rel_err(got[rows].float().cpu(), ref) < tol
+    worst = max(rel_err(got[rows][i * 128:(i + 1) * 128].float().cpu(), ref[i * 128:(i + 1) * 128]) for i in range(len(rows) // 128))
+    assert worst < (4 if f32 else 2) * tol, worst       # no single sampled block is off
+    assert bool(torch.isfinite(got.float()).all())
+    # every element of every tile, on the device
+    ref, ref2 = reference(None, DEV)
+    tile = dict(tile=(128, 128), tol_tile=(4 if f32 else 2) * tol)
+    par2 = par
+    if f32 and pro == "fold":       # the fold's cancellation (see _fold_f32); |gelu'| <= 1.13, |gelu''| <= 0.8, kept entries / (1 - p)
+        par2 = _fold_f32(par, mean, rstd, s_, K, ref2, gain=0.8 / (1 - p)) if got2 is not None else None
+        par = _fold_f32(par, mean, rstd, s_, K, ref, gain=1.13 / (1 - p) if got2 is not None else 1.0)
+        print(f"fold bounds {M} {N} {K} {epi}:", par, par2)
+    tensor_parity(got, ref, tol_norm=tol, **par, **tile, what=f"{fam}: loop {pro} {epi}")
+    if got2 is not None:
+        tensor_parity(got2, ref2, tol_norm=tol2, **par2, tile=(128, 128), tol_tile=(4 if f32 else 2) * tol2, what=f"{fam}: loop {pro} {epi} C2")
+
+
+@pytest.mark.parametrize("pro,epi", _LOOP_CASES + _TRAIN_CASES)
+@pytest.mark.parametrize("M,N,K", [(128 * 2003, 128, 128), (128 * 701, 384, 512),
+                                   (256 * 301, 512, 512), (256 * 150 + 128, 256, 1024)])   # the last two: gemm_nt256_k
+def test_nt_persistent_tile_loop_every_prologue_and_epilogue(M, N, K, pro, epi):
+    """The last two shapes enter gemm_nt256_k (hwgat_linear_nt_f32_ex: N % 256 == 0, K >= 128 and (M / 256) (N / 256) = 602
+    and 150 tiles >= 128); the second of them also runs the 128-row remainder launch, folded for PRO_LN_FOLD.  With
+    _TRAIN_CASES that is the headline's training form on the kernel it trains on: PRO_LN_FOLD + EPI_BIAS_GELU_DROP_G
+    forward (both outputs checked), EPI_MUL_AUX backward.  The first two shapes take the same pairs through the 128x128
+    kernels' loop."""
+    # sampled row blocks: first, the last ones (un-swizzled tail: 2003 % 8 = 3, 701 % 8 = 5), a few inside
+    _persistent_loop(M, N, K, pro, epi, torch.float32,
+                     lambda nb: sorted({0, 1, 7, 8, nb // 2, nb // 3 * 2 + 1, nb - 9, nb - 3, nb - 2, nb - 1, 511, 512, 513}))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -379,16 +566,19 @@ def test_nt_epilogue_row_statistics_and_merged_store(M, N, K, F, Kt, dtype):
     W = (torch.randn(N, K, device=DEV, generator=g) * 0.1).to(dtype)
     b = torch.randn(N, device=DEV, generator=g)
     res = (torch.randn(M, N, device=DEV, generator=g) + 0.7).to(dtype)            # a non-zero row mean
-    plain = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=p)
-    out, mean, rstd = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=p, stats=True)
+    plain = _nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=p)
+    out, mean, rstd = _nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=p, stats=True)
     assert torch.equal(out, plain)
+    ref = res.double() + (A.double() @ W.double().t() + b.double()) * HF.dropout_mask((M, N), 9, p, DEV).double()
+    linear_parity(plain, ref, tol_norm=TOL if dtype == torch.float32 else BT, **(NT_F32 if dtype == torch.float32 else NT_BF16),
+                  what=("nt_f32" if dtype == torch.float32 else "nt_bf16") + ": drop_res with row statistics")
     ref = plain.double()
     assert rel_err(mean.cpu(), ref.mean(-1).cpu()) < 1e-5
     assert rel_err(rstd.cpu(), (ref.var(-1, unbiased=False) + 1e-5).rsqrt().cpu()) < 1e-5
     if M % (F * Kt):
         return
     Bn = M // (F * Kt)
-    mg, mean2, rstd2 = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=p, stats=True, merge=(F, Kt))
+    mg, mean2, rstd2 = _nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=p, stats=True, merge=(F, Kt))
     want = plain.view(Bn, F // 2, 2, Kt, N).transpose(2, 3).reshape(Bn, F // 2, Kt, 2 * N)     # the reference's reshape
     assert mg.shape == want.shape and torch.equal(mg, want)
     wd = want.double().view(-1, 2 * N)
@@ -396,64 +586,22 @@ def test_nt_epilogue_row_statistics_and_merged_store(M, N, K, F, Kt, dtype):
     assert rel_err(rstd2.cpu(), (wd.var(-1, unbiased=False) + 1e-5).rsqrt().cpu()) < 1e-5
 
 
-@pytest.mark.parametrize("pro,epi", _LOOP_CASES)
-@pytest.mark.parametrize("M,N,K", [(256 * 301, 512, 512), (256 * 150 + 128, 256, 128)])
+@pytest.mark.parametrize("pro,epi", _LOOP_CASES + _TRAIN_CASES)
+@pytest.mark.parametrize("M,N,K", [(256 * 301, 512, 512), (256 * 150 + 128, 256, 128),
+                                   (256 * 301, 512, 192), (256 * 150 + 128, 256, 576)])
 def test_bf16_nt256_persistent_tile_loop_every_prologue_and_epilogue(M, N, K, pro, epi):
-    """gemm_nt256_bf16_k (N % 256 == 0): more tiles than its 256 resident blocks, odd row-block count, a 128-row
-    remainder launch; every prologue / epilogue pair against fp64 on sampled row blocks (operands and the prologue's
-    output rounded to bf16 like the kernel's MFMA operands)."""
-    p = 0.1
-    g = torch.Generator(device=DEV).manual_seed(M + N + len(pro) * 7 + len(epi))
-    A = torch.randn(M, K, device=DEV, generator=g).bfloat16()
-    W = (torch.randn(N, K, device=DEV, generator=g) * 0.1).bfloat16()
-    b = torch.randn(N, device=DEV, generator=g)
-    res = torch.randn(M, N, device=DEV, generator=g).bfloat16()
-    aux = torch.randn(M, N, device=DEV, generator=g).bfloat16()
-    gamma, beta = torch.randn(K, device=DEV, generator=g), torch.randn(K, device=DEV, generator=g)
-    kw = {}
-    if pro == "ln":
-        mean, rstd = HF.ln_stats(A, gamma, beta)
-        kw.update(pro=HF.PRO_LN, ln=(mean, rstd, gamma, beta))
-    elif pro == "drop":
-        kw.update(pro=HF.PRO_DROP, pro_seed=77, pro_p=p)
-    code = {"none": HF.EPI_NONE, "bias": HF.EPI_BIAS, "drop_res": HF.EPI_BIAS_DROP_RES,
-            "gelu_drop": HF.EPI_BIAS_GELU_DROP, "gelu_bwd": HF.EPI_GELU_BWD}[epi]
-    bias = None if epi in ("none", "gelu_bwd") else b
-    if epi in ("drop_res", "gelu_drop", "gelu_bwd"):
-        kw.update(epi_seed=1234, epi_p=p)
-    got = HF.linear_nt(A, W, bias, epi=code, res=res if epi == "drop_res" else None,
-                       aux=aux if epi == "gelu_bwd" else None, **kw)
-    got2 = None
-    if epi == "gelu_drop":
-        got, got2 = got
-    nb = M // 128
-    blocks = sorted({0, 1, 2, 15, 16, nb // 2, nb - 5, nb - 2, nb - 1, 511, 512, 513})
-    rows = torch.cat([torch.arange(128) + 128 * bi for bi in blocks if 0 <= bi < nb]).to(DEV)
-    Ar = A[rows].double().cpu()
-    if pro == "ln":
-        Ar = torch.nn.functional.layer_norm(Ar, (K,), gamma.double().cpu(), beta.double().cpu())
-    elif pro == "drop":
-        Ar = Ar * HF.dropout_mask((M, K), 77, p, DEV)[rows].double().cpu()
-    Ar = Ar.float().bfloat16().double()                     # the MFMA operand is bf16
-    lin = Ar @ W.double().cpu().t()
-    if bias is not None:
-        lin = lin + b.double().cpu()
-    mask = HF.dropout_mask((M, N), 1234, p, DEV)[rows].double().cpu() if "epi_p" in kw else None
-    if epi == "drop_res":
-        ref = res[rows].double().cpu() + lin * mask
-    elif epi == "gelu_drop":
-        assert rel_err(got2[rows].float().cpu(), lin) < BT
-        ref = torch.nn.functional.gelu(got2[rows].double().cpu()) * mask
-    elif epi == "gelu_bwd":
-        h = aux[rows].double().cpu().requires_grad_(True)
-        torch.nn.functional.gelu(h).sum().backward()
-        ref = lin * mask * h.grad
-    else:
-        ref = lin
-    assert rel_err(got[rows].float().cpu(), ref) < BT
-    worst = max(rel_err(got[rows][i * 128:(i + 1) * 128].float().cpu(), ref[i * 128:(i + 1) * 128]) for i in range(len(rows) // 128))
-    assert worst < 2 * BT, worst
-    assert bool(torch.isfinite(got.float()).all())
+    """The 256 x 256 bf16 kernels (N % 256 == 0): more tiles than the 256 resident blocks, odd row-block count, a 128-row
+    remainder launch; every prologue / epilogue pair against fp64 on sampled row blocks and on every element (operands and
+    the prologue's output rounded to bf16 like the kernel's MFMA operands).
+    Which kernel a case reaches, from hwgat_linear_nt_bf16_ex (gemm_bf16.hip): all four shapes pass its 256-wide branch
+    (N % 256 == 0, K >= 128, 602 / 150 tiles >= 128), which asks hwgat_nt8w_bf16_takes (gemm_bf16_nt8w.hip) and otherwise
+    launches gemm_nt256_bf16_k.  The eight-wave kernel takes K % 128 == 0 with no prologue or the fold and epilogues none /
+    bias / drop_res / gelu_drop_g / mul_aux, so at K = 512 and K = 128 those pairs run on it and the PRO_LN / PRO_DROP pairs
+    and gelu_drop / gelu_bwd on gemm_nt256_bf16_k.  K = 192 and K = 576 (K % 128 == 64, K % 64 == 0) are declined by
+    hwgat_nt8w_bf16_takes for every pair: there ALL pairs, the training forms PRO_LN_FOLD + EPI_BIAS / EPI_BIAS_GELU_DROP_G
+    and EPI_MUL_AUX included, run on gemm_nt256_bf16_k."""
+    _persistent_loop(M, N, K, pro, epi, torch.bfloat16,
+                     lambda nb: sorted({0, 1, 2, 15, 16, nb // 2, nb - 5, nb - 2, nb - 1, 511, 512, 513}))
 
 
 # ---- LayerNorm folded into the weights and the epilogue (hwgat_ln_fold + pro 3): the form norm1 -> qkv and norm2 -> fc1
@@ -477,15 +625,22 @@ def test_layernorm_folded_into_weights_and_epilogue(M, N, K, dtype):
     lin = xn @ W.double().t() + b.double()
     tol = 3e-5 if dtype == "f32" else 1e-2
     assert HF.LN_FOLD
-    got = HF.linear_nt_ln(Ad, W.to(DEV), b.to(DEV), ln)
+    got = _nt_ln(Ad, W.to(DEV), b.to(DEV), ln)
     assert rel_err(got.float().cpu(), lin) < tol
+    par = _fold_f32(NT_F32, ln[0], ln[1], s, K, lin) if dtype == "f32" else NT_BF16_FOLD
+    fam = "nt_f32_fold: " if dtype == "f32" else "nt_bf16_fold: "
+    linear_parity(got, lin, tol_norm=tol, **par, what=fam + "bias")
     p = 0.1
-    u, h1 = HF.linear_nt_ln(Ad, W.to(DEV), b.to(DEV), ln, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
+    u, h1 = _nt_ln(Ad, W.to(DEV), b.to(DEV), ln, epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
     mask = HF.dropout_mask((M, N), 1234, p, DEV).cpu().double()
     assert rel_err(h1.float().cpu(), lin) < tol
     assert rel_err(u.float().cpu(), torch.nn.functional.gelu(h1.float().cpu().double()) * mask) < (tol if dtype == "f32" else 6e-3)
+    u_ref = torch.nn.functional.gelu(h1.float().cpu().double()) * mask
+    linear_parity(h1, lin, tol_norm=tol, **par, what=fam + "gelu_drop pre-activation")
+    # (u is compared with the GELU of the STORED pre-activation: the fold's cancellation does not enter)
+    linear_parity(u, u_ref, tol_norm=tol, **(NT_F32 if dtype == "f32" else par), what=("nt_f32: fold " if dtype == "f32" else fam) + "gelu_drop")
     # and it is the same function as the normalising loader (pro 1) up to rounding
-    old = HF.linear_nt(Ad, W.to(DEV).to(dt), b.to(DEV), pro=HF.PRO_LN, ln=ln)
+    old = _nt(Ad, W.to(DEV).to(dt), b.to(DEV), pro=HF.PRO_LN, ln=ln)
     assert rel_err(got.float().cpu(), old.float().cpu().double()) < (3e-5 if dtype == "f32" else 1.5e-2)
 
 
@@ -500,20 +655,24 @@ def test_gelu_factor_stored_forward_multiplied_backward(M, N, K, dtype):
     Ad, Wd = A.to(dt).to(DEV), W.to(dt).to(DEV)
     lin = Ad.float().cpu().double() @ Wd.float().cpu().double().t() + b.double()
     mask = HF.dropout_mask((M, N), 1234, p, DEV).cpu().double()
-    u, gp = HF.linear_nt(Ad, Wd, b.to(DEV), epi=HF.EPI_BIAS_GELU_DROP_G, epi_seed=1234, epi_p=p)
+    u, gp = _nt(Ad, Wd, b.to(DEV), epi=HF.EPI_BIAS_GELU_DROP_G, epi_seed=1234, epi_p=p)
     x = lin.clone().requires_grad_(True)
     torch.nn.functional.gelu(x).sum().backward()
     tol = 5e-5 if dtype == "f32" else 6e-3
     assert rel_err(u.float().cpu(), torch.nn.functional.gelu(lin) * mask) < tol
     assert rel_err(gp.float().cpu(), x.grad * mask) < tol
+    par = NT_F32_GELU if dtype == "f32" else NT_BF16
+    fam = "nt_f32_gelu: " if dtype == "f32" else "nt_bf16: "
+    linear_parity((u, gp), (torch.nn.functional.gelu(lin) * mask, x.grad * mask), tol_norm=tol, **par, what=fam + "gelu_drop_g")
     # the same pair as the older codes
-    u2, h1 = HF.linear_nt(Ad, Wd, b.to(DEV), epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
+    u2, h1 = _nt(Ad, Wd, b.to(DEV), epi=HF.EPI_BIAS_GELU_DROP, epi_seed=1234, epi_p=p)
     assert rel_err(u.float().cpu(), u2.float().cpu().double()) < tol
     dy = torch.randn(M, K, generator=torch.Generator().manual_seed(4)).to(dt).to(DEV)       # "A" = dY [M,K'], W [N,K']
-    got = HF.linear_nt(dy, Wd, None, epi=HF.EPI_MUL_AUX, aux=gp)
+    got = _nt(dy, Wd, None, epi=HF.EPI_MUL_AUX, aux=gp)
     ref = (dy.float().cpu().double() @ Wd.float().cpu().double().t()) * gp.float().cpu().double()
     assert rel_err(got.float().cpu(), ref) < tol
-    old = HF.linear_nt(dy, Wd, None, epi=HF.EPI_GELU_BWD, aux=h1, epi_seed=1234, epi_p=p)
+    linear_parity(got, ref, tol_norm=tol, **par, what=fam + "mul_aux")
+    old = _nt(dy, Wd, None, epi=HF.EPI_GELU_BWD, aux=h1, epi_seed=1234, epi_p=p)
     assert rel_err(got.float().cpu(), old.float().cpu().double()) < (1e-4 if dtype == "f32" else 1.5e-2)
 
 
@@ -573,7 +732,10 @@ def test_epilogue_row_statistics_on_rows_whose_mean_dwarfs_their_spread(offset, 
     W = (torch.randn(N, K, device=DEV, generator=g) * 0.05).to(dtype)
     b = torch.zeros(N, device=DEV)
     res = (torch.randn(M, N, device=DEV, generator=g) + offset).to(dtype)
-    out, mean, rstd = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=0.0, stats=True)
+    out, mean, rstd = _nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=9, epi_p=0.0, stats=True)
+    f32 = dtype == torch.float32
+    linear_parity(out, res.double() + A.double() @ W.double().t(), tol_norm=TOL if f32 else BT, **(NT_F32 if f32 else NT_BF16),
+                  what=("nt_f32" if f32 else "nt_bf16") + f": drop_res, row mean {offset}")
     ones = torch.ones(N, device=DEV)
     m2, r2 = HF.ln_stats(out, ones, ones)
     truth_m = out.double().mean(-1)
@@ -613,17 +775,17 @@ def test_bf16_nt8w_every_epilogue_every_element(M, N, K, epi):
     got2 = ref2 = None
     tol = BT
     if epi == "none":
-        got, ref = HF.linear_nt(A, W, None, epi=HF.EPI_NONE), lin
+        got, ref = _nt(A, W, None, epi=HF.EPI_NONE), lin
     elif epi == "bias":
-        got, ref = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS), lin + b.double()
+        got, ref = _nt(A, W, b, epi=HF.EPI_BIAS), lin + b.double()
     elif epi in ("drop_res", "drop_res_stats", "drop_res_merge"):
         ref = res.double() + (lin + b.double()) * mask
         if epi == "drop_res":
-            got = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=4321, epi_p=p)
+            got = _nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=4321, epi_p=p)
         else:
             F, Kt = 4, M // 8                               # (B = 2, F = 4, K_tok = M / 8) token grid
             merge = (F, Kt) if epi == "drop_res_merge" else None
-            got, mean, rstd = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=4321, epi_p=p, stats=True, merge=merge)
+            got, mean, rstd = _nt(A, W, b, epi=HF.EPI_BIAS_DROP_RES, res=res, epi_seed=4321, epi_p=p, stats=True, merge=merge)
             if merge:
                 ref = ref.view(2, F // 2, 2, Kt, N).transpose(2, 3).reshape(-1, 2 * N)
                 got = got.reshape(-1, 2 * N)
@@ -631,7 +793,7 @@ def test_bf16_nt8w_every_epilogue_every_element(M, N, K, epi):
             assert rel_err(mean.cpu(), gd.mean(-1).cpu()) < 1e-5
             assert rel_err(rstd.cpu(), (gd.var(-1, unbiased=False) + 1e-5).rsqrt().cpu()) < 1e-5
     elif epi == "mul_aux":
-        got, ref = HF.linear_nt(A, W, None, epi=HF.EPI_MUL_AUX, aux=aux), lin * aux.double()
+        got, ref = _nt(A, W, None, epi=HF.EPI_MUL_AUX, aux=aux), lin * aux.double()
     else:
         if epi.startswith("fold"):
             if K in (128, 256, 512, 1024):
@@ -642,12 +804,12 @@ def test_bf16_nt8w_every_epilogue_every_element(M, N, K, epi):
             pre = xn @ W32.double().t() + b.double()
             tol = 1.5e-2                                    # the fold cancels mean * s against the product (bf16 operands)
             if epi == "fold_bias":
-                got, ref = HF.linear_nt_ln(A, W32, b, ln), pre
+                got, ref = _nt_ln(A, W32, b, ln), pre
             else:
-                got, got2 = HF.linear_nt_ln(A, W32, b, ln, epi=HF.EPI_BIAS_GELU_DROP_G, epi_seed=4321, epi_p=p)
+                got, got2 = _nt_ln(A, W32, b, ln, epi=HF.EPI_BIAS_GELU_DROP_G, epi_seed=4321, epi_p=p)
         else:
             pre = lin + b.double()
-            got, got2 = HF.linear_nt(A, W, b, epi=HF.EPI_BIAS_GELU_DROP_G, epi_seed=4321, epi_p=p)
+            got, got2 = _nt(A, W, b, epi=HF.EPI_BIAS_GELU_DROP_G, epi_seed=4321, epi_p=p)
         if got2 is not None:
             h = pre.clone().requires_grad_(True)
             torch.nn.functional.gelu(h).sum().backward()
@@ -662,6 +824,9 @@ def test_bf16_nt8w_every_epilogue_every_element(M, N, K, epi):
     assert float(per_tile.max()) < 3 * tol, float(per_tile.max())
     if ref2 is not None:
         assert rel_err(got2.float().cpu(), ref2.cpu()) < 2 * tol
+    fold = epi.startswith("fold")
+    linear_parity(got if got2 is None else (got, got2), ref if ref2 is None else (ref, ref2), tol_norm=tol if got2 is None else (tol, 2 * tol),
+                  **(NT_BF16_FOLD if fold else NT_BF16), what=("nt_bf16_fold: " if fold else "nt_bf16: ") + "eight-wave " + epi)
 
 
 # ---- the eight-wave LDS-DMA bf16 weight-gradient kernel (gemm_bf16_tn8w.hip): N % 256 == K % 256 == 0, M % 128 == 0,
@@ -690,4 +855,5 @@ def test_bf16_tn8w_weight_and_bias_grad_every_element(M, N, K):
     dW2 = torch.zeros(N, K, device=DEV)
     HF.linear_tn(dY, X, dW2, None)
     assert float((dW2.double() - (ref_w - dW0.double())).norm() / scale_w) < 1e-4
+    linear_parity((dW2, db - db0), (ref_w - dW0.double(), dY.double().sum(0)), tol_norm=1e-4, **TN_BF16, what="tn_bf16: eight-wave")
 

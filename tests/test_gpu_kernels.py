@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import hwgat_oracle as O
-from helpers import attn_parity, entrywise, rel_err, tie_free_threshold
+from helpers import attn_parity, entrywise, rel_err, tensor_parity, tie_free_threshold
 
 pytestmark = pytest.mark.gpu
 hw = importlib.import_module("sl-hwgat_amd")
@@ -21,6 +21,15 @@ BF16_NORM = dict(o=BF16_TOL, dq=2 * BF16_TOL, dk=2 * BF16_TOL, dv=2 * BF16_TOL)
 # comments), capped at 1e-4 (fp32) and 2e-2 (bf16)
 WIN_ENTRY_F32 = dict(o=8e-7, dq=1.1e-6, dk=9e-7, dv=7.5e-7)            # observed 2.6e-7 / 3.6e-7 / 2.8e-7 / 2.4e-7
 WIN_ENTRY_BF16 = dict(o=1.5e-2, dq=1.3e-2, dk=1.5e-2, dv=1.5e-2)       # observed 4.9e-3 / 4.4e-3 / 5.1e-3 / 4.8e-3
+# entry and row bounds of tensor_parity on the LayerNorm family at the model's widths (layernorm.hip): 3 x the worst error
+# observed on an MI355X against the fp64 reference over this module's cases (in the comments), at or below the caps
+# (bf16-stored outputs: entry 1.2e-2, row 1e-2; fp32 outputs: 1e-5 each)
+LN_F32 = dict(tol_entry=1.2e-6, tol_row=5.1e-6)                       # observed 4.1e-7 / 1.7e-6 (y, dx, masked copy, xn, pooled output)
+LN_BF16 = dict(tol_entry=1.05e-2, tol_row=1e-2)                       # observed 3.5e-3 / 4.4e-3 (row: the cap; rows differ in scale, the
+#                                                                        largest carries 1.6 x the RMS row norm and its rounding with it)
+LN_STAT = 5.1e-7                                                      # observed 1.7e-7 (mean, rstd entry-wise)
+LN_DG = 5.8e-6                                                        # observed 1.9e-6 over three runs (atomic order: 1.6e-6 ... 1.9e-6) (dgamma, dbeta
+#                                                                        entry-wise; fp32 from either storage type)
 
 
 def _windows(qkv, n_heads, shifted):
@@ -211,9 +220,14 @@ def test_layer_norm_fwd_bwd(d):
         assert rel_err(xg.grad.cpu(), xr.grad) < F32_TOL
         assert rel_err(wg.grad.cpu(), wr.grad) < F32_TOL
         assert rel_err(bg.grad.cpu(), br.grad) < F32_TOL
+        tensor_parity(y, O.layer_norm(x.double(), w.double(), b.double()), tol_norm=F32_TOL, **LN_F32, what=f"ln_f32: y d {d} n {n}")
+        tensor_parity(xg.grad, xr.grad, tol_norm=F32_TOL, **LN_F32, what=f"ln_f32: dx d {d} n {n}")
+        tensor_parity(wg.grad, wr.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dgamma d {d} n {n}")
+        tensor_parity(bg.grad, br.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dbeta d {d} n {n}")
         xb = x.to(DEV, torch.bfloat16)
         yb = HF.layer_norm(xb, wg.detach(), bg.detach())
         assert rel_err(yb.float().cpu(), O.layer_norm(xb.cpu().double(), w.double(), b.double())) < BF16_TOL
+        tensor_parity(yb, O.layer_norm(xb.cpu().double(), w.double(), b.double()), tol_norm=BF16_TOL, **LN_BF16, what=f"ln_bf16: y d {d} n {n}")
 
 
 def test_ln_bwd_residual_argument():
@@ -350,6 +364,10 @@ def test_ln_mean_pool(d, n_tok, B):
     assert rel_err(xg.grad.cpu(), xr.grad) < F32_TOL
     assert rel_err(wg.grad.cpu(), wr.grad) < 1e-4
     assert rel_err(bg.grad.cpu(), br.grad) < F32_TOL
+    tensor_parity(out, ref, tol_norm=F32_TOL, **LN_F32, what=f"ln_f32: pool out d {d}")
+    tensor_parity(xg.grad, xr.grad, tol_norm=F32_TOL, **LN_F32, what=f"ln_f32: pool dx d {d}")
+    tensor_parity(wg.grad, wr.grad, tol_norm=1e-4, tol_entry=LN_DG, what=f"ln_dg: pool dgamma d {d}")
+    tensor_parity(bg.grad, br.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: pool dbeta d {d}")
 
 
 def test_full_size_properties_config2():
@@ -458,6 +476,117 @@ def test_ln_bwd_xn_also_writes_the_layernorm_output(d, dtype):
             assert torch.equal(out[1], dxm0)
         ref = O.layer_norm(x.cpu().double(), w.cpu().double(), b.cpu().double())
         assert rel_err(xn.float().cpu(), ref) < (F32_TOL if dtype == torch.float32 else BF16_TOL)
+        f32 = dtype == torch.float32
+        tensor_parity(xn, ref, tol_norm=F32_TOL if f32 else BF16_TOL, **(LN_F32 if f32 else LN_BF16),
+                      what=("ln_f32" if f32 else "ln_bf16") + f": xn d {d} mask {mask is not None}")
         y = torch.empty_like(x)
         L.call("hwgat_ln_fwd", L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(mean), L.ptr(rstd), n, d, dc, L.stream())
         assert rel_err(xn.float().cpu(), y.float().cpu().double()) < (1e-6 if dtype == torch.float32 else 4e-3)
+
+
+# ---- the LayerNorm kernels of the model's own widths (layernorm.hip) against fp64, every output of every entry point in
+# both storage types, through their grid-stride loops.  ln_grid gives a block of 4 waves x RPW rows a pass (RPW = 2 rows
+# per wave at d = 128, else 1) and caps the forward at 2048 blocks, the backward at 1024: one pass covers 1024 * 4 * RPW
+# rows backward and 2048 * 4 * RPW forward.  The two large row counts lie 1003 rows above those, so blocks loop and the
+# walk ends ragged: 1003 is odd, so the last wave pass is partly empty and at d = 128 the last row pair half empty.
+def _ln_rows(d):
+    rpw = 2 if d == 128 else 1
+    return [1, 7, 64, 1000, 1024 * 4 * rpw + 1003, 2048 * 4 * rpw + 1003]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d", [128, 256, 512, 1024])
+def test_layernorm_model_widths_every_output_against_fp64(d, dtype):
+    """forward y, mean, rstd; backward dx (row by row), masked copy, xn, dgamma, dbeta (entry-wise) of the plain, masked,
+    xn and xn + masked entry points, default and deterministic, with and without the residual.  Rows have a per-row
+    scale and a mean of three standard deviations.  The fp64 reference is computed on the device and reads the stored
+    (fp32 / bf16) values, so dgamma / dbeta / mean / rstd -- fp32 sums of exactly known terms -- are held to the fp32 bounds in
+    both storage types."""
+    f32 = dtype == torch.float32
+    tol, par, fam = (F32_TOL, LN_F32, "ln_f32") if f32 else (BF16_TOL, LN_BF16, "ln_bf16")
+    for n in _ln_rows(d):
+        g = torch.Generator(device=DEV).manual_seed(d + n)
+        x = (torch.randn(n, d, device=DEV, generator=g) * (0.5 + torch.rand(n, 1, device=DEV, generator=g))
+             + 3.0 * torch.randn(n, 1, device=DEV, generator=g)).to(dtype)
+        gm, bt = 1 + 0.3 * torch.randn(d, device=DEV, generator=g), 0.3 * torch.randn(d, device=DEV, generator=g)
+        dy = torch.randn(n, d, device=DEV, generator=g).to(dtype)
+        dres = torch.randn(n, d, device=DEV, generator=g).to(dtype)
+        xr = x.double().requires_grad_(True)
+        gr, br = gm.double().requires_grad_(True), bt.double().requires_grad_(True)
+        yr = torch.nn.functional.layer_norm(xr, (d,), gr, br, 1e-5)
+        yr.backward(dy.double())
+        yr, dxr = yr.detach(), xr.grad
+        tag = f"d {d} n {n}"
+        y = HF.layer_norm(x, gm, bt)
+        tensor_parity(y, yr, tol_norm=tol, **par, what=f"{fam}: y {tag}")
+        mean, rstd = HF.ln_stats(x, gm, bt)
+        tensor_parity(mean, x.double().mean(1), tol_norm=F32_TOL, tol_entry=LN_STAT, what=f"ln_stat: mean {dtype} {tag}")
+        tensor_parity(rstd, (x.double().var(1, unbiased=False) + 1e-5).rsqrt(), tol_norm=F32_TOL, tol_entry=LN_STAT,
+                      what=f"ln_stat: rstd {dtype} {tag}")
+        mk = HF.dropout_mask((n, d), 5, 0.3, DEV).double()
+        for det in (False, True):
+            # (the masked and xn entry points require the residual: they refuse a NULL dres)
+            for variant in ("plain", "masked", "xn", "xn_masked", "plain_nores"):
+                res = None if variant == "plain_nores" else dres
+                want_dx = dxr if res is None else dxr + dres.double()
+                # poisoned accumulators would be wrong (dgamma / dbeta accumulate); dx, the masked copy and xn are
+                # allocated inside the wrapper
+                dg, db = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
+                kw = dict(deterministic=det)
+                if "masked" in variant:
+                    kw.update(mask=(5, 0.3))
+                if "xn" in variant:
+                    kw.update(beta=bt)
+                r = HF.ln_backward(dy, x, mean, rstd, gm, res, dg, db, **kw)
+                r = r if isinstance(r, tuple) else (r,)
+                v = f"{tag} {variant} det {det}"
+                tensor_parity(r[0], want_dx, tol_norm=tol, **par, what=f"{fam}: dx {v}")
+                k = 1
+                if "masked" in variant:
+                    tensor_parity(r[1], want_dx * mk, tol_norm=tol, **par, what=f"{fam}: dxm {v}")
+                    k = 2
+                if "xn" in variant:
+                    tensor_parity(r[k], yr, tol_norm=tol, **par, what=f"{fam}: xn {v}")
+                tensor_parity(dg, gr.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dgamma {dtype} {v}")
+                tensor_parity(db, br.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dbeta {dtype} {v}")
+        # the autograd path (hwgat_ln_bwd without a residual through _LayerNorm.backward)
+        xa, ga, ba = x.clone().requires_grad_(True), gm.clone().requires_grad_(True), bt.clone().requires_grad_(True)
+        HF.layer_norm(xa, ga, ba).backward(dy)
+        tensor_parity(xa.grad, dxr, tol_norm=tol, **par, what=f"{fam}: dx autograd {tag}")
+        tensor_parity(ga.grad, gr.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dgamma {dtype} autograd {tag}")
+        tensor_parity(ba.grad, br.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dbeta {dtype} autograd {tag}")
+
+
+@pytest.mark.parametrize("d,n_tok,B", [(512, 640, 3), (128, 37, 2), (1024, 16, 1), (128, 6000, 3), (1024, 1001, 2)])
+@pytest.mark.parametrize("det", [False, True])
+def test_ln_mean_pool_bf16_against_fp64(d, n_tok, B, det):
+    """ln_mean_pool on bf16 activations at the model's widths, atomic and deterministic form: output, dx, dgamma, dbeta.
+    A launch splits the tokens of a clip into hwgat_lnpool_partial_rows(B, n_tok) chunks of ceil(n_tok / chunks) tokens:
+    37 tokens make 5 chunks of 8 with 5 in the last, 1001 make 126 of 8 with 1 in the last, and (B 3, 6000 tokens) make 682
+    chunks of 9, of which the last 15 hold no token at all (asserted below)."""
+    chunks = hw._lib.lib().hwgat_lnpool_partial_rows(B, n_tok)
+    per = -(-n_tok // chunks)
+    if n_tok in (37, 1001, 6000):
+        assert n_tok % chunks != 0 and chunks * per > n_tok
+    if n_tok == 6000:
+        assert (chunks - 1) * per >= n_tok                   # whole chunks without a token
+    g = torch.Generator(device=DEV).manual_seed(d + n_tok)
+    x = (torch.randn(B, n_tok, d, device=DEV, generator=g) * (0.5 + torch.rand(B, n_tok, 1, device=DEV, generator=g))
+         + 3.0 * torch.randn(B, n_tok, 1, device=DEV, generator=g)).bfloat16()
+    w, b = 1 + 0.3 * torch.randn(d, device=DEV, generator=g), 0.3 * torch.randn(d, device=DEV, generator=g)
+    df = torch.randn(B, d, device=DEV, generator=g)
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
+    ref = torch.nn.functional.layer_norm(xr, (d,), wr, br, 1e-5).mean(1)
+    ref.backward(df.double())
+    xg, wg, bg = (t.clone().requires_grad_(True) for t in (x, w, b))
+    out = HF.ln_mean_pool(xg, wg, bg, deterministic=det)
+    out.backward(df)
+    tag = f"d {d} n_tok {n_tok} B {B} det {det}"
+    # the pooled output and dgamma / dbeta are fp32 sums over the stored bf16 rows, which the reference reads too
+    tensor_parity(out, ref, tol_norm=F32_TOL, **LN_F32, what=f"ln_f32: pool out bf16 {tag}")
+    tensor_parity(xg.grad, xr.grad, tol_norm=BF16_TOL, **LN_BF16, what=f"ln_bf16: pool dx {tag}")
+    tensor_parity(wg.grad, wr.grad, tol_norm=1e-4, tol_entry=LN_DG, what=f"ln_dg: pool dgamma bf16 {tag}")
+    tensor_parity(bg.grad, br.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: pool dbeta bf16 {tag}")
+    if det:
+        out2 = HF.ln_mean_pool(x, w, b, deterministic=True)
+        assert torch.equal(out.detach(), out2)
