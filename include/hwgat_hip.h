@@ -57,8 +57,11 @@ extern "C" {
  *         hwgat_lnwpool_bwd_masked, LayerNorm + weighted token pool (GATE)
  *   4005  the ST-GCN baseline (additions only): hwgat_stgcn_weight_prep, hwgat_stgcn_conv, hwgat_stgcn_conv_dw(_bytes),
  *         hwgat_stgcn_colsum, hwgat_stgcn_red_bytes, hwgat_stgcn_bn_{stats,eval_stats,apply,bwd},
- *         hwgat_stgcn_agg_{fwd,bwd}(_bytes), hwgat_stgcn_pool_{fwd,bwd}, hwgat_stgcn_copy_cols */
-#define HWGAT_ABI_VERSION 4005
+ *         hwgat_stgcn_agg_{fwd,bwd}(_bytes), hwgat_stgcn_pool_{fwd,bwd}, hwgat_stgcn_copy_cols
+ *   4006  the DecoupledGCN baseline (additions only): hwgat_dgcn_agg_{fwd,bwd}(_bytes), hwgat_dgcn_gate_{sum,apply,bwd},
+ *         hwgat_dgcn_abs_sum, hwgat_dgcn_draw, hwgat_dgcn_mask_{spatial,temporal}, hwgat_dgcn_merge(_bwd),
+ *         hwgat_dgcn_masked_sum */
+#define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -616,6 +619,59 @@ int hwgat_stgcn_pool_fwd(const float* x, float* out, int N, int R, int C, uint32
 int hwgat_stgcn_pool_bwd(const float* dout, float* dx, int N, int R, int C, uint32_t seed, float p,
                          const uint32_t* seed_base, void* stream);
 int hwgat_stgcn_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, int64_t rows, void* stream);
+
+/* ---- DecoupledGCN baseline (ABI 4006; reference hwgat/models/DecoupledGCN.py).  fp32 only, channels-last activations
+ * (N, T, V, C) with V <= 32 joints; everything else of a unit (1x1 / temporal convolutions, BatchNorm, pooled head) runs
+ * on the hwgat_stgcn_* entry points.  No kernel uses an atomic: every sum has a fixed order.
+ *
+ * Decoupled aggregation, An (3, G, V, V) the column-normalised learnable adjacency, channel c uses group c mod G
+ * (G divides C):
+ * hwgat_dgcn_agg_fwd: out (NT, V, C)[f, w, c] = sum_{k, v} An[k, c mod G, v, w] y[f, v, k C + c], y (NT, V, 3 C).
+ * hwgat_dgcn_agg_bwd: dy (NT, V, 3 C)[f, v, k C + c] = sum_w An[k, c mod G, v, w] d[f, w, c] and, when dAn is not NULL,
+ *   dAn[k, g, v, w] = sum_{f, c = g mod G} y[f, v, k C + c] d[f, w, c] (written; ws >= hwgat_dgcn_agg_bwd_bytes(NT, G)).
+ *
+ * Attention gates, s_v (N, V), s_t (N, T), s_c (N, C) (any of them NULL = 0):
+ * hwgat_dgcn_gate_sum: out = scale * sum over one axis of
+ *     h (g' (1 + s_v[n, v]) (1 + s_t[n, t]) (1 + s_c[n, c]) + m[n, t, c] m_scale),   g' = g (N, T, V, C) or 1 when NULL,
+ *   the m term absent when m is NULL; axis 0: over t, out (N, V, C); axis 1: over v, out (N, T, C).
+ * hwgat_dgcn_gate_apply: out = h (1 + s_v) (1 + s_t) (1 + s_c).
+ * hwgat_dgcn_gate_bwd: dh = d (1 + s_v) (1 + s_t) (1 + s_c) + dm1[n, t, c] (1 + s_v) / V + dm0[n, v, c] / T, the gradient
+ *   of the gated output and of the two squeezes mean_V h (1 + s_v) (N, T, C) and mean_T h (N, V, C) with respect to h.
+ *
+ * DropGraph.  z = x, or (x - mean) rstd gamma + beta when mean is not NULL (a BatchNorm read on the fly):
+ * hwgat_dgcn_abs_sum: axis 0: out (N, V) = sum_{t, c} |z|; axis 1: out (N, T) = sum_{v, c} |z| fs[n, v] (fs NULL = 1).
+ * hwgat_dgcn_draw: out[i] = 1 where the hash uniform of (seed + *seed_base, i) is below p[i], else 0 (p <= 0: never,
+ *   p >= 1: always; the uniform of an element does not depend on p).
+ * hwgat_dgcn_mask_spatial: mask[n, w] = 0 where sum_v seeds[n, v] A[v, w] > 0.001, else 1; f = mask * scale and
+ *   scale[0] = N V / sum(mask) over the whole batch (one workgroup; an all-zero mask gives inf, as the reference).
+ * hwgat_dgcn_mask_temporal: mask[n, t] = 1 - max_{|t' - t| <= block / 2} seeds[n, t'] (block odd), f and scale likewise.
+ * hwgat_dgcn_merge: out = relu(bn(c) fs1[n, v] ft1[n, t] + r' fs2[n, v] ft2[n, t]), r' = r or its BatchNorm read when
+ *   res_mean is not NULL.
+ * hwgat_dgcn_merge_bwd: g = dout [out > 0]; dz1 = g fs1 ft1, dz2 = g fs2 ft2.
+ * hwgat_dgcn_masked_sum: out = a [ma > 0] + b [mb > 0] (a mask that is NULL passes everything). */
+int hwgat_dgcn_agg_fwd(const float* y, const float* An, float* out, int64_t NT, int V, int C, int G, void* stream);
+int64_t hwgat_dgcn_agg_bwd_bytes(int64_t NT, int G);
+int hwgat_dgcn_agg_bwd(const float* y, const float* d, const float* An, float* dy, float* dAn, int64_t NT, int V, int C,
+                       int G, float* ws, int64_t ws_bytes, void* stream);
+int hwgat_dgcn_gate_sum(const float* h, const float* g, const float* sv, const float* st, const float* sc, const float* m,
+                        float m_scale, float* out, int N, int T, int V, int C, int axis, float scale, void* stream);
+int hwgat_dgcn_gate_apply(const float* h, const float* sv, const float* st, const float* sc, float* out, int N, int T,
+                          int V, int C, void* stream);
+int hwgat_dgcn_gate_bwd(const float* d, const float* sv, const float* st, const float* sc, const float* dm1,
+                        const float* dm0, float* dh, int N, int T, int V, int C, void* stream);
+int hwgat_dgcn_abs_sum(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                       const float* fs, float* out, int N, int T, int V, int C, int axis, void* stream);
+int hwgat_dgcn_draw(const float* p, float* out, int64_t n, uint32_t seed, const uint32_t* seed_base, void* stream);
+int hwgat_dgcn_mask_spatial(const float* seeds, const float* A, float* f, float* scale, int N, int V, void* stream);
+int hwgat_dgcn_mask_temporal(const float* seeds, float* f, float* scale, int N, int T, int block, void* stream);
+int hwgat_dgcn_merge(const float* c, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                     const float* r, const float* res_mean, const float* res_rstd, const float* res_gamma,
+                     const float* res_beta, const float* fs1, const float* ft1, const float* fs2, const float* ft2,
+                     float* out, int N, int T, int V, int C, void* stream);
+int hwgat_dgcn_merge_bwd(const float* dout, const float* out, const float* fs1, const float* ft1, const float* fs2,
+                         const float* ft2, float* dz1, float* dz2, int N, int T, int V, int C, void* stream);
+int hwgat_dgcn_masked_sum(const float* a, const float* ma, const float* b, const float* mb, float* out, int64_t n,
+                          void* stream);
 
 #ifdef __cplusplus
 }

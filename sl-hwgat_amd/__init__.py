@@ -18,9 +18,11 @@ from .models.WGATE import Model as WGATEModel
 from .models.GATE import Model as GATEModel
 from .models.Transformer import Model as TransformerModel
 from .models.STGCN import Model as STGCNModel
-from .models.model_params import HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams, STGCNParams
+from .models.DecoupledGCN import Model as DecoupledGCNModel
+from .models.model_params import (HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams, STGCNParams,
+                                  DecoupledGCNParams)
 
 __all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
            "TransformerModel",
-           "TransformerParams", "STGCNModel", "STGCNParams", "functional",
+           "TransformerParams", "STGCNModel", "STGCNParams", "DecoupledGCNModel", "DecoupledGCNParams", "functional",
            "part_table", "_lib", "checkpoint", "augment"]

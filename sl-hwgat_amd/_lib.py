@@ -109,6 +109,19 @@ _SIGS = {
     "hwgat_stgcn_pool_fwd": [_P, _P, _I, _I, _I, _U, _F, _P, _P],
     "hwgat_stgcn_pool_bwd": [_P, _P, _I, _I, _I, _U, _F, _P, _P],
     "hwgat_stgcn_copy_cols": [_P, _I, _P, _I, _L, _P],
+    "hwgat_dgcn_agg_fwd": [_P, _P, _P, _L, _I, _I, _I, _P],
+    "hwgat_dgcn_agg_bwd_bytes": [_L, _I],
+    "hwgat_dgcn_agg_bwd": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P, _L, _P],
+    "hwgat_dgcn_gate_sum": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _F, _P],
+    "hwgat_dgcn_gate_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "hwgat_dgcn_gate_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "hwgat_dgcn_abs_sum": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "hwgat_dgcn_draw": [_P, _P, _L, _U, _P, _P],
+    "hwgat_dgcn_mask_spatial": [_P, _P, _P, _P, _I, _I, _P],
+    "hwgat_dgcn_mask_temporal": [_P, _P, _P, _I, _I, _I, _P],
+    "hwgat_dgcn_merge": [_P] * 15 + [_I, _I, _I, _I, _P],
+    "hwgat_dgcn_merge_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "hwgat_dgcn_masked_sum": [_P, _P, _P, _P, _P, _L, _P],
 }
 _lib = None
 

@@ -1204,3 +1204,115 @@ def stgcn_copy_cols(x, width):
     out = torch.empty(*x.shape[:-1], width, device=x.device, dtype=torch.float32)
     call("hwgat_stgcn_copy_cols", ptr(x), C, ptr(out), width, x.numel() // C, stream())
     return out
+
+
+# ---------------------------------------------------------------- DecoupledGCN baseline (models/DecoupledGCN.py, dgcn_block.py)
+# fp32, channels-last (N, T, V, C).  Thin launchers of csrc/dgcn_ops.hip; the autograd node is in dgcn_block.py.
+def dgcn_aggregate(y, An, groups):
+    """(N, T, V, 3C) -> (N, T, V, C): sum_{k,v} An[k, c mod G, v, w] y[.., v, k C + c], An (3, G, V, V)"""
+    N, T, V, C3 = y.shape
+    out = torch.empty(N, T, V, C3 // 3, device=y.device, dtype=torch.float32)
+    call("hwgat_dgcn_agg_fwd", ptr(y), ptr(An), ptr(out), N * T, V, C3 // 3, groups, stream())
+    return out
+
+
+def dgcn_aggregate_backward(y, d, An, groups, want_dAn=True):
+    """(dy, dAn or None) of dgcn_aggregate"""
+    N, T, V, C3 = y.shape
+    dy = torch.empty_like(y)
+    dAn = ws = None
+    nbytes = 0
+    if want_dAn:
+        dAn = torch.empty_like(An)
+        ws, nbytes = _ws(_lib.lib().hwgat_dgcn_agg_bwd_bytes(N * T, groups), y.device)
+    call("hwgat_dgcn_agg_bwd", ptr(y), ptr(d), ptr(An), ptr(dy), ptr(dAn), N * T, V, C3 // 3, groups, ptr(ws), nbytes,
+         stream())
+    return dy, dAn
+
+
+def dgcn_gate_sum(h, axis, scale=1.0, g=None, sv=None, st=None, sc=None, m=None, m_scale=0.0):
+    """scale * sum over t (axis 0, -> (N, V, C)) or over v (axis 1, -> (N, T, C)) of
+    h (g (1 + sv[n, v]) (1 + st[n, t]) (1 + sc[n, c]) + m[n, t, c] m_scale); absent factors are 1, an absent m term 0"""
+    N, T, V, C = h.shape
+    out = torch.empty(N, V if axis == 0 else T, C, device=h.device, dtype=torch.float32)
+    call("hwgat_dgcn_gate_sum", ptr(h), ptr(g), ptr(sv), ptr(st), ptr(sc), ptr(m), float(m_scale), ptr(out), N, T, V, C,
+         int(axis), float(scale), stream())
+    return out
+
+
+def dgcn_gate_apply(h, sv, st, sc):
+    """h (1 + sv[n, v]) (1 + st[n, t]) (1 + sc[n, c])"""
+    N, T, V, C = h.shape
+    out = torch.empty_like(h)
+    call("hwgat_dgcn_gate_apply", ptr(h), ptr(sv), ptr(st), ptr(sc), ptr(out), N, T, V, C, stream())
+    return out
+
+
+def dgcn_gate_backward(d, sv, st, sc, dm1, dm0):
+    """dh = d (1 + sv)(1 + st)(1 + sc) + dm1[n, t, c] (1 + sv) / V + dm0[n, v, c] / T"""
+    N, T, V, C = d.shape
+    dh = torch.empty_like(d)
+    call("hwgat_dgcn_gate_bwd", ptr(d), ptr(sv), ptr(st), ptr(sc), ptr(dm1), ptr(dm0), ptr(dh), N, T, V, C, stream())
+    return dh
+
+
+def dgcn_abs_sum(x, axis, bn=None, fs=None):
+    """axis 0: (N, V) = sum_{t,c} |z|; axis 1: (N, T) = sum_{v,c} |z| fs[n, v]; z = x or its BatchNorm read
+    bn = (mean, rstd, gamma, beta)"""
+    N, T, V, C = x.shape
+    b = bn or (None, None, None, None)
+    out = torch.empty(N, V if axis == 0 else T, device=x.device, dtype=torch.float32)
+    call("hwgat_dgcn_abs_sum", ptr(x), ptr(b[0]), ptr(b[1]), ptr(b[2]), ptr(b[3]), ptr(fs), ptr(out), N, T, V, C, int(axis),
+         stream())
+    return out
+
+
+def dgcn_draw(p, seed, seed_base=None):
+    """Bernoulli(p) seeds (1.0 / 0.0) from the hash uniform of (seed + *seed_base, element index)"""
+    out = torch.empty_like(p)
+    call("hwgat_dgcn_draw", ptr(p), ptr(out), p.numel(), seed & 0xFFFFFFFF, ptr(seed_base), stream())
+    return out
+
+
+def dgcn_mask_spatial(seeds, A):
+    """(mask * scale (N, V), scale (1,)) of the spatial DropGraph: joints reached by a seed through A (V, V) are dropped"""
+    N, V = seeds.shape
+    f = torch.empty_like(seeds)
+    scale = torch.empty(1, device=seeds.device, dtype=torch.float32)
+    call("hwgat_dgcn_mask_spatial", ptr(seeds), ptr(A), ptr(f), ptr(scale), N, V, stream())
+    return f, scale
+
+
+def dgcn_mask_temporal(seeds, block):
+    """(mask * scale (N, T), scale (1,)) of the temporal DropGraph: frames within block // 2 of a seed are dropped"""
+    N, T = seeds.shape
+    f = torch.empty_like(seeds)
+    scale = torch.empty(1, device=seeds.device, dtype=torch.float32)
+    call("hwgat_dgcn_mask_temporal", ptr(seeds), ptr(f), ptr(scale), N, T, int(block), stream())
+    return f, scale
+
+
+def dgcn_merge(c, bn, r, res_bn, fs1, ft1, fs2, ft2):
+    """relu(bn(c) fs1[n, v] ft1[n, t] + r' fs2[n, v] ft2[n, t]); bn / res_bn = (mean, rstd, gamma, beta), res_bn None: r' = r"""
+    N, T, V, C = c.shape
+    rb = res_bn or (None, None, None, None)
+    out = torch.empty_like(c)
+    call("hwgat_dgcn_merge", ptr(c), ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), ptr(r), ptr(rb[0]), ptr(rb[1]),
+         ptr(rb[2]), ptr(rb[3]), ptr(fs1), ptr(ft1), ptr(fs2), ptr(ft2), ptr(out), N, T, V, C, stream())
+    return out
+
+
+def dgcn_merge_backward(dout, out, fs1, ft1, fs2, ft2):
+    """(dz1, dz2): dout [out > 0] times the two mask products"""
+    N, T, V, C = dout.shape
+    dz1, dz2 = torch.empty_like(dout), torch.empty_like(dout)
+    call("hwgat_dgcn_merge_bwd", ptr(dout), ptr(out), ptr(fs1), ptr(ft1), ptr(fs2), ptr(ft2), ptr(dz1), ptr(dz2), N, T, V,
+         C, stream())
+    return dz1, dz2
+
+
+def dgcn_masked_sum(a, ma, b, mb):
+    """a [ma > 0] + b [mb > 0]; a mask that is None passes everything"""
+    out = torch.empty_like(a)
+    call("hwgat_dgcn_masked_sum", ptr(a), ptr(ma), ptr(b), ptr(mb), ptr(out), a.numel(), stream())
+    return out

@@ -252,3 +252,23 @@ class STGCNParams:
     def get_model_params(self):
         return (self.kp_dim, self.num_kps, self.center, self.edges_, self.edge_importance_weighting, self.n_out_features,
                 self.num_classes, self.dropout_ratio, self.batch_norm)
+
+
+class DecoupledGCNParams:
+    """the reference's DecoupledGCNParams (hwgat/models/model_params.py:540-588): same attributes, defaults, edge list
+    (the 29-joint upper-body graph of STGCNParams) and positional tuple"""
+
+    def __init__(self, dataset_params, input_dim, device=None) -> None:
+        self.kp_dim = input_dim
+        self.num_kps = 29
+        self.num_classes = dataset_params['num_class']
+        self.groups = 8
+        self.block_size = 41
+        self.n_out_features = 256
+        self.dropout_ratio = 0
+        self.batch_norm = False
+        self.edges_ = _stgcn_edges()
+
+    def get_model_params(self):
+        return (self.kp_dim, self.num_kps, self.edges_, self.groups, self.block_size, self.n_out_features,
+                self.num_classes, self.dropout_ratio, self.batch_norm)
