@@ -76,8 +76,8 @@ int hwgat_seed_advance(uint32_t* state, void* stream);
 /* the same state written from host integers (kernel arguments, no copy): state = { counter, base(counter), initial, salt }.
  * The eager path of a model calls it once per train-mode forward; after it, hwgat_seed_advance continues from `counter`. */
 int hwgat_seed_set(uint32_t* state, uint32_t counter, uint32_t initial, uint32_t salt, void* stream);
-/* 1 for the kernel-lab build (`python sl-hwgat_amd/build.py --lab`, libhwgat_hip_lab.so: environment A/B switches compiled
- * in), 0 for the product library (reads no environment variables).  The lab tools assert 1 on the library they load. */
+/* 1 for the kernel-lab build (`python sl-hwgat_amd/build.py --lab`, libhwgat_hip_lab.so: environment switches for launch
+ * parameters and instrumentation compiled in), 0 for the product library (reads no environment variables).  The lab tools assert 1 on the library they load. */
 int hwgat_is_lab_build(void);
 
 /* ---- debug: dump the lane->element maps of v_mfma_f32_32x32x2_f32 so the

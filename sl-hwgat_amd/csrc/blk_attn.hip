@@ -20,14 +20,19 @@
 // feeds dP and goes straight to registers); P^T and dS^T meet in one shared scratch tile.
 //
 // HBM traffic is the algorithmic 4*E*s (fwd) / 7*E*s (bwd) like the window kernel; the MFMA work per
-// byte is 2 x (64/58)^2 higher (64-slot tiles for 58 tokens), so at head_dim 64 the backward pass sits
-// at the fp32 MFMA / HBM ridge rather than clearly HBM-bound (HGATE section).
+// byte is 2 x (64/58)^2 higher (64-slot tiles for 58 tokens).
+//
+// This file serves head_dim 32 in both storage types.  head_dim 64 (every HGATE stage) goes to the 16x16-tile,
+// four-waves-per-unit kernels of blk_attn_f32.hip / blk_attn_bf16.hip, which replaced this form there
+// (profiles/r03_blk_attn_bf16_pmc.json); the entry points below dispatch.
 #include "attn_common.h"
 #include "blk_common.h"
 #include "fused_ops.h"            // the dropout hash (attention dropout, HGATE.py:78,106)
 
 namespace {
 using namespace blk;
+
+constexpr int HD = 32;                         // head_dim
 
 // masks + softmax on one lane's 2 x 16 logits of one query row.
 // s[kt][r] = S[q][key slot kt*32 + crow(r,hh)] on entry, p = final probabilities on exit.
@@ -80,7 +85,7 @@ __device__ __forceinline__ void blk_keep(float (&k)[2][16], const AttnDrop& ad, 
         }
 }
 
-template <typename T, int HD> struct BlkCfg {
+template <typename T> struct BlkCfg {
     using E = typename tile_of<T>::E;          // LDS tile element: fp32 tiles + fp32 MFMAs, or raw bf16 tiles + bf16 MFMAs (attn_common.h)
     static constexpr int LDW = HD + tile_of<T>::PAD;
     static constexpr int NT = HD / 32;
@@ -93,12 +98,12 @@ template <typename T, int HD> struct BlkCfg {
 
 // =============================================================== forward
 // Two wavefronts share a unit: wave w loads frame tile w of Q and K and owns query tile w.
-template <typename T, int HD, bool ADROP = false>
+template <typename T, bool ADROP>
 __global__ __launch_bounds__(128, 2) void blk_attn_fwd_k(const T* __restrict__ qkv, T* __restrict__ o,
                                                       const uint32_t* __restrict__ maskbits, BlkGeom g,
                                                       int n_units, AttnDrop ad) {
     if constexpr (ADROP) ad.seed += seed_base_of(ad.base);
-    using C = BlkCfg<T, HD>;
+    using C = BlkCfg<T>;
     constexpr int LDW = C::LDW, NT = C::NT, NLD = C::NLD, RPI = C::RPI, TILE = C::TILE;
     using E = typename C::E;
     constexpr bool QS = tile_of<T>::QSCALED;
@@ -190,13 +195,13 @@ __global__ __launch_bounds__(128, 2) void blk_attn_fwd_k(const T* __restrict__ q
 // transposed dS and P tiles meet in a shared scratch tile.  Phase B: wave w owns KEY tile w
 // (dK_w = sum_qt dS^T Q_qt, dV_w = sum_qt P^T dO_qt).  Q, K, dO live in LDS; V is only ever the
 // row-per-lane operand of dP, so it goes from HBM straight into registers.
-template <typename T, int HD, bool ADROP = false>
+template <typename T, bool ADROP>
 __global__ __launch_bounds__(128, sizeof(T) == 2 ? 2 : 1) void blk_attn_bwd_k(const T* __restrict__ qkv, const T* __restrict__ dO,
                                                       T* __restrict__ dqkv,
                                                       const uint32_t* __restrict__ maskbits, BlkGeom g,
                                                       int n_units, AttnDrop ad) {
     if constexpr (ADROP) ad.seed += seed_base_of(ad.base);
-    using C = BlkCfg<T, HD>;
+    using C = BlkCfg<T>;
     constexpr int LDW = C::LDW, NT = C::NT, NLD = C::NLD, RPI = C::RPI, TILE = C::TILE;
     using E = typename C::E;
     constexpr bool QS = tile_of<T>::QSCALED, B16 = sizeof(T) == 2;
@@ -410,21 +415,21 @@ bool bgeom_ok(int B, int F, int KJ, int nH, int hd) {
 
 constexpr int LDS_PER_CU = 160 * 1024;
 
-template <typename T, int HD>
+template <typename T>
 int launch_bfwd(const void* qkv, void* o, const uint32_t* mb, BlkGeom g, int n_units, AttnDrop ad, hipStream_t st) {
-    constexpr int per_cu = LDS_PER_CU / (6 * BlkCfg<T, HD>::TILE * (int)sizeof(typename BlkCfg<T, HD>::E));
+    constexpr int per_cu = LDS_PER_CU / (6 * BlkCfg<T>::TILE * (int)sizeof(typename BlkCfg<T>::E));
     const int blocks = min(n_units, 256 * (per_cu > 8 ? 8 : per_cu));
-    if (ad.p > 0.f) blk_attn_fwd_k<T, HD, true><<<blocks, 128, 0, st>>>((const T*)qkv, (T*)o, mb, g, n_units, ad);
-    else blk_attn_fwd_k<T, HD><<<blocks, 128, 0, st>>>((const T*)qkv, (T*)o, mb, g, n_units, ad);
+    if (ad.p > 0.f) blk_attn_fwd_k<T, true><<<blocks, 128, 0, st>>>((const T*)qkv, (T*)o, mb, g, n_units, ad);
+    else blk_attn_fwd_k<T, false><<<blocks, 128, 0, st>>>((const T*)qkv, (T*)o, mb, g, n_units, ad);
     HWGAT_LAUNCH_CHECK();
 }
-template <typename T, int HD>
+template <typename T>
 int launch_bbwd(const void* qkv, const void* dO, void* dqkv, const uint32_t* mb, BlkGeom g, int n_units, AttnDrop ad,
                 hipStream_t st) {
-    constexpr int per_cu = LDS_PER_CU / ((6 * BlkCfg<T, HD>::TILE + 64 * 66) * (int)sizeof(typename BlkCfg<T, HD>::E));
+    constexpr int per_cu = LDS_PER_CU / ((6 * BlkCfg<T>::TILE + 64 * 66) * (int)sizeof(typename BlkCfg<T>::E));
     const int blocks = min(n_units, 256 * (per_cu > 4 ? 4 : per_cu));
-    if (ad.p > 0.f) blk_attn_bwd_k<T, HD, true><<<blocks, 128, 0, st>>>((const T*)qkv, (const T*)dO, (T*)dqkv, mb, g, n_units, ad);
-    else blk_attn_bwd_k<T, HD><<<blocks, 128, 0, st>>>((const T*)qkv, (const T*)dO, (T*)dqkv, mb, g, n_units, ad);
+    if (ad.p > 0.f) blk_attn_bwd_k<T, true><<<blocks, 128, 0, st>>>((const T*)qkv, (const T*)dO, (T*)dqkv, mb, g, n_units, ad);
+    else blk_attn_bwd_k<T, false><<<blocks, 128, 0, st>>>((const T*)qkv, (const T*)dO, (T*)dqkv, mb, g, n_units, ad);
     HWGAT_LAUNCH_CHECK();
 }
 
@@ -440,24 +445,15 @@ extern "C" int hwgat_blk_attn_fwd_drop(const void* qkv, void* o, const uint32_t*
     const int64_t units = (int64_t)B * g.f * nH;
     if (units > 0x7fffffff) return HWGAT_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
-#define FWD(T)                                                                              \
-    switch (hd) {                                                                           \
-        case 32: return launch_bfwd<T, 32>(qkv, o, maskbits, g, (int)units, ad, st);        \
-        default: return launch_bfwd<T, 64>(qkv, o, maskbits, g, (int)units, ad, st);        \
-    }
+    // head_dim 64 (every HGATE stage): the 16x16-tile, four-waves-per-unit kernels of blk_attn_f32.hip / blk_attn_bf16.hip
     if (dtype == HWGAT_F32) {
-        // head_dim 64 (every HGATE stage): the 16x16-tile, four-waves-per-unit kernels of blk_attn_f32.hip / blk_attn_bf16.hip;
-        // the 32x32-tile form stays for head_dim 32 and as the lab A/B (HWGAT_BLK_F32=0, HWGAT_BLK_B16=0)
-        static const bool old_f32 = lab_env("HWGAT_BLK_F32") && lab_env("HWGAT_BLK_F32")[0] == '0';
-        if (hd == 64 && !old_f32) return hwgat_launch_blk_fwd_f32(qkv, o, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
-        FWD(float)
+        if (hd == 64) return hwgat_launch_blk_fwd_f32(qkv, o, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
+        return launch_bfwd<float>(qkv, o, maskbits, g, (int)units, ad, st);
     }
     if (dtype == HWGAT_BF16) {
-        static const bool old_b16 = lab_env("HWGAT_BLK_B16") && lab_env("HWGAT_BLK_B16")[0] == '0';     // see hwgat_blk_attn_bwd
-        if (hd == 64 && !old_b16) return hwgat_launch_blk_fwd_b16(qkv, o, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
-        FWD(bf16_t)
+        if (hd == 64) return hwgat_launch_blk_fwd_b16(qkv, o, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
+        return launch_bfwd<bf16_t>(qkv, o, maskbits, g, (int)units, ad, st);
     }
-#undef FWD
     return HWGAT_EDTYPE;
 }
 
@@ -476,24 +472,14 @@ extern "C" int hwgat_blk_attn_bwd_drop(const void* qkv, const void* dO, void* dq
     const int64_t units = (int64_t)B * g.f * nH;
     if (units > 0x7fffffff) return HWGAT_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
-#define BWD(T)                                                                                    \
-    switch (hd) {                                                                                 \
-        case 32: return launch_bbwd<T, 32>(qkv, dO, dqkv, maskbits, g, (int)units, ad, st);       \
-        default: return launch_bbwd<T, 64>(qkv, dO, dqkv, maskbits, g, (int)units, ad, st);       \
-    }
     if (dtype == HWGAT_F32) {
-        static const bool old_f32 = lab_env("HWGAT_BLK_F32") && lab_env("HWGAT_BLK_F32")[0] == '0';
-        if (hd == 64 && !old_f32) return hwgat_launch_blk_bwd_f32(qkv, dO, dqkv, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
-        BWD(float)
+        if (hd == 64) return hwgat_launch_blk_bwd_f32(qkv, dO, dqkv, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
+        return launch_bbwd<float>(qkv, dO, dqkv, maskbits, g, (int)units, ad, st);
     }
     if (dtype == HWGAT_BF16) {
-        // head_dim 64 (every HGATE stage): the 16x16-tile, four-waves-per-unit kernel of blk_attn_bf16.hip; the 32x32-tile
-        // form stays for head_dim 32 and as the lab A/B (HWGAT_BLK_B16=0)
-        static const bool old_b16 = lab_env("HWGAT_BLK_B16") && lab_env("HWGAT_BLK_B16")[0] == '0';
-        if (hd == 64 && !old_b16) return hwgat_launch_blk_bwd_b16(qkv, dO, dqkv, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
-        BWD(bf16_t)
+        if (hd == 64) return hwgat_launch_blk_bwd_b16(qkv, dO, dqkv, maskbits, B, F, KJ, nH, shifted, ad.seed, ad.p, ad.base, st);
+        return launch_bbwd<bf16_t>(qkv, dO, dqkv, maskbits, g, (int)units, ad, st);
     }
-#undef BWD
     return HWGAT_EDTYPE;
 }
 

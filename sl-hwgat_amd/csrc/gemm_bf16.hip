@@ -634,20 +634,16 @@ extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float
         }
     }
     // outputs whose width is a multiple of 256: the 256x256 one-wave-per-SIMD kernel (gemm_bf16_nt256.hip: half the
-    // L2 -> LDS stream of the 128x128 tile) over the 256-aligned rows; HWGAT_NT_KERNEL=old keeps the 128x128 kernel
-    static const bool nt_old = [] { const char* e = lab_env("HWGAT_NT_KERNEL"); return e && e[0] == 'o'; }();
-    static const int nt256_min_k = [] { const char* e = lab_env("HWGAT_NT256_MINK"); return e ? atoi(e) : 128; }();
+    // L2 -> LDS stream of the 128x128 tile) over the 256-aligned rows
     // (fewer than 128 such tiles: the 128 x 128 kernel spreads a serving-size launch over four times as many CUs)
-    if (!nt_old && !epi_is_relu(epi) && N % 256 == 0 && K >= nt256_min_k && M >= 256 &&
+    if (!epi_is_relu(epi) && N % 256 == 0 && K >= 128 && M >= 256 &&
         ((M / 256) * (N / 256) >= 128 || a.stat_sum != nullptr)) {     // (the row statistics of the 256-wide kernels are the order-fixed ones: eval determinism)
         const int64_t m256 = M / 256 * 256;
         NtArgsB b = a;
         b.M = m256;
-        // ... on the eight-wave LDS-DMA kernel (gemm_bf16_nt8w.hip) where it applies; HWGAT_NT8W=0 (lab builds) keeps
-        // the one-wave-per-SIMD kernel for A/B runs
-        static const bool no8w = [] { const char* e = lab_env("HWGAT_NT8W"); return e && e[0] == '0'; }();
-        const int rc = (!no8w && hwgat_nt8w_bf16_takes(b, pro, epi)) ? hwgat_launch_nt8w_bf16(b, pro, epi, st)
-                                                                      : hwgat_launch_nt256_bf16(b, pro, epi, st);
+        // ... on the eight-wave LDS-DMA kernel (gemm_bf16_nt8w.hip) where it applies, else the one-wave-per-SIMD kernel
+        const int rc = hwgat_nt8w_bf16_takes(b, pro, epi) ? hwgat_launch_nt8w_bf16(b, pro, epi, st)
+                                                          : hwgat_launch_nt256_bf16(b, pro, epi, st);
         if (rc || m256 == M) return rc;
         const NtArgsB t = nt_rows_b(a, m256, M - m256);   // 128 rows left: RAGGED instantiation (global row index in the dropout hash)
         switch (pro) {
@@ -728,21 +724,18 @@ static int tn_bf16_impl(const void* A, const void* B, float* dW, float* db, int6
         }
         HWGAT_LAUNCH_CHECK();
     }
-    // dW at least 256 x 256: the 128x128-wave-tile kernel (gemm_bf16_tn256.hip); HWGAT_TN_KERNEL=old keeps this file's
-    static const bool tn_old = [] { const char* e = lab_env("HWGAT_TN_KERNEL"); return e && e[0] == 'o'; }();
+    // dW at least 256 x 256: the 128x128-wave-tile kernel (gemm_bf16_tn256.hip)
     // ... where its tiles fill the 256 CUs in whole rounds of equal blocks (tile count a divisor of 256: 1, 2, 4, 8 ...);
     // 3 or 12 tiles (the qkv weight) need three rounds of short M slices and lose to the 128x128 kernel:
     // stage 2 dWqkv 492 vs 454 us, stage 1 349 vs 272 (same box, tools/tn_lab.py)
-    // plain operands, whole 256x256 tiles: the eight-wave LDS-DMA kernel (gemm_bf16_tn8w.hip); HWGAT_TN8W=0 (lab builds)
-    // keeps the kernels below for A/B runs
-    static const bool no8w = [] { const char* e = lab_env("HWGAT_TN8W"); return e && e[0] == '0'; }();
-    if (!no8w && hwgat_tn8w_bf16_takes(M, N, K, pro_p, mean)) {
+    // plain operands, whole 256x256 tiles: the eight-wave LDS-DMA kernel (gemm_bf16_tn8w.hip)
+    if (hwgat_tn8w_bf16_takes(M, N, K, pro_p, mean)) {
         TnArgsB a{(const bf16_t*)A, (const bf16_t*)B, dW, db, nullptr, nullptr, nullptr, nullptr, M, N, K, 1, M, pro_seed, pro_p, 0};
         a.det_dw = det.dw; a.det_db = det.db; a.det_cap = det.cap;
         return hwgat_launch_tn8w_bf16(a, (hipStream_t)stream);
     }
     const int t256 = (N / 256) * (K / 256);
-    if (!tn_old && N % 256 == 0 && K % 256 == 0 && M % 32 == 0 && 256 % t256 == 0 && !(pro_p > 0.f && mean)) {
+    if (N % 256 == 0 && K % 256 == 0 && M % 32 == 0 && 256 % t256 == 0 && !(pro_p > 0.f && mean)) {
         TnArgsB a{(const bf16_t*)A, (const bf16_t*)B, dW, db, mean, rstd, gamma, beta, M, N, K, 1, M, pro_seed, pro_p, 0};
         a.seed_base = seed_base;
         a.det_dw = det.dw; a.det_db = det.db; a.det_cap = det.cap;

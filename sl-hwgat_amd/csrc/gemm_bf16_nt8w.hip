@@ -53,7 +53,7 @@ __device__ __forceinline__ void wg_barrier() {          // raw: no implicit vmcn
 
 // STAT: 0 = plain epilogue, 1 = + row statistics, 2 = + row statistics and the merged store, 3 = folded LayerNorm.
 // DBG (lab builds only, wrong results by design): 1 = no epilogue stores, 2 = no DMA waits, 3 = no DMA at all,
-// 4 = no DMA and no fragment reads -- what each part of the schedule costs (tools/nt8w_lab.py).
+// 4 = no DMA and no fragment reads -- what each part of the schedule costs (tools/nt8w_dbg.py).
 template <int EPI, int STAT, int DBG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt8w_bf16_k(NtArgsB p) {
     HWGAT_RESOLVE_SEEDS2(p);

@@ -38,11 +38,7 @@ constexpr int BK_MIN = 16;                                      // K must be a m
 
 // Tiling configuration: WM x WN waves, each owning TM x TN MFMA tiles of 32x32.
 //   NtSmall  2x2 waves x (2x2) tiles = 128x128 block, 256 threads, 2 blocks / CU
-//   NtBig    4x2 waves x (2x4) tiles = 256x256 block, 512 threads, 1 block / CU (still 2 waves / SIMD):
-//            twice the MFMAs per barrier, half the global->LDS bytes per flop, 25 % fewer LDS
-//            fragment reads per MFMA.  Needs M % 256 == N % 256 == 0.
 using NtSmall = TileCfg<2, 2, 2, 2>;
-using NtBig = TileCfg<4, 2, 2, 4, 32, 1>;
 using NtK16 = TileCfg<2, 2, 2, 2, 16, 3>;                      // 41 KB LDS -> 3 blocks / CU
 //   NtN64    4x1 waves x (1x2) tiles = 128x64 block, 256 threads, 2 blocks / CU: outputs whose width is an odd multiple
 //            of 64 (N % 128 == 64: stage width 64 / 192 and its qkv, HWGATE embed_dim 64 / 192).  The same kernel body
@@ -331,31 +327,25 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_nt
 }
 
 // ------------------------------------------------------------------ dW / db
-// rows of M per LDS stage = C::BK (32, or 16 for the 3-blocks-per-CU configuration)
+// rows of M per LDS stage = C::BK
 
-// dW tile configurations (output tile BT x BT of dW, both operands [32][BT] per stage):
+// dW tile configuration (output tile BT x BT of dW, both operands [32][BT] per stage):
 //   TnSmall  2x2 waves x (2x2) tiles = 128x128, 256 threads, 2 blocks / CU
-//   TnBig    4x2 waves x (2x4) tiles = 256x256, 512 threads, 1 block / CU (N % 256 == K % 256 == 0)
+// (a 256x256 eight-wave tile, K slabs of 16 at three blocks per CU and a v_mfma_f32_16x16x4_f32 form were measured and
+// removed: the last ran +2..4 % at K <= 256 and -2 % at K = 512, profiles/r01f_gemm_tile_ab.txt)
 using TnSmall = TileCfg<2, 2, 2, 2>;
-using TnBig = TileCfg<4, 2, 2, 4, 32, 1>;
-using TnK16 = TileCfg<2, 2, 2, 2, 16, 3>;                      // 32 KB LDS -> 3 blocks / CU
 
-// MF16 selects v_mfma_f32_16x16x4_f32 (the form the vendor library uses: same flop rate, half the
-// accumulator-register traffic per flop) instead of v_mfma_f32_32x32x2_f32.  Measured on MI355X:
-// +2..4 % at K <= 256, -2 % at K = 512 -- not the source of the library's 0.91 vs our 0.82 MFMA
-// utilisation; kept behind HWGAT_GEMM_TILE=m for A/B runs.
 // RAGGED: launch over the last M % 32 rows (see gemm_nt_k): one partial stage, rows >= M count as zero.
-template <int PRO, bool BLN, typename C, bool MF16 = false, bool RAGGED = false>
+template <int PRO, bool BLN, typename C, bool RAGGED = false>
 __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_tn_k(TnArgs p) {
     HWGAT_RESOLVE_SEED1(p);
     constexpr int TM = C::BK;
     constexpr int BT = C::BM;                                  // == C::BN
-    constexpr int LDR = MF16 ? BT + 16 : BT;                   // LDS row stride: +16 keeps the 4 rows of a 16x16x4 operand on distinct banks
     constexpr int TNW = C::TMW, TKW = C::TNW;
     constexpr int TPR = BT / 4;                                // threads per staged row (16 B each)
     constexpr int RPP = C::THREADS / TPR;                      // rows per pass (8 in every config)
     constexpr int NP = TM / RPP;                               // passes per operand per stage
-    __shared__ __attribute__((aligned(16))) float sm[2 * 2 * TM * LDR];      // [buf][A|B][TM][LDR]
+    __shared__ __attribute__((aligned(16))) float sm[2 * 2 * TM * BT];      // [buf][A|B][TM][BT]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lq = lane & 31, hh = lane >> 5;
     const int wn = wave / C::WN, wk = wave % C::WN;
@@ -397,8 +387,8 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_tn
         }
     };
     auto commit = [&](int buf, int it) {
-        float* As = sm + buf * (2 * TM * LDR);
-        float* Bs = As + TM * LDR;
+        float* As = sm + buf * (2 * TM * BT);
+        float* Bs = As + TM * BT;
         const int64_t r0 = r_begin + (int64_t)it * TM + lrow;
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
@@ -408,47 +398,43 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_tn
             if constexpr (BLN) b = (b - bm[i]) * bs[i] * lg + lb;
             if constexpr (RAGGED) { if (r0 + RPP * i > m_last) a = f32x4{0.f, 0.f, 0.f, 0.f}; }
             colsum += a;
-            *reinterpret_cast<f32x4*>(As + (lrow + RPP * i) * LDR + lc4) = a;
-            *reinterpret_cast<f32x4*>(Bs + (lrow + RPP * i) * LDR + lc4) = b;
+            *reinterpret_cast<f32x4*>(As + (lrow + RPP * i) * BT + lc4) = a;
+            *reinterpret_cast<f32x4*>(Bs + (lrow + RPP * i) * BT + lc4) = b;
         }
     };
 
-    // accumulators: 32x32 tiles (f32x16) or 16x16 tiles (f32x4), 64 registers per lane either way
-    constexpr int TI = MF16 ? TNW * 2 : TNW, TJ = MF16 ? TKW * 2 : TKW, TS = MF16 ? 16 : 32;
-    typedef typename std::conditional<MF16, f32x4, f32x16>::type acc_t;
-    acc_t acc[TI][TJ];
+    constexpr int TI = TNW, TJ = TKW;
+    f32x16 acc[TI][TJ];                                        // 32x32 tiles, 64 registers per lane
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
         for (int jj = 0; jj < TJ; ++jj)
 #pragma unroll
-            for (int e = 0; e < (MF16 ? 4 : 16); ++e) acc[i][jj][e] = 0.f;
+            for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
 
     issue(0);
     commit(0, 0);
     __syncthreads();
     int buf = 0;
-    // operand lane maps: 32x32x2: lane (col = lane&31, k = lane>>5), 2 rows of m per step;
-    //                    16x16x4: lane (col = lane&15, k = lane>>4), 4 rows of m per step
-    const int lc = MF16 ? (lane & 15) : lq, lk = MF16 ? (lane >> 4) : hh;
-    constexpr int KPS = MF16 ? 4 : 2;                          // rows of m consumed per MFMA step
+    // operand lane map of 32x32x2: lane (col = lq, k = hh), 2 rows of m per step
+    constexpr int KPS = 2;                                     // rows of m consumed per MFMA step
     for (int it = 0; it < n_it; ++it) {
         const bool have_next = it + 1 < n_it;
         if (have_next) issue(it + 1);
-        const float* As = sm + buf * (2 * TM * LDR) + wn * (TNW * 32) + lc;
-        const float* Bs = sm + buf * (2 * TM * LDR) + TM * LDR + wk * (TKW * 32) + lc;
+        const float* As = sm + buf * (2 * TM * BT) + wn * (TNW * 32) + lq;
+        const float* Bs = sm + buf * (2 * TM * BT) + TM * BT + wk * (TKW * 32) + lq;
         // software-pipelined operand fetch: the LDS reads of chunk c+1 are in flight while the
         // MFMAs of chunk c issue (the compiler then waits with counted lgkmcnt, not 0)
-        constexpr int NSTEP = TM / KPS, CH = MF16 ? 2 : 4, NCH = NSTEP / CH;
+        constexpr int NSTEP = TM / KPS, CH = 4, NCH = NSTEP / CH;
         float fa[2][CH][TI], fb[2][CH][TJ];
         auto fetch = [&](int c, int slot) {
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
-                const int ro = (KPS * (c * CH + e) + lk) * LDR;
+                const int ro = (KPS * (c * CH + e) + hh) * BT;
 #pragma unroll
-                for (int i = 0; i < TI; ++i) fa[slot][e][i] = As[ro + TS * i];
+                for (int i = 0; i < TI; ++i) fa[slot][e][i] = As[ro + 32 * i];
 #pragma unroll
-                for (int jj = 0; jj < TJ; ++jj) fb[slot][e][jj] = Bs[ro + TS * jj];
+                for (int jj = 0; jj < TJ; ++jj) fb[slot][e][jj] = Bs[ro + 32 * jj];
             }
         };
         fetch(0, 0);
@@ -461,12 +447,8 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_tn
 #pragma unroll
                 for (int i = 0; i < TI; ++i)
 #pragma unroll
-                    for (int jj = 0; jj < TJ; ++jj) {
-                        if constexpr (MF16)
-                            acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[c & 1][e][i], fb[c & 1][e][jj], acc[i][jj], 0, 0, 0);
-                        else
-                            acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c & 1][e][i], fb[c & 1][e][jj], acc[i][jj], 0, 0, 0);
-                    }
+                    for (int jj = 0; jj < TJ; ++jj)
+                        acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c & 1][e][i], fb[c & 1][e][jj], acc[i][jj], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (have_next) commit(buf ^ 1, it + 1);
@@ -475,16 +457,15 @@ __global__ __launch_bounds__(C::THREADS, C::OCC * C::THREADS / 256) void gemm_tn
     }
     const bool det = p.det_dw != nullptr;                       // deterministic mode: see TnArgs
     float* dwo = det ? p.det_dw + (int64_t)split * p.N * p.K : p.dW;
-    // D[i = n][j = k]: 32x32: lane (k = lq, hh), reg r -> dW[n = crow(r,hh)][k]
-    //                  16x16: lane (k = lane&15, q = lane>>4), reg r -> dW[n = 4q + r][k]
+    // D[i = n][j = k]: lane (k = lq, hh), reg r -> dW[n = crow(r,hh)][k]
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
         for (int jj = 0; jj < TJ; ++jj)
 #pragma unroll
-            for (int r = 0; r < (MF16 ? 4 : 16); ++r) {
-                const int n = n0 + wn * (TNW * 32) + i * TS + (MF16 ? 4 * lk + r : crow(r, hh));
-                const int k = k0 + wk * (TKW * 32) + jj * TS + lc;
+            for (int r = 0; r < 16; ++r) {
+                const int n = n0 + wn * (TNW * 32) + i * 32 + crow(r, hh);
+                const int k = k0 + wk * (TKW * 32) + jj * 32 + lq;
                 HWGAT_TN_ACC(det, dwo, (int64_t)n * p.K + k, acc[i][jj][r]);
             }
     if (p.db != nullptr && k0 == 0) {                           // one k-tile column owns the bias gradient
@@ -574,15 +555,6 @@ TnArgs tn_rows(TnArgs a, int64_t r0, int64_t rows) {
     return a;
 }
 
-// tile choice; HWGAT_GEMM_TILE=small|big overrides (A/B measurements only)
-int tile_override() {
-    static const int v = [] {
-        const char* e = lab_env("HWGAT_GEMM_TILE");
-        return !e ? 0 : (e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : (e[0] == 'k' ? 3 : (e[0] == 'm' ? 6 : (e[0] == 't' ? 7 : 0)))));
-    }();
-    return v;
-}
-
 // N % 128 == 64: the 128x64 tile over the whole 128-row blocks, then a RAGGED launch for the last M % 128 rows
 // (row statistics / merged store are not built for this tile: the caller takes the separate statistics pass)
 int launch_nt_n64(const NtArgs& a, int pro, int epi, hipStream_t st) {
@@ -609,7 +581,7 @@ int launch_nt_n64(const NtArgs& a, int pro, int epi, hipStream_t st) {
     }
 }
 
-template <int PRO, bool BLN, typename C, bool MF16 = false, bool RAGGED = false>
+template <int PRO, bool BLN, typename C, bool RAGGED = false>
 int launch_tn(TnArgs a, hipStream_t st) {
     constexpr int TM = C::BK;
     const int n_tiles = (a.N / C::BM) * (a.K / C::BM);
@@ -633,7 +605,7 @@ int launch_tn(TnArgs a, hipStream_t st) {
     a.rows_per_split = rows;
     if (a.det_dw && a.n_split > a.det_cap) return HWGAT_ESHAPE;
     const int grid = ((a.n_split + 7) / 8) * 8 * n_tiles;
-    gemm_tn_k<PRO, BLN, C, MF16, RAGGED><<<grid, C::THREADS, 0, st>>>(a);
+    gemm_tn_k<PRO, BLN, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a);
     HWGAT_LAUNCH_CHECK();
 }
 
@@ -689,8 +661,8 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
         }
     }
     // Tile choice, measured on MI355X (profiles/r01f_gemm_tile_ab.txt):
-    //  - the 8-wave 256x256 tile loses to two independent 128x128 blocks per CU (110 vs 129 TF at
-    //    K=512): kept only behind HWGAT_GEMM_TILE=big for A/B runs;
+    //  - an 8-wave 256x256 tile lost to two independent 128x128 blocks per CU (110 vs 129 TF at
+    //    K=512) and was removed;
     //  - four resident blocks (K16, 128 VGPRs) are 2-3 % slower than two; K slabs of 16 with THREE
     //    resident blocks per CU are ~1 % slower for plain epilogues but
     //    7-15 % faster when the epilogue is heavy (dropout+residual, GELU, GELU backward): the third
@@ -700,13 +672,10 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
     // 256-aligned rows.  Same box, TFLOP/s, 128x128 kernels -> this one (tools/nt_lab.py, profiles/r02b_nt_lab_*.txt):
     // stage 2 plain dX 131.7 -> 143.2 and 130.4 -> 141.1, LN-prologue qkv 120.6 -> 132.1, fc1 107.8 -> 121.0, fc2 125.9 ->
     // 136.0, GELU-backward 102.7 -> 114.7, dropout-prologue dX 111.1 -> 124.3, projection 119.1 -> 126.4; stage 1 (K = 256
-    // ... 768) +1 ... +10 %; stage 0 (N = 256, K = 128) +3 ... +5 %.  HWGAT_NT_KERNEL=old keeps everything on the 128x128
-    // kernels, HWGAT_NT256_MINK moves the K threshold (A/B runs).
-    static const bool nt_old = [] { const char* e = lab_env("HWGAT_NT_KERNEL"); return e && e[0] == 'o'; }();
-    static const int nt256_min_k = [] { const char* e = lab_env("HWGAT_NT256_MINK"); return e ? atoi(e) : 128; }();
+    // ... 768) +1 ... +10 %; stage 0 (N = 256, K = 128) +3 ... +5 %.
     // (serving batches: fewer than 128 tiles of 256 x 256 leave most of the 256 CUs without a tile -- the 128 x 128 kernel
     //  has four times as many; B = 1 eval forward 3.96 -> see profiles/r03_serve_lab.txt)
-    if (!nt_old && !epi_is_relu(epi) && tile_override() == 0 && N % 256 == 0 && K >= nt256_min_k && M >= 256 &&
+    if (!epi_is_relu(epi) && N % 256 == 0 && K >= 128 && M >= 256 &&
         ((M / 256) * (N / 256) >= 128 || a.stat_sum != nullptr)) {     // (the row statistics of the 256-wide kernels are the order-fixed ones: eval determinism)
         const int64_t m256 = M / 256 * 256;
         NtArgs b = a;
@@ -727,17 +696,13 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
     }
     const bool heavy = epi == EPI_BIAS_DROP_RES || epi == EPI_BIAS_GELU_DROP || epi == EPI_GELU_BWD || epi == EPI_BIAS_GELU_DROP_G || epi == EPI_MUL_AUX ||
                        epi_is_relu(epi);
-    const bool big = tile_override() == 2 && (M % 256 == 0) && (N % 256 == 0);
-    const bool k16 = tile_override() == 3 || (tile_override() == 0 && heavy);
-#define NT_GO(P) return big ? launch_nt<P, NtBig>(a, epi, st) : (k16 ? launch_nt<P, NtK16>(a, epi, st) : launch_nt<P, NtSmall>(a, epi, st))
-    switch (pro) {
-        case PRO_NONE: NT_GO(PRO_NONE);
-        case PRO_LN_FOLD: return k16 ? launch_nt<PRO_NONE, NtK16>(a, epi, st, true) : launch_nt<PRO_NONE, NtSmall>(a, epi, st, true);
-        case PRO_LN: NT_GO(PRO_LN);
-        case PRO_DROP: NT_GO(PRO_DROP);
+    switch (pro) {                                               // heavy epilogues: K slabs of 16, three blocks per CU
+        case PRO_NONE: return heavy ? launch_nt<PRO_NONE, NtK16>(a, epi, st) : launch_nt<PRO_NONE, NtSmall>(a, epi, st);
+        case PRO_LN_FOLD: return heavy ? launch_nt<PRO_NONE, NtK16>(a, epi, st, true) : launch_nt<PRO_NONE, NtSmall>(a, epi, st, true);
+        case PRO_LN: return heavy ? launch_nt<PRO_LN, NtK16>(a, epi, st) : launch_nt<PRO_LN, NtSmall>(a, epi, st);
+        case PRO_DROP: return heavy ? launch_nt<PRO_DROP, NtK16>(a, epi, st) : launch_nt<PRO_DROP, NtSmall>(a, epi, st);
         default: return HWGAT_EINVAL;
     }
-#undef NT_GO
 }
 
 extern "C" int hwgat_linear_nt_f32(const float* A, const float* W, const float* bias, float* C, int64_t M,
@@ -750,8 +715,7 @@ extern "C" int hwgat_linear_nt_f32(const float* A, const float* W, const float* 
 }
 
 static bool tn256_takes(int64_t M, int N, int K, float pro_p, const float* mean) {
-    const int ov = tile_override();
-    return M % 32 == 0 && (ov == 0 || ov == 7) && N % 256 == 0 && K % 256 == 0 && (int64_t)N * K > 256 * 256 && !(pro_p > 0.f && mean);
+    return M % 32 == 0 && N % 256 == 0 && K % 256 == 0 && (int64_t)N * K > 256 * 256 && !(pro_p > 0.f && mean);
 }
 
 extern "C" int64_t hwgat_linear_tn_f32_ws_bytes(int64_t M, int N, int K) {
@@ -798,24 +762,16 @@ static int tn_f32_impl(const float* A, const float* B, float* dW, float* db, int
             if (rc) return rc;
         }
         const TnArgs t = tn_rows(a, m_bulk, M - m_bulk);
-        if (pro_p > 0.f) return mean ? launch_tn<PRO_DROP, true, TnSmall, false, true>(t, st) : launch_tn<PRO_DROP, false, TnSmall, false, true>(t, st);
-        return mean ? launch_tn<PRO_NONE, true, TnSmall, false, true>(t, st) : launch_tn<PRO_NONE, false, TnSmall, false, true>(t, st);
+        if (pro_p > 0.f) return mean ? launch_tn<PRO_DROP, true, TnSmall, true>(t, st) : launch_tn<PRO_DROP, false, TnSmall, true>(t, st);
+        return mean ? launch_tn<PRO_NONE, true, TnSmall, true>(t, st) : launch_tn<PRO_NONE, false, TnSmall, true>(t, st);
     }
     // 256-aligned multi-tile outputs: the one-wave-per-SIMD 256x256 kernel with pinned MFMA/memory
     // interleave (gemm_f32_tn256.hip; +2..8 % over the variants below, e.g. 131 vs 121-126 TF on
     // 1536x512).  Single 256x256 outputs and everything else: 128x128 blocks, two per CU.
-    // HWGAT_GEMM_TILE = small | big | k16 | m(fma16) select the alternatives for A/B runs.
-    const int ov = tile_override();
-    if ((ov == 0 || ov == 7) && N % 256 == 0 && K % 256 == 0 && (int64_t)N * K > 256 * 256 && !(pro_p > 0.f && mean))
+    if (N % 256 == 0 && K % 256 == 0 && (int64_t)N * K > 256 * 256 && !(pro_p > 0.f && mean))
         return hwgat_launch_tn256(a, st);
-    const bool big = ov == 2 && (N % 256 == 0) && (K % 256 == 0);
-    const bool k16 = ov == 3;
-    const bool mf16 = ov == 6;
-#define TN_GO(P, L) return mf16 ? launch_tn<P, L, TnSmall, true>(a, st) : (big ? launch_tn<P, L, TnBig>(a, st) : (k16 ? launch_tn<P, L, TnK16>(a, st) : launch_tn<P, L, TnSmall>(a, st)))
-    if (pro_p > 0.f) { if (mean) TN_GO(PRO_DROP, true); else TN_GO(PRO_DROP, false); }
-    if (mean) TN_GO(PRO_NONE, true);
-    TN_GO(PRO_NONE, false);
-#undef TN_GO
+    if (pro_p > 0.f) return mean ? launch_tn<PRO_DROP, true, TnSmall>(a, st) : launch_tn<PRO_DROP, false, TnSmall>(a, st);
+    return mean ? launch_tn<PRO_NONE, true, TnSmall>(a, st) : launch_tn<PRO_NONE, false, TnSmall>(a, st);
 }
 
 extern "C" int hwgat_linear_tn_f32(const float* A, const float* B, float* dW, float* db, int64_t M, int N,

@@ -23,7 +23,6 @@
 // HBM traffic is exactly the algorithmic 4*E*s (fwd) / 7*E*s (bwd): every q,k,v
 // (and dO) element is read once, every o (dq,dk,dv) element written once; all
 // rows are 128-byte-line aligned segments of hd*s bytes.
-#include <stdlib.h>
 #include <type_traits>
 #include "attn_common.h"
 #include "fused_ops.h"            // the dropout hash (attention dropout)
@@ -237,19 +236,22 @@ __global__ __launch_bounds__(256, 2) void win_attn_fwd_k(const T* __restrict__ q
     }
 }
 
-// =============================================================== backward
+// =============================================================== backward, head_dim 32 and 64: one wave per unit
 
+// four waves per workgroup: 4 x 34 KiB of LDS per CU at head_dim 64
 // (bf16 tiles: 18 KiB of LDS per wave instead of 34, so two 4-wave workgroups share a CU)
-template <typename T, int HD, bool TRAIN, int WAVES, bool ADROP = false>
-__global__ __launch_bounds__(WAVES * 64, (sizeof(T) == 2 && HD <= 64) ? 2 : 1) void win_attn_bwd_k(const T* __restrict__ qkv,
+template <typename T, int HD, bool TRAIN, bool ADROP = false>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void win_attn_bwd_k(const T* __restrict__ qkv,
                                                                 const T* __restrict__ dO,
                                                                 T* __restrict__ dqkv,
                                                                 const uint32_t* __restrict__ maskbits,
                                                                 const float* __restrict__ thr_p,
                                                                 WinGeom g, int n_units, AttnDrop ad) {
     if constexpr (ADROP) ad.seed += seed_base_of(ad.base);
+    static_assert(HD <= 64, "head_dim 128 takes win_attn_bwd_split_k");
     using TL = tile_of<T>;                                   // see win_attn_fwd_k
     using E = typename TL::E;
+    constexpr int WAVES = 4;
     constexpr int LDW = HD + TL::PAD;
     constexpr int NT = HD / 32;
     constexpr int EPV = io<T>::EPV;
@@ -637,20 +639,16 @@ int launch_bwd(const void* qkv, const void* dO, void* dqkv, const uint32_t* mb, 
                WinGeom g, int n_units, AttnDrop ad, hipStream_t st) {
 #define BWD_ARGS (const T*)qkv, (const T*)dO, (T*)dqkv, mb, thr, g, n_units, ad
     if constexpr (HD == 128) {                               // two waves per unit, four waves per CU (see win_attn_bwd_split_k)
-        static const bool whole = [] { const char* e = lab_env("HWGAT_ATTN_SPLIT"); return e && e[0] == '0'; }();
-        if (!whole) {
-            const int blocks = min(n_units, 256 * (sizeof(T) == 2 ? 3 : 2));   // bf16 tiles: 44 KiB per workgroup
-            if (thr && ad.p > 0.f) win_attn_bwd_split_k<T, true, true><<<blocks, 128, 0, st>>>(BWD_ARGS);
-            else if (thr) win_attn_bwd_split_k<T, true><<<blocks, 128, 0, st>>>(BWD_ARGS);
-            else win_attn_bwd_split_k<T, false><<<blocks, 128, 0, st>>>(BWD_ARGS);
-            HWGAT_LAUNCH_CHECK();
-        }
+        const int blocks = min(n_units, 256 * (sizeof(T) == 2 ? 3 : 2));       // bf16 tiles: 44 KiB per workgroup
+        if (thr && ad.p > 0.f) win_attn_bwd_split_k<T, true, true><<<blocks, 128, 0, st>>>(BWD_ARGS);
+        else if (thr) win_attn_bwd_split_k<T, true><<<blocks, 128, 0, st>>>(BWD_ARGS);
+        else win_attn_bwd_split_k<T, false><<<blocks, 128, 0, st>>>(BWD_ARGS);
+    } else {
+        const int blocks = min((n_units + 3) / 4, sizeof(T) == 2 ? 512 : 256);
+        if (thr && ad.p > 0.f) win_attn_bwd_k<T, HD, true, true><<<blocks, 256, 0, st>>>(BWD_ARGS);
+        else if (thr) win_attn_bwd_k<T, HD, true><<<blocks, 256, 0, st>>>(BWD_ARGS);
+        else win_attn_bwd_k<T, HD, false><<<blocks, 256, 0, st>>>(BWD_ARGS);
     }
-    constexpr int WAVES = HD <= 64 ? 4 : 2;                  // 4 x 34 KiB or 2 x 66 KiB of LDS per CU
-    const int blocks = min((n_units + WAVES - 1) / WAVES, (sizeof(T) == 2 && HD <= 64) ? 512 : 256);
-    if (thr && ad.p > 0.f) win_attn_bwd_k<T, HD, true, WAVES, true><<<blocks, WAVES * 64, 0, st>>>(BWD_ARGS);
-    else if (thr) win_attn_bwd_k<T, HD, true, WAVES><<<blocks, WAVES * 64, 0, st>>>(BWD_ARGS);
-    else win_attn_bwd_k<T, HD, false, WAVES><<<blocks, WAVES * 64, 0, st>>>(BWD_ARGS);
 #undef BWD_ARGS
     HWGAT_LAUNCH_CHECK();
 }

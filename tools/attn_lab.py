@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Window-attention kernel rates at a given shape (default: one micro-batch of BASELINE config 5, head_dim 128):
 algorithmic bytes (4 E s forward, 7 E s backward) / time against the 8 TB/s HBM roof.
-    python tools/attn_lab.py [B F nW nH hd]          HWGAT_ATTN_SPLIT=0 selects the one-wave hd=128 backward"""
+    python tools/attn_lab.py [B F nW nH hd]
+(the one-wave head_dim 128 backward that win_attn_bwd_split_k replaced is recorded in profiles/r02c_attn_lab.txt)"""
 import importlib, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

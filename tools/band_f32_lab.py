@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
 """WGATE fp32 band attention through the LAB library: frames per staged group (HWGAT_BAND_PF), frame segments per clip
-(HWGAT_BAND_FSEG / HWGAT_BAND_BSEG), and the one-wave-per-head kernels of band_attn.hip (HWGAT_BAND_F32=0) for reference."""
-import ctypes, importlib, os, subprocess, sys
+(HWGAT_BAND_FSEG / HWGAT_BAND_BSEG).  (The one-wave-per-head kernels these replaced at head_dim 16 are recorded in
+profiles/r04n_band_f32_lab.txt.)"""
+import ctypes, importlib, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if len(sys.argv) > 1 and sys.argv[1] == "old":                   # (the switch is read once per process)
-    os.environ["HWGAT_BAND_F32"] = "0"
 hw = importlib.import_module("sl-hwgat_amd")
 HF, L = hw.functional, hw._lib
 from oracle import wgat_oracle as OW
@@ -41,10 +40,6 @@ def timed(fn, n=100):
 
 fwd = lambda: HF.attn_fwd("band", qkv, o, rows, None, nH, False)
 bwd = lambda: HF.attn_bwd("band", qkv, do, dq, rows, None, nH, False)
-if os.environ.get("HWGAT_BAND_F32") == "0":
-    tf, tb = timed(fwd), timed(bwd)
-    print(f"one wave per head (band_attn.hip): fwd {tf:7.1f} us {4 * E / tf / 1e6:5.2f} TB/s | bwd {tb:7.1f} us {7 * E / tb / 1e6:5.2f} TB/s")
-    sys.exit(0)
 for nhw, pf, seg in ((4, 2, 1), (4, 1, 1), (8, 1, 1), (8, 2, 1), (8, 1, 2), (4, 2, 1), (4, 1, 1), (8, 1, 1), (8, 2, 1), (8, 1, 2)):
     os.environ["HWGAT_BAND_NHW"] = str(nhw)                      # (forward only: the backward pass keeps 4 heads per workgroup)
     os.environ["HWGAT_BAND_PF"] = str(pf)
@@ -53,4 +48,3 @@ for nhw, pf, seg in ((4, 2, 1), (4, 1, 1), (8, 1, 1), (8, 2, 1), (8, 1, 2), (4, 
     os.environ["HWGAT_BAND_PF"] = str(min(pf, 2))
     tb = timed(bwd)
     print(f"heads per workgroup {nhw} frames per group {pf} segments {seg}: fwd {tf:7.1f} us {4 * E / tf / 1e6:5.2f} TB/s | bwd (4 heads) {tb:7.1f} us {7 * E / tb / 1e6:5.2f} TB/s", flush=True)
-subprocess.run([sys.executable, os.path.abspath(__file__), "old"], check=False)

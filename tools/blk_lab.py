@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HGATE fp32 block attention through the LAB library: start skew of the workgroups that share a CU (HWGAT_BLK_SKEW, in units
-of 64 cycles per resident index), old 32x32-tile kernels (HWGAT_BLK_F32=0) for reference."""
+of 64 cycles per resident index) x forward workgroups per CU (HWGAT_BLK_OCC)."""
 import ctypes, importlib, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

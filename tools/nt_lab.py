@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch rates of the fp32 NT linear kernels on the HWGAT shapes (B=64 config 2), every prologue / epilogue the
-fused block uses.  Run once per kernel choice, e.g.
-    HWGAT_NT256_MINK=100000 python tools/nt_lab.py     # 128x128 kernels only (round-1 path)
-    python tools/nt_lab.py                             # default dispatch (256x256 one-wave-per-SIMD kernel where eligible)
+fused block uses, through the shipped dispatch (256x256 one-wave-per-SIMD kernel where eligible; the A/B against the
+128x128-only dispatch is recorded at hwgat_linear_nt_f32_ex in csrc/gemm_f32.hip).
 Prints TFLOP/s per (stage, linear, variant) and the per-step total of the 32 NT launches."""
 import importlib, os, sys
 import torch
