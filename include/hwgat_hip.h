@@ -60,7 +60,9 @@ extern "C" {
  *         hwgat_stgcn_agg_{fwd,bwd}(_bytes), hwgat_stgcn_pool_{fwd,bwd}, hwgat_stgcn_copy_cols
  *   4006  the DecoupledGCN baseline (additions only): hwgat_dgcn_agg_{fwd,bwd}(_bytes), hwgat_dgcn_gate_{sum,apply,bwd},
  *         hwgat_dgcn_abs_sum, hwgat_dgcn_draw, hwgat_dgcn_mask_{spatial,temporal}, hwgat_dgcn_merge(_bwd),
- *         hwgat_dgcn_masked_sum */
+ *         hwgat_dgcn_masked_sum
+ *         later additions under the same number (additions only, no existing signature changed): hwgat_sce_{fwd,bwd}, the
+ *         fused smoothed cross-entropy; hwgat_eval_accumulate, hwgat_eval_acc_bytes, the device-side evaluation accumulators */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -672,6 +674,44 @@ int hwgat_dgcn_merge_bwd(const float* dout, const float* out, const float* fs1, 
                          const float* ft2, float* dz1, float* dz2, int N, int T, int V, int C, void* stream);
 int hwgat_dgcn_masked_sum(const float* a, const float* ma, const float* b, const float* mb, float* out, int64_t n,
                           void* stream);
+
+/* ---- smoothed cross-entropy on the logits and device-side evaluation (csrc/loss_eval.hip; reference:
+ * hwgat/losses/SmoothCrossEntropy.py, hwgat/utils.py:118-161 evaluate / predictions_plus_true, :324-350 gen_cm_w).
+ * logits fp32 (B, C) row-major, target int64 (B); B >= 1 (at most 2^31 - 1) and 1 <= C <= 65536, else HWGAT_ESHAPE.
+ * `n_valid` is a DEVICE int32 read when the kernels run (clamped to [0, B]); NULL means all B rows.  Rows at or beyond
+ * it are neither read nor written by the forward and the accumulator, and get zeros in the backward.  A target outside
+ * [0, C) is never used as an index.  No float atomic: every output is bit-reproducible.
+ *
+ * hwgat_sce_fwd, per row b with t = target[b] (two launches: the rows, then the mean):
+ *   lse[b]      = log sum_j exp(z[b, j]), max-subtracted
+ *   row_loss[b] = (1 - eps) (lse - z[b, t]) + eps (lse - mean_j z[b, j]); eps = 0 is plain cross-entropy
+ *   rank[b]     = #{j : z[b, j] > z[b, t]} + #{j < t : z[b, j] == z[b, t]}, the target's place in a stable descending sort
+ *   pred[b]     = the lowest index that holds the row maximum
+ *   loss[0]     = mean of row_loss over the first n_valid rows, summed in a fixed order (n_valid = 0: NaN)
+ *   A bad target gives row_loss = NaN (and so the mean) and rank = C; a row with a NaN (or +inf) logit gives lse =
+ *   row_loss = NaN, rank = C and pred some index in [0, C).
+ * hwgat_sce_bwd: dlogits[b, j] = g[0] / n_valid * (exp(z[b, j] - lse[b]) - (1 - eps) [j == t] - eps / C), g a DEVICE
+ *   float (the upstream gradient of the scalar loss); a row with a bad target is NaN throughout.
+ *
+ * hwgat_eval_accumulate (one workgroup) folds the outputs of one hwgat_sce_fwd into the accumulator block `acc`, which
+ * the caller zeroes to reset.  Layout of the block, hwgat_eval_acc_bytes(C, k_max, cap) bytes, offsets in bytes:
+ *      0  int64   n_samples                      rows seen (bad targets included)
+ *      8  int64   n_batches                      calls with n_valid > 0
+ *     16  int64   n_invalid                      rows with a target outside [0, C): counted here and nowhere below
+ *     24  double  loss_sum_samples               sum of row_loss
+ *     32  double  loss_sum_batches               sum of the batch means loss[0]
+ *     40  int64   rank_hist[k_max + 1]           rank_hist[min(rank, k_max)] += 1: top-k hits = sum of the first k entries
+ *     ..  int64   confusion[C][C]                confusion[target][pred] += 1
+ *     ..  int32   pred_log[cap], target_log[cap] row i of the run at index i while i < cap (cap may be 0); once the log
+ *                                                is full, further rows are counted above but not logged */
+int hwgat_sce_fwd(const float* logits, const int64_t* target, const int32_t* n_valid, float* lse, float* row_loss,
+                  int32_t* rank, int32_t* pred, float* loss, int64_t B, int C, float eps, void* stream);
+int hwgat_sce_bwd(const float* logits, const int64_t* target, const int32_t* n_valid, const float* lse, const float* g,
+                  float* dlogits, int64_t B, int C, float eps, void* stream);
+int64_t hwgat_eval_acc_bytes(int C, int k_max, int64_t cap);
+int hwgat_eval_accumulate(void* acc, const float* row_loss, const int32_t* rank, const int32_t* pred,
+                          const int64_t* target, const float* loss, const int32_t* n_valid, int64_t B, int C, int k_max,
+                          int64_t cap, void* stream);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,10 @@ _SIGS = {
     "hwgat_dgcn_merge": [_P] * 15 + [_I, _I, _I, _I, _P],
     "hwgat_dgcn_merge_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hwgat_dgcn_masked_sum": [_P, _P, _P, _P, _P, _L, _P],
+    "hwgat_sce_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
+    "hwgat_sce_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
+    "hwgat_eval_acc_bytes": [_I, _I, _L],
+    "hwgat_eval_accumulate": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _L, _P],
 }
 _lib = None
 

@@ -1,0 +1,295 @@
+// Smoothed cross-entropy on the classifier's logits and the device-side evaluation accumulators (reference:
+// hwgat/losses/SmoothCrossEntropy.py, hwgat/utils.py:118-161 evaluate / predictions_plus_true, :324-350 gen_cm_w).
+//
+//   hwgat_sce_fwd          sce_fwd_k: one workgroup per row -- max / arg-max / sum z, then sum exp / rank count; the row is
+//                          staged in LDS when it fits (C <= SCE_LDS_FLOATS), else read twice; 16-byte loads when
+//                          C % 4 == 0.  sce_mean_k (one workgroup) then takes the mean of the row losses in a fixed order.
+//   hwgat_sce_bwd          sce_bwd_k: one pass over the logits with the stored lse.
+//   hwgat_eval_accumulate  eval_acc_k: one workgroup folds a batch into the accumulator block (layout: hwgat_hip.h).
+//
+// No float or double atomic anywhere: every floating-point sum is a per-thread strided sum followed by a fixed butterfly
+// and a fixed combination of the four waves, so every output is bit-reproducible.  The integer counters of the
+// accumulator use integer atomicAdd (order does not change an integer sum).
+// A target outside [0, C) is never used as an index: it is replaced by 0 for addressing and the row is marked bad.
+#include "common.h"
+#include <limits.h>
+#include <math.h>
+
+namespace {
+
+constexpr int SCE_THREADS = 256;
+constexpr int SCE_LDS_FLOATS = 8192;           // rows of up to 32 KB are staged in LDS
+constexpr int SCE_MAX_C = 65536;
+
+template <typename T>
+__device__ __forceinline__ T wave_all_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// sum over the workgroup's 256 threads in a fixed order; `red` holds 4 values and may be reused right after the call
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
+    v = wave_all_sum(v);
+    __syncthreads();
+    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// rows that take part: *n_valid clamped to [0, B], all B when the pointer is NULL
+__device__ __forceinline__ int64_t valid_rows(const int32_t* n_valid, int64_t B) {
+    if (!n_valid) return B;
+    const int64_t n = *n_valid;
+    return n < 0 ? 0 : (n > B ? B : n);
+}
+
+__device__ __forceinline__ void take_max(float v, int j, float& m, int& mi) {
+    if (v > m) { m = v; mi = j; }                // strict: the lowest index of equal values stays; a NaN never enters
+}
+
+template <bool STAGED, bool VEC>
+__global__ __launch_bounds__(SCE_THREADS) void sce_fwd_k(const float* __restrict__ z, const int64_t* __restrict__ target,
+                                                        const int32_t* __restrict__ n_valid, float* __restrict__ lse,
+                                                        float* __restrict__ row_loss, int32_t* __restrict__ rank,
+                                                        int32_t* __restrict__ pred, int64_t B, int C, float eps) {
+    __shared__ __attribute__((aligned(16))) float row_s[STAGED ? SCE_LDS_FLOATS : 4];
+    __shared__ float red_f[4];
+    __shared__ int red_i[4];
+    __shared__ float red_m[4];
+    const int64_t b = blockIdx.x;
+    if (b >= valid_rows(n_valid, B)) return;     // uniform over the workgroup
+    const int tid = threadIdx.x;
+    const float* zr = z + b * C;
+    const int64_t t64 = target[b];
+    const bool t_ok = t64 >= 0 && t64 < C;
+    const int t = t_ok ? (int)t64 : 0;
+
+    // pass 1: max, lowest arg-max, sum of the logits; stage the row
+    float m = -INFINITY, sz = 0.f;
+    int mi = INT_MAX;
+    if (VEC) {
+        const f32x4* zr4 = reinterpret_cast<const f32x4*>(zr);
+        for (int q = tid; q < C / 4; q += SCE_THREADS) {
+            const f32x4 v = zr4[q];
+            if (STAGED) reinterpret_cast<f32x4*>(row_s)[q] = v;
+            take_max(v.x, 4 * q, m, mi);
+            take_max(v.y, 4 * q + 1, m, mi);
+            take_max(v.z, 4 * q + 2, m, mi);
+            take_max(v.w, 4 * q + 3, m, mi);
+            sz += (v.x + v.y) + (v.z + v.w);
+        }
+    } else {
+        for (int j = tid; j < C; j += SCE_THREADS) {
+            const float v = zr[j];
+            if (STAGED) row_s[j] = v;
+            take_max(v, j, m, mi);
+            sz += v;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        const int oi = __shfl_xor(mi, o, 64);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    if (lane_id() == 0) { red_m[tid >> 6] = m; red_i[tid >> 6] = mi; }
+    __syncthreads();                             // also publishes the staged row
+    m = red_m[0];
+    mi = red_i[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const float om = red_m[w];
+        const int oi = red_i[w];
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    const float* row = STAGED ? row_s : zr;
+    const float zt = t_ok ? row[t] : NAN;
+
+    // pass 2: sum exp(z - max) and the target's position in a stable descending sort
+    float s = 0.f;
+    int cnt = 0;
+    if (VEC) {
+        const f32x4* r4 = reinterpret_cast<const f32x4*>(row);
+        for (int q = tid; q < C / 4; q += SCE_THREADS) {
+            const f32x4 v = r4[q];
+            const int j = 4 * q;
+            s += (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m));
+            cnt += (v.x > zt || (v.x == zt && j < t)) + (v.y > zt || (v.y == zt && j + 1 < t)) +
+                   (v.z > zt || (v.z == zt && j + 2 < t)) + (v.w > zt || (v.w == zt && j + 3 < t));
+        }
+    } else {
+        for (int j = tid; j < C; j += SCE_THREADS) {
+            const float v = row[j];
+            s += expf(v - m);
+            cnt += v > zt || (v == zt && j < t);
+        }
+    }
+    s = block_sum(s, red_f);
+    sz = block_sum(sz, red_f);
+    cnt = block_sum(cnt, red_i);
+    if (tid == 0) {
+        const float ls = logf(s);
+        const float l = m + ls;                  // NaN for a row with a NaN or +inf logit
+        // lse - z_t and lse - mean as (max - .) + log s: the rounding of lse (half an ulp of a number of the logits'
+        // size) stays out of a loss that is small when the target holds the maximum
+        const float smooth = eps != 0.f ? eps * ((m - sz / (float)C) + ls) : 0.f;
+        const bool bad = !t_ok || !(l == l);
+        lse[b] = l;
+        row_loss[b] = (1.f - eps) * ((m - zt) + ls) + smooth;        // zt is NaN for a bad target
+        rank[b] = bad ? C : cnt;
+        pred[b] = mi < C ? mi : 0;               // INT_MAX only when no logit compares above -inf
+    }
+}
+
+__global__ __launch_bounds__(SCE_THREADS) void sce_mean_k(const float* __restrict__ row_loss,
+                                                         const int32_t* __restrict__ n_valid, float* __restrict__ loss,
+                                                         int64_t B) {
+    __shared__ float red_f[4];
+    const int64_t nv = valid_rows(n_valid, B);
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < nv; i += SCE_THREADS) s += row_loss[i];
+    s = block_sum(s, red_f);
+    if (threadIdx.x == 0) loss[0] = s / (float)nv;           // an empty mean is NaN, as torch's
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(SCE_THREADS) void sce_bwd_k(const float* __restrict__ z, const int64_t* __restrict__ target,
+                                                        const int32_t* __restrict__ n_valid, const float* __restrict__ lse,
+                                                        const float* __restrict__ g, float* __restrict__ dz, int64_t B,
+                                                        int C, float eps) {
+    const int64_t b = blockIdx.x;
+    const int64_t nv = valid_rows(n_valid, B);
+    const int tid = threadIdx.x;
+    const float* zr = z + b * C;
+    float* dr = dz + b * C;
+    const bool live = b < nv;
+    const int64_t t64 = live ? target[b] : 0;
+    const bool t_ok = t64 >= 0 && t64 < C;
+    const int t = t_ok ? (int)t64 : -1;          // -1 matches no column
+    const float fill = live ? NAN : 0.f;         // a live row gets here only with a bad target
+    if (!live || !t_ok) {
+        for (int j = tid; j < C; j += SCE_THREADS) dr[j] = fill;
+        return;
+    }
+    const float scale = g[0] / (float)nv;
+    const float l = lse[b];
+    const float hit = 1.f - eps, flat = eps / (float)C;
+    if (VEC) {
+        const f32x4* zr4 = reinterpret_cast<const f32x4*>(zr);
+        f32x4* dr4 = reinterpret_cast<f32x4*>(dr);
+        for (int q = tid; q < C / 4; q += SCE_THREADS) {
+            const f32x4 v = zr4[q];
+            const int j = 4 * q;
+            f32x4 d;
+            d.x = scale * (expf(v.x - l) - (j == t ? hit : 0.f) - flat);
+            d.y = scale * (expf(v.y - l) - (j + 1 == t ? hit : 0.f) - flat);
+            d.z = scale * (expf(v.z - l) - (j + 2 == t ? hit : 0.f) - flat);
+            d.w = scale * (expf(v.w - l) - (j + 3 == t ? hit : 0.f) - flat);
+            dr4[q] = d;
+        }
+    } else {
+        for (int j = tid; j < C; j += SCE_THREADS) dr[j] = scale * (expf(zr[j] - l) - (j == t ? hit : 0.f) - flat);
+    }
+}
+
+// accumulator block, in 8-byte words (hwgat_hip.h documents the same offsets)
+constexpr int ACC_N_SAMPLES = 0, ACC_N_BATCHES = 1, ACC_N_INVALID = 2, ACC_LOSS_SAMPLES = 3, ACC_LOSS_BATCHES = 4,
+              ACC_RANK_HIST = 5;
+
+__global__ __launch_bounds__(SCE_THREADS) void eval_acc_k(int64_t* __restrict__ acc, const float* __restrict__ row_loss,
+                                                         const int32_t* __restrict__ rank,
+                                                         const int32_t* __restrict__ pred,
+                                                         const int64_t* __restrict__ target,
+                                                         const float* __restrict__ loss,
+                                                         const int32_t* __restrict__ n_valid, int64_t B, int C, int k_max,
+                                                         int64_t cap) {
+    __shared__ double red_d[4];
+    __shared__ int red_i[4];
+    const int64_t nv = valid_rows(n_valid, B);
+    if (nv == 0) return;                         // an empty batch is no batch
+    const int tid = threadIdx.x;
+    unsigned long long* hist = reinterpret_cast<unsigned long long*>(acc + ACC_RANK_HIST);
+    unsigned long long* conf = hist + (k_max + 1);
+    int32_t* pred_log = reinterpret_cast<int32_t*>(conf + (int64_t)C * C);
+    int32_t* target_log = pred_log + cap;
+    const int64_t base = acc[ACC_N_SAMPLES];     // read by every thread before thread 0 rewrites it (barriers below)
+    double s = 0.0;
+    int invalid = 0;
+    for (int64_t r = tid; r < nv; r += SCE_THREADS) {
+        s += (double)row_loss[r];
+        const int64_t t = target[r];
+        const int p = pred[r];
+        const bool t_ok = t >= 0 && t < C;
+        if (!t_ok) {
+            ++invalid;
+        } else {
+            int k = rank[r];
+            k = k < 0 ? 0 : (k > k_max ? k_max : k);
+            atomicAdd(hist + k, 1ull);
+            if (p >= 0 && p < C) atomicAdd(conf + t * C + p, 1ull);
+        }
+        if (base + r < cap) {                    // a full log drops further rows; the counters above still see them
+            pred_log[base + r] = p;
+            target_log[base + r] = t_ok ? (int32_t)t : -1;
+        }
+    }
+    s = block_sum(s, red_d);
+    invalid = block_sum(invalid, red_i);
+    if (tid == 0) {
+        acc[ACC_N_SAMPLES] = base + nv;
+        acc[ACC_N_BATCHES] += 1;
+        acc[ACC_N_INVALID] += invalid;
+        double* f = reinterpret_cast<double*>(acc);
+        f[ACC_LOSS_SAMPLES] += s;
+        f[ACC_LOSS_BATCHES] += (double)loss[0];
+    }
+}
+
+inline bool bad_shape(int64_t B, int C) { return B < 1 || B > 0x7fffffff || C < 1 || C > SCE_MAX_C; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+extern "C" int hwgat_sce_fwd(const float* logits, const int64_t* target, const int32_t* n_valid, float* lse, float* row_loss,
+                             int32_t* rank, int32_t* pred, float* loss, int64_t B, int C, float eps, void* stream) {
+    if (!logits || !target || !lse || !row_loss || !rank || !pred || !loss) return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = C % 4 == 0 && aligned16(logits);
+    const bool staged = C <= SCE_LDS_FLOATS;
+#define SCE_FWD(S, V) sce_fwd_k<S, V><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_valid, lse, row_loss, rank, pred, B, C, eps)
+    if (staged) { if (vec) SCE_FWD(true, true); else SCE_FWD(true, false); }
+    else { if (vec) SCE_FWD(false, true); else SCE_FWD(false, false); }
+#undef SCE_FWD
+    sce_mean_k<<<1, SCE_THREADS, 0, st>>>(row_loss, n_valid, loss, B);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_sce_bwd(const float* logits, const int64_t* target, const int32_t* n_valid, const float* lse,
+                             const float* g, float* dlogits, int64_t B, int C, float eps, void* stream) {
+    if (!logits || !target || !lse || !g || !dlogits) return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (C % 4 == 0 && aligned16(logits) && aligned16(dlogits))
+        sce_bwd_k<true><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_valid, lse, g, dlogits, B, C, eps);
+    else
+        sce_bwd_k<false><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_valid, lse, g, dlogits, B, C, eps);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int64_t hwgat_eval_acc_bytes(int C, int k_max, int64_t cap) {
+    if (C < 1 || C > SCE_MAX_C || k_max < 0 || cap < 0) return -1;
+    return 8 * (ACC_RANK_HIST + ((int64_t)k_max + 1) + (int64_t)C * C + cap);       // the two int32 logs fill `cap` words
+}
+
+extern "C" int hwgat_eval_accumulate(void* acc, const float* row_loss, const int32_t* rank, const int32_t* pred,
+                                     const int64_t* target, const float* loss, const int32_t* n_valid, int64_t B, int C,
+                                     int k_max, int64_t cap, void* stream) {
+    if (!acc || !row_loss || !rank || !pred || !target || !loss || k_max < 0 || cap < 0) return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    eval_acc_k<<<1, SCE_THREADS, 0, (hipStream_t)stream>>>(static_cast<int64_t*>(acc), row_loss, rank, pred, target, loss,
+                                                          n_valid, B, C, k_max, cap);
+    HWGAT_LAUNCH_CHECK();
+}

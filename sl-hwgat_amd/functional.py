@@ -1316,3 +1316,78 @@ def dgcn_masked_sum(a, ma, b, mb):
     out = torch.empty_like(a)
     call("hwgat_dgcn_masked_sum", ptr(a), ptr(ma), ptr(b), ptr(mb), ptr(out), a.numel(), stream())
     return out
+
+
+# ---------------------------------------------------------------- smoothed cross-entropy and evaluation (train.py, evaluate.py)
+# Thin launchers of csrc/loss_eval.hip.  logits fp32 (B, C), target int64 (B); `n_valid` is a device int32 (1,) or None (all
+# rows): rows at or beyond it are left untouched by the forward and the accumulator and are zero in the backward.
+EVAL_ACC_HEADER_WORDS = 5       # n_samples, n_batches, n_invalid (int64), loss_sum_samples, loss_sum_batches (double)
+
+
+def _sce_check(logits, target):
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"logits must be fp32 (B, C), got {logits.dtype} {tuple(logits.shape)}")
+    if target.dtype != torch.int64 or target.shape != logits.shape[:1]:
+        raise ValueError(f"target must be int64 (B,), got {target.dtype} {tuple(target.shape)}")
+
+
+def sce_forward(logits, target, eps, n_valid=None, out=None):
+    """(loss (1,), row_loss (B,), lse (B,), rank (B,) int32, pred (B,) int32) of the smoothed cross-entropy; `out` takes the
+    same five tensors preallocated"""
+    _sce_check(logits, target)
+    B, C = logits.shape
+    if out is None:
+        f = torch.empty(2 * B + 1, device=logits.device, dtype=torch.float32)
+        i = torch.empty(2, B, device=logits.device, dtype=torch.int32)
+        out = (f[2 * B:], f[:B], f[B:2 * B], i[0], i[1])
+    loss, row_loss, lse, rank, pred = out
+    call("hwgat_sce_fwd", ptr(logits), ptr(target), ptr(n_valid), ptr(lse), ptr(row_loss), ptr(rank), ptr(pred), ptr(loss),
+         B, C, float(eps), stream())
+    return out
+
+
+def sce_backward(logits, target, lse, g, eps, n_valid=None, out=None):
+    """d loss / d logits times the device scalar `g` (float32, one element)"""
+    _sce_check(logits, target)
+    B, C = logits.shape
+    dz = torch.empty_like(logits) if out is None else out
+    call("hwgat_sce_bwd", ptr(logits), ptr(target), ptr(n_valid), ptr(lse), ptr(g), ptr(dz), B, C, float(eps), stream())
+    return dz
+
+
+def eval_acc_words(num_classes, k_max, cap):
+    """size of the accumulator block of eval_accumulate in 8-byte words (layout: include/hwgat_hip.h)"""
+    n = _lib.lib().hwgat_eval_acc_bytes(int(num_classes), int(k_max), int(cap))
+    if n < 0:
+        raise ValueError(f"no accumulator for num_classes {num_classes}, k_max {k_max}, log capacity {cap}")
+    return n // 8
+
+
+def eval_accumulate(acc, row_loss, rank, pred, target, loss, n_valid, num_classes, k_max, cap):
+    """fold one sce_forward into the int64 accumulator block `acc` (eval_acc_words long, zeroed to reset)"""
+    if acc.dtype != torch.int64 or acc.numel() < eval_acc_words(num_classes, k_max, cap):
+        raise ValueError("the accumulator block must be int64 and eval_acc_words(num_classes, k_max, cap) long")
+    call("hwgat_eval_accumulate", ptr(acc), ptr(row_loss), ptr(rank), ptr(pred), ptr(target), ptr(loss), ptr(n_valid),
+         row_loss.numel(), int(num_classes), int(k_max), int(cap), stream())
+
+
+class _SmoothCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, eps, n_valid):
+        loss, _, lse, rank, pred = sce_forward(logits, target, eps, n_valid)
+        ctx.save_for_backward(logits, target, lse)
+        ctx.eps, ctx.n_valid = eps, n_valid
+        ctx.mark_non_differentiable(rank, pred)
+        return loss.view(()), rank, pred
+
+    @staticmethod
+    def backward(ctx, g, _rank, _pred):
+        logits, target, lse = ctx.saved_tensors
+        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
+        return sce_backward(logits, target, lse, g, ctx.eps, ctx.n_valid), None, None, None
+
+
+def smooth_ce(logits, target, eps, n_valid=None):
+    """(loss, rank, pred): the batch-mean smoothed cross-entropy as an autograd node (forward two launches, backward one),
+    with the detached rank of the target in a stable descending sort and the arg-max (both int32)"""
+    return _SmoothCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_valid)

@@ -17,6 +17,35 @@ class SmoothedCrossEntropyLoss(torch.nn.Module):
         return ((1.0 - self.smooth_factor) * nll + self.smooth_factor * (-lp.mean(-1))).mean()
 
 
+class FusedSmoothedCrossEntropyLoss(torch.nn.Module):
+    """SmoothedCrossEntropyLoss on the HIP kernels of csrc/loss_eval.hip: two launches forward, one backward, instead of
+    the ~15 of log_softmax / gather / mean / blend and their backward.  The forward also leaves `last_rank` (the target's
+    place in a stable descending sort of the row, int32) and `last_pred` (lowest arg-max index, int32) of its batch on the
+    device; `correct()` is the number of rows whose target ranks first.  The rank's tie rule and argmax both prefer the
+    lowest index, so that is the `(argmax == target).sum()` of TrainStep without its three launches."""
+
+    def __init__(self, smooth_factor: float = 0.01):
+        super().__init__()
+        self.smooth_factor = smooth_factor
+        self.last_rank = self.last_pred = None
+
+    def forward(self, input, target):
+        import importlib
+        HF = importlib.import_module(__package__ + ".functional")
+        loss, self.last_rank, self.last_pred = HF.smooth_ce(input, target, self.smooth_factor)
+        return loss
+
+    def correct(self):
+        return (self.last_rank == 0).sum()
+
+
+def _correct(criterion, out, y):
+    """correct-count of the batch the criterion has just seen: its own when it keeps one, else the argmax line"""
+    if hasattr(criterion, "correct"):
+        return criterion.correct()
+    return (out.detach().argmax(-1) == y).sum()
+
+
 class TrainStep:
     """zero_grad -> forward -> loss -> backward (-> bucketed all-reduce) -> optimizer.
 
@@ -51,7 +80,7 @@ class TrainStep:
             loss = self.criterion(out, ys) * (xs.shape[0] / n)
             loss.backward()
             total = loss.detach() if total is None else total + loss.detach()
-            c = (out.detach().argmax(-1) == ys).sum()
+            c = _correct(self.criterion, out, ys)
             correct = c if correct is None else correct + c
         if self.reducer is not None:
             self.reducer.finish()
@@ -146,7 +175,7 @@ class GraphedTrainStep:
             self.reducer.finish()
         if step:
             self.opt.step()
-        return loss.detach(), (out.detach().argmax(-1) == self.y).sum()
+        return loss.detach(), _correct(self.criterion, out, self.y)
 
     def _addresses(self):
         return tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
