@@ -18,6 +18,8 @@ all dropout masks are recomputed (masks are a hash of (seed, element index)).
 
 backward (4 dW/db GEMMs, 4 dX GEMMs, attention backward, 2 LN backward launches).
 """
+from typing import Any, NamedTuple, Optional, Tuple
+
 import torch
 
 from . import functional as HF
@@ -69,13 +71,35 @@ class _DwQueue:
             self.main.wait_event(ev)
 
 
+class BlockConfig(NamedTuple):
+    """everything of a fused_block call that is not a differentiable tensor: the one non-tensor argument of _FusedBlock"""
+    bits: torch.Tensor                      # the attention kind's mask rows
+    n_heads: int
+    shifted: bool
+    p: float                                # dropout rate of the proj / fc1 / fc2 sites
+    seeds: Tuple[int, ...]                  # site seeds: proj, fc1, fc2, attention probabilities
+    kind: str                               # a key of functional.ATTN_KINDS
+    want_stats: bool
+    merge_out: bool
+    up: Optional[Tuple[int, float]]         # (seed, p) of the producing block's fc2 dropout, with a carrier only
+    carry_out: bool
+    book: Any                               # functional.CarryBook of the forward call, or None
+    deterministic: bool
+    attn_p: float
+    prep: Optional[dict]                    # this block's entry of the call's functional.WeightPrep
+    seed_base: Optional[torch.Tensor]
+    deterministic_backward: bool            # fixed-order parameter gradients (functional.linear_tn / ln_backward)
+
+
 class _FusedBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xc, thr, m1, r1, n1w, n1b, wqkv, bqkv, wp, bp, n2w, n2b, w1, b1, w2, b2, cfg):
         # xc: the "carrier" the producing block handed over with x (or None).  It has no data (a 1-element tensor
         # expanded to x's shape); its only purpose is that THIS block's backward can return, as its gradient, the masked
         # copy of dx that the producing block needs in front of its fc2 dropout (cfg `up` = that dropout's seed).
-        bits, n_heads, shifted, p, seeds, kind, want_stats, merge_out, up, carry_out, book, deterministic, attn_p, prep, sb, _det_bwd = cfg
+        bits, n_heads, shifted, p, seeds, kind = cfg.bits, cfg.n_heads, cfg.shifted, cfg.p, cfg.seeds, cfg.kind
+        want_stats, merge_out, up, carry_out, book = cfg.want_stats, cfg.merge_out, cfg.up, cfg.carry_out, cfg.book
+        deterministic, attn_p, prep, sb = cfg.deterministic, cfg.attn_p, cfg.prep, cfg.seed_base
         ctx.set_materialize_grads(False)          # an unused carrier gradient arrives as None, not as a zero tensor
         B, F, K, d = x.shape
         dt = x.dtype                              # fp32, or bf16 activations with fp32 master weights
@@ -136,9 +160,9 @@ class _FusedBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dmo, _dro, doutm=None):
         x, thr, n1w, n1b, wqkv, wp, n2w, n2b, w1, w2, m1, r1, qkv, o, y, m2, r2, h1, u = ctx.saved_tensors
-        bits, n_heads, shifted, p, seeds, kind = ctx.cfg[:6]
-        up, attn_p, prep, sb = ctx.cfg[8], ctx.cfg[12], ctx.cfg[13] or {}, ctx.cfg[14]
-        det = bool(ctx.cfg[15])                    # `deterministic_backward`: fixed-order parameter gradients (functional.linear_tn / ln_backward)
+        cfg = ctx.cfg
+        bits, n_heads, shifted, p, seeds, kind = cfg.bits, cfg.n_heads, cfg.shifted, cfg.p, cfg.seeds, cfg.kind
+        up, attn_p, prep, sb, det = cfg.up, cfg.attn_p, cfg.prep or {}, cfg.seed_base, cfg.deterministic_backward
         if prep and ("w2T" not in prep or prep["w2T"].dtype != x.dtype):
             prep = {}
 
@@ -233,7 +257,9 @@ def fused_block(x, thr, blk, bits, n_heads, shifted, p, seeds, kind="win", stats
                 merge_out=False, return_stats=False, carrier=None, up=None, carry_out=False, return_carrier=None,
                 book=None, deterministic=False, attn_p=0.0, prep=None, seed_base=None, deterministic_backward=False):
     """x (B,F,K,d) contiguous; `blk` holds norm1/attn.qkv/attn.proj/norm2/ff.fc1/ff.fc2.
-    `kind`: 'win' = HWGATE part-window attention, 'blk' = HGATE block attention (thr must be None).
+    `kind`: a key of functional.ATTN_KINDS -- 'win' = HWGATE part windows (W = 16), 'pwin' = HWGATE part windows of any
+    other size W <= 32, 'blk' = HGATE blocks, 'band' = WGATE (W = 16), 'wband' = GATE and WGATE with any other W <= 32;
+    `thr` must be None for all but 'win' / 'pwin', `shifted` False for 'band' / 'wband'.
     `stats` = (mean, rstd) of the rows of x if the producer already has them; `want_stats`: have the fc2 epilogue produce
     the statistics of the output rows; `merge_out`: store the output in the TemporalMerging layout (B, F/2, K, 2d)
     (done only where the epilogue can: fp32, whole tiles -- check the returned shape).
@@ -242,7 +268,7 @@ def fused_block(x, thr, blk, bits, n_heads, shifted, p, seeds, kind="win", stats
     loaders: `carry_out` makes this block return a data-less carrier next to `out`; the consumer passes it as `carrier`
     together with `up` = (this block's seeds[2], p) and returns the masked gradient as the carrier's gradient; both
     sides need the same `book` (functional.CarryBook of this forward call), without one no carrier is made or used.
-    `attn_p`: attention dropout rate (reference HWGATE.py:78,112; 'win' only, needs `thr` and a fourth seed, seeds[3]).
+    `attn_p`: attention dropout rate (reference HWGATE.py:78,112; needs a fourth seed, seeds[3], and for 'win' / 'pwin' `thr`).
     `prep`: this block's entry of the call's functional.WeightPrep (derived weight copies made by one launch per call).
     `seed_base`: 1-element device tensor added to every site seed when a kernel runs (functional.embed), or None.
     `deterministic_backward`: bit-reproducible parameter gradients (per-split / per-block partial images added in a fixed
@@ -258,9 +284,11 @@ def fused_block(x, thr, blk, bits, n_heads, shifted, p, seeds, kind="win", stats
         x, carrier, thr, m1, r1, blk.norm1.weight, blk.norm1.bias, blk.attn.qkv.weight, blk.attn.qkv.bias,
         blk.attn.proj.weight, blk.attn.proj.bias, blk.norm2.weight, blk.norm2.bias,
         blk.ff.fc1.weight, blk.ff.fc1.bias, blk.ff.fc2.weight, blk.ff.fc2.bias,
-        (bits, n_heads, shifted, float(p), tuple(int(s) for s in seeds), kind, bool(want_stats), bool(merge_out),
-         (int(up[0]), float(up[1])) if (up is not None and carrier is not None) else None, bool(carry_out),
-         book, bool(deterministic), float(attn_p), prep, seed_base, bool(deterministic_backward)))
+        BlockConfig(bits=bits, n_heads=n_heads, shifted=shifted, p=float(p), seeds=tuple(int(s) for s in seeds), kind=kind,
+                    want_stats=bool(want_stats), merge_out=bool(merge_out),
+                    up=(int(up[0]), float(up[1])) if (up is not None and carrier is not None) else None,
+                    carry_out=bool(carry_out), book=book, deterministic=bool(deterministic), attn_p=float(attn_p),
+                    prep=prep, seed_base=seed_base, deterministic_backward=bool(deterministic_backward)))
     oc = oc if oc.numel() else None
     if return_carrier is None:
         return_carrier = bool(carry_out)

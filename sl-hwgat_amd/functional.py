@@ -4,6 +4,8 @@ Every function here calls straight into libhwgat_hip.so through `_lib.call`;
 nothing falls back to torch arithmetic.  All activations are in the natural
 token order (B, F, K, d).
 """
+from typing import Callable, NamedTuple
+
 import torch
 
 from . import _lib
@@ -190,20 +192,6 @@ def wband_mask_rows(adj: torch.Tensor, frames: int, window_size: int) -> torch.T
     return torch.where(rows >= 2 ** 31, rows - 2 ** 32, rows).to(torch.int32).contiguous()
 
 
-def _wband_shape(o, rows, n_heads):
-    """(B, F, nW, W, head_dim) of a 'wband' launch; nW comes from the (nW, 32, 3) mask words"""
-    B, F, K, d = o.shape
-    if rows.dtype != torch.int32 or rows.dim() != 3 or tuple(rows.shape[1:]) != (32, 3):
-        raise ValueError("'wband' attention needs the (nW, 32, 3) int32 words of functional.wband_mask_rows")
-    nW = rows.shape[0]
-    if K % nW or K // nW > 32:
-        raise ValueError(f"mask words are for {nW} windows, activations have {K} joints per frame")
-    hd = d // n_heads
-    if d % n_heads or hd not in (16, 32):
-        raise NotImplementedError(f"head_dim {d / n_heads:g}: the wide band attention kernels take head_dim 16 or 32")
-    return B, F, nW, K // nW, hd
-
-
 # ---------------------------------------------------------------- embedding
 def embed(x, idx, bmat, pe, K, out_dtype=torch.float32, drop_p=0.0, seed=0, seed_base=None):
     """gather + Fourier features + PE (+ dropout) (no gradient: B is frozen, PE a buffer).
@@ -253,12 +241,121 @@ def layer_norm(x, gamma, beta, deterministic=False):
 
 
 # ---------------------------------------------------------------- attention
-class _WinAttn(torch.autograd.Function):
+def _tile16_dims(shape, bits, n_heads):
+    B, F, K, d = shape
+    return B, F, K // 16, n_heads, d // n_heads
+
+
+def _blk_dims(shape, bits, n_heads):
+    B, F, K, d = shape
+    return B, F, K, n_heads, d // n_heads
+
+
+def _pwin_dims(shape, bits, n_heads):
+    """(B, F, K, W, n_heads, head_dim) of a 'pwin' launch; W comes from the (2, nW, 2W) mask rows"""
+    B, F, K, d = shape
+    if bits.dtype != torch.int64 or bits.dim() != 3 or bits.shape[0] != 2 or bits.shape[2] % 2:
+        raise ValueError("'pwin' attention needs the (2, nW, 2W) int64 rows of functional.pwin_mask_bits")
+    W = bits.shape[2] // 2
+    if bits.shape[1] * W != K:
+        raise ValueError(f"mask rows are for {bits.shape[1]} windows of {W} joints, activations have {K} joints")
+    hd = d // n_heads
+    if hd not in (32, 64):
+        raise NotImplementedError(f"head_dim {hd}: the part-window attention kernels for window sizes other than 16 "
+                                  f"take head_dim 32 or 64")
+    return B, F, K, W, n_heads, hd
+
+
+def _wband_dims(shape, rows, n_heads):
+    """(B, F, nW, W, n_heads, head_dim) of a 'wband' launch; nW comes from the (nW, 32, 3) mask words"""
+    B, F, K, d = shape
+    if rows.dtype != torch.int32 or rows.dim() != 3 or tuple(rows.shape[1:]) != (32, 3):
+        raise ValueError("'wband' attention needs the (nW, 32, 3) int32 words of functional.wband_mask_rows")
+    nW = rows.shape[0]
+    if K % nW or K // nW > 32:
+        raise ValueError(f"mask words are for {nW} windows, activations have {K} joints per frame")
+    hd = d // n_heads
+    if d % n_heads or hd not in (16, 32):
+        raise NotImplementedError(f"head_dim {d / n_heads:g}: the wide band attention kernels take head_dim 16 or 32")
+    return B, F, nW, K // nW, n_heads, hd
+
+
+class AttnKind(NamedTuple):
+    """one attention kind: entry points `<stem>_fwd[_drop]` / `<stem>_bwd[_drop]` (include/hwgat_hip.h) taking
+    qkv, o | (do, dqkv), mask[, thr], *dims(o_shape, mask, n_heads)[, shifted], dtype[, seed, p, seed_base], stream"""
+    stem: str
+    takes_thr: bool             # the train-mode threshold drop of the part-window models (HWGATE.py:94-100)
+    takes_shifted: bool         # the last-slot mask of a shifted layer
+    dims: Callable              # (o_shape, mask, n_heads) -> the integer arguments, after checking mask and head_dim
+    refusal: str                # what the assertion says when a threshold / shift is given to a kind without one
+
+
+ATTN_KINDS = {
+    # HWGATE part windows, W = 16
+    "win": AttnKind("hwgat_win_attn", True, True, _tile16_dims, ""),
+    # HWGATE part windows of any other size W <= 32 (W from the mask rows, functional.pwin_mask_bits)
+    "pwin": AttnKind("hwgat_pwin_attn", True, True, _pwin_dims, ""),
+    # HGATE blocks
+    "blk": AttnKind("hwgat_blk_attn", False, True, _blk_dims, "HGATE has no train-mode threshold"),
+    # WGATE, W = 16
+    "band": AttnKind("hwgat_band_attn", False, False, _tile16_dims, "WGATE has neither threshold nor shift"),
+    # GATE, and WGATE with any other W <= 32 (functional.wband_mask_rows)
+    "wband": AttnKind("hwgat_wband_attn", False, False, _wband_dims, "the band models have neither threshold nor shift"),
+}
+
+
+def _attn_kind(kind):
+    if kind not in ATTN_KINDS:
+        raise ValueError(kind)
+    return ATTN_KINDS[kind]
+
+
+def _attn_drop(kind, thr, drop):
+    """(seed, p, seed_base) of the attention dropout (reference HWGATE.py:78,112, HGATE.py:78,106, WGATE.py:81,103) or None"""
+    if drop is None or float(drop[1]) <= 0.0:
+        return None
+    if _attn_kind(kind).takes_thr and thr is None:
+        raise ValueError("attention dropout is a train-mode operation: it needs the train-mode threshold tensor")
+    return int(drop[0]) & 0xFFFFFFFF, float(drop[1]), (drop[2] if len(drop) > 2 else None)
+
+
+def _attn_launch(direction, kind, qkv, tensors, bits, thr, n_heads, shifted, drop):
+    """launch `<stem>_<direction>` of `kind`, or its `_drop` entry when the dropout rate is above 0;
+    `tensors` = (o,) for 'fwd', (do, dqkv) for 'bwd'"""
+    rec = _attn_kind(kind)
+    drop = _attn_drop(kind, thr, drop)
+    assert (rec.takes_thr or thr is None) and (rec.takes_shifted or not shifted), rec.refusal
+    args = [ptr(qkv), *(ptr(t) for t in tensors), ptr(bits)]
+    if rec.takes_thr:
+        args.append(ptr(thr))
+    args += rec.dims(tensors[0].shape, bits, n_heads)
+    if rec.takes_shifted:
+        args.append(int(shifted))
+    args.append(dtype_code(qkv))
+    if drop is None:
+        call(f"{rec.stem}_{direction}", *args, stream())
+    else:
+        call(f"{rec.stem}_{direction}_drop", *args, drop[0], drop[1], ptr(drop[2]), stream())
+
+
+def attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop=None):
+    """launch the attention forward of a model family: 'win' = HWGATE part windows (W = 16), 'pwin' = HWGATE part
+    windows of any other size W <= 32 (W from `bits`, functional.pwin_mask_bits), 'blk' = HGATE blocks, 'band' = WGATE
+    (W = 16), 'wband' = GATE and WGATE with any other W <= 32 (functional.wband_mask_rows).
+    `drop` = (seed, p) or (seed, p, seed_base): attention dropout ('win' / 'pwin': train mode only)"""
+    _attn_launch("fwd", kind, qkv, (o,), bits, thr, n_heads, shifted, drop)
+
+
+def attn_bwd(kind, qkv, do, dqkv, bits, thr, n_heads, shifted, drop=None):
+    """the backward of attn_fwd: dqkv from qkv and do, masks regenerated from the same `drop`"""
+    _attn_launch("bwd", kind, qkv, (do, dqkv), bits, thr, n_heads, shifted, drop)
+
+
+class _Attn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, bits, thr, n_heads, shifted, drop, kind="win"):
+    def forward(ctx, qkv, bits, thr, n_heads, shifted, drop, kind):
         B, F, K, d3 = qkv.shape
-        d = d3 // 3
-        o = torch.empty(B, F, K, d, device=qkv.device, dtype=qkv.dtype)
+        o = torch.empty(B, F, K, d3 // 3, device=qkv.device, dtype=qkv.dtype)
         attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop)
         ctx.save_for_backward(qkv, bits, thr)
         ctx.cfg = (n_heads, int(shifted), drop, kind)
@@ -274,194 +371,36 @@ class _WinAttn(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None
 
 
-def _attn_drop(kind, thr, drop):
-    """(seed, p, seed_base) of the attention dropout (reference HWGATE.py:78,112, HGATE.py:78,106, WGATE.py:81,103) or None"""
-    if drop is None or float(drop[1]) <= 0.0:
-        return None
-    if kind in ("win", "pwin") and thr is None:
-        raise ValueError("attention dropout is a train-mode operation: it needs the train-mode threshold tensor")
-    return int(drop[0]) & 0xFFFFFFFF, float(drop[1]), (drop[2] if len(drop) > 2 else None)
-
-
-def _pwin_shape(o, bits, n_heads):
-    """(B, F, K, W, head_dim) of a 'pwin' launch; W comes from the (2, nW, 2W) mask rows"""
-    B, F, K, d = o.shape
-    if bits.dtype != torch.int64 or bits.dim() != 3 or bits.shape[0] != 2 or bits.shape[2] % 2:
-        raise ValueError("'pwin' attention needs the (2, nW, 2W) int64 rows of functional.pwin_mask_bits")
-    W = bits.shape[2] // 2
-    if bits.shape[1] * W != K:
-        raise ValueError(f"mask rows are for {bits.shape[1]} windows of {W} joints, activations have {K} joints")
-    hd = d // n_heads
-    if hd not in (32, 64):
-        raise NotImplementedError(f"head_dim {hd}: the part-window attention kernels for window sizes other than 16 "
-                                  f"take head_dim 32 or 64")
-    return B, F, K, W, hd
-
-
-def attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, drop=None):
-    """launch the attention forward of a model family: 'win' = HWGATE part windows (W = 16), 'pwin' = HWGATE part
-    windows of any other size W <= 32 (W from `bits`, functional.pwin_mask_bits), 'blk' = HGATE blocks, 'band' = WGATE
-    (W = 16), 'wband' = GATE and WGATE with any other W <= 32 (functional.wband_mask_rows).
-    `drop` = (seed, p) or (seed, p, seed_base): attention dropout ('win', train mode only)"""
-    B, F, K, d = o.shape
-    drop = _attn_drop(kind, thr, drop)
-    if kind == "win" and drop is not None:
-        call("hwgat_win_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B, F, K // 16, n_heads, d // n_heads,
-             int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-    elif kind == "win":
-        call("hwgat_win_attn_fwd", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B, F, K // 16, n_heads, d // n_heads,
-             int(shifted), dtype_code(qkv), stream())
-    elif kind == "pwin":
-        B_, F_, K_, W, hd = _pwin_shape(o, bits, n_heads)
-        if drop is not None:
-            call("hwgat_pwin_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads, hd,
-                 int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_pwin_attn_fwd", ptr(qkv), ptr(o), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads, hd, int(shifted),
-                 dtype_code(qkv), stream())
-    elif kind == "blk":
-        assert thr is None, "HGATE has no train-mode threshold"
-        if drop is not None:
-            call("hwgat_blk_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), B, F, K, n_heads, d // n_heads, int(shifted),
-                 dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_blk_attn_fwd", ptr(qkv), ptr(o), ptr(bits), B, F, K, n_heads, d // n_heads, int(shifted),
-                 dtype_code(qkv), stream())
-    elif kind == "band":
-        assert thr is None and not shifted, "WGATE has neither threshold nor shift"
-        if drop is not None:
-            call("hwgat_band_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), B, F, K // 16, n_heads, d // n_heads,
-                 dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_band_attn_fwd", ptr(qkv), ptr(o), ptr(bits), B, F, K // 16, n_heads, d // n_heads,
-                 dtype_code(qkv), stream())
-    elif kind == "wband":
-        assert thr is None and not shifted, "the band models have neither threshold nor shift"
-        B_, F_, nW, W, hd = _wband_shape(o, bits, n_heads)
-        if drop is not None:
-            call("hwgat_wband_attn_fwd_drop", ptr(qkv), ptr(o), ptr(bits), B_, F_, nW, W, n_heads, hd, dtype_code(qkv),
-                 drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_wband_attn_fwd", ptr(qkv), ptr(o), ptr(bits), B_, F_, nW, W, n_heads, hd, dtype_code(qkv), stream())
-    else:
-        raise ValueError(kind)
-
-
-def attn_bwd(kind, qkv, do, dqkv, bits, thr, n_heads, shifted, drop=None):
-    B, F, K, d = do.shape
-    drop = _attn_drop(kind, thr, drop)
-    if kind == "win" and drop is not None:
-        call("hwgat_win_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B, F, K // 16, n_heads,
-             d // n_heads, int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-    elif kind == "win":
-        call("hwgat_win_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B, F, K // 16, n_heads,
-             d // n_heads, int(shifted), dtype_code(qkv), stream())
-    elif kind == "pwin":
-        B_, F_, K_, W, hd = _pwin_shape(do, bits, n_heads)
-        if drop is not None:
-            call("hwgat_pwin_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads,
-                 hd, int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_pwin_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), ptr(thr), B_, F_, K_, W, n_heads, hd,
-                 int(shifted), dtype_code(qkv), stream())
-    elif kind == "blk":
-        if drop is not None:
-            call("hwgat_blk_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B, F, K, n_heads, d // n_heads,
-                 int(shifted), dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_blk_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B, F, K, n_heads, d // n_heads,
-                 int(shifted), dtype_code(qkv), stream())
-    elif kind == "band":
-        if drop is not None:
-            call("hwgat_band_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B, F, K // 16, n_heads, d // n_heads,
-                 dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_band_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B, F, K // 16, n_heads, d // n_heads,
-                 dtype_code(qkv), stream())
-    elif kind == "wband":
-        B_, F_, nW, W, hd = _wband_shape(do, bits, n_heads)
-        if drop is not None:
-            call("hwgat_wband_attn_bwd_drop", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B_, F_, nW, W, n_heads, hd,
-                 dtype_code(qkv), drop[0], drop[1], ptr(drop[2]), stream())
-        else:
-            call("hwgat_wband_attn_bwd", ptr(qkv), ptr(do), ptr(dqkv), ptr(bits), B_, F_, nW, W, n_heads, hd,
-                 dtype_code(qkv), stream())
-    else:
-        raise ValueError(kind)
-
-
-class _BlkAttn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, bits, n_heads, shifted, drop):
-        B, F, K, d3 = qkv.shape
-        o = torch.empty(B, F, K, d3 // 3, device=qkv.device, dtype=qkv.dtype)
-        attn_fwd("blk", qkv, o, bits, None, n_heads, shifted, drop)
-        ctx.save_for_backward(qkv, bits)
-        ctx.cfg = (n_heads, int(shifted), drop)
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        qkv, bits = ctx.saved_tensors
-        n_heads, shifted, drop = ctx.cfg
-        do = do.contiguous()
-        dqkv = torch.empty_like(qkv)
-        attn_bwd("blk", qkv, do, dqkv, bits, None, n_heads, shifted, drop)
-        return dqkv, None, None, None, None
-
-
-class _BandAttn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, rows, n_heads, drop, kind="band"):
-        B, F, K, d3 = qkv.shape
-        o = torch.empty(B, F, K, d3 // 3, device=qkv.device, dtype=qkv.dtype)
-        attn_fwd(kind, qkv, o, rows, None, n_heads, False, drop)
-        ctx.save_for_backward(qkv, rows)
-        ctx.cfg = (n_heads, drop, kind)
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        qkv, rows = ctx.saved_tensors
-        n_heads, drop, kind = ctx.cfg
-        do = do.contiguous()
-        dqkv = torch.empty_like(qkv)
-        attn_bwd(kind, qkv, do, dqkv, rows, None, n_heads, False, drop)
-        return dqkv, None, None, None, None
-
-
 def band_attention(qkv, rows, n_heads, drop=None):
     """WGATE: qkv (B,F,K,3d) -> o (B,F,K,d); a window = one 16-joint part window over all F frames.
     `drop` = (seed, p[, seed_base]): attention dropout (reference WGATE.py:103)."""
-    return _BandAttn.apply(qkv.contiguous(), rows, n_heads, _attn_drop("band", None, drop))
+    return _Attn.apply(qkv.contiguous(), rows, None, n_heads, False, _attn_drop("band", None, drop), "band")
 
 
 def wband_attention(qkv, rows, n_heads, drop=None):
     """GATE / WGATE with a window size other than 16: qkv (B,F,K,3d) -> o (B,F,K,d); a window = W <= 32 joints over all
     F frames, K = nW * W; `rows` = functional.wband_mask_rows(adj, F, W) on the device.
     `drop` = (seed, p[, seed_base]): attention dropout (reference GATE.py:65, WGATE.py:103)."""
-    return _BandAttn.apply(qkv.contiguous(), rows, n_heads, _attn_drop("wband", None, drop), "wband")
+    return _Attn.apply(qkv.contiguous(), rows, None, n_heads, False, _attn_drop("wband", None, drop), "wband")
 
 
 def block_attention(qkv, bits, n_heads, shifted, drop=None):
     """HGATE: qkv (B,F,K,3d) -> o (B,F,K,d); a block = 2 frames x all K joints.
     `drop` = (seed, p[, seed_base]): attention dropout (reference HGATE.py:106)."""
-    return _BlkAttn.apply(qkv.contiguous(), bits, n_heads, shifted, _attn_drop("blk", None, drop))
+    return _Attn.apply(qkv.contiguous(), bits, None, n_heads, shifted, _attn_drop("blk", None, drop), "blk")
 
 
 def window_attention(qkv, bits, thr, n_heads, shifted, drop=None):
     """qkv (B,F,K,3d) -> o (B,F,K,d).  `thr`: 1-element fp32 device tensor
     (train mode) or None (eval mode).  `drop` = (seed, p): attention dropout on the
     probabilities (reference HWGATE.py:112), train mode only."""
-    drop = _attn_drop("win", thr, drop)
-    return _WinAttn.apply(qkv.contiguous(), bits, thr, n_heads, shifted, drop)
+    return _Attn.apply(qkv.contiguous(), bits, thr, n_heads, shifted, _attn_drop("win", thr, drop), "win")
 
 
 def part_window_attention(qkv, bits, thr, n_heads, shifted, drop=None):
     """HWGATE with a window size W != 16: qkv (B,F,K,3d) -> o (B,F,K,d); `bits` = functional.pwin_mask_bits(adj, W)
     (on the device), the rest as window_attention."""
-    drop = _attn_drop("pwin", thr, drop)
-    return _WinAttn.apply(qkv.contiguous(), bits, thr, n_heads, shifted, drop, "pwin")
+    return _Attn.apply(qkv.contiguous(), bits, thr, n_heads, shifted, _attn_drop("pwin", thr, drop), "pwin")
 
 
 # ---------------------------------------------------------------- merge
@@ -731,7 +670,8 @@ class HandOver:
     """What one block's epilogues produced for the next block of the same forward call: `of` = the tensor the values
     belong to, `stats` = (mean, rstd) of its rows (from the fc2 epilogue), `carrier` / `up` = the data-less carrier of
     the masked gradient and the (seed, p) of the dropout it masks, `plan[k]` = (produce output statistics, store merged)
-    for block k, `book` = the CarryBook of the call.  A local of Model.forward_features; never stored on the module."""
+    for block k, `book` = the CarryBook of the call.  A local of FamilyModel._run_blocks (models/_family.py); never stored on
+    the module."""
 
     def __init__(self, last_block=-1, deterministic=False):
         self.of = self.stats = self.carrier = self.up = None

@@ -14,44 +14,35 @@ neighbouring key frames.  Embedding, LayerNorms, fused linears and the final nor
 kernels HWGATE uses, unchanged.  `adj_mask` is kept only for the state_dict contract; the kernels read
 the mask rows derived from `adj_mat`.
 """
-import torch
 from torch import nn
 
 from .. import functional as HF
-from . import HWGATE as _base
+from ._family import FamilyModel, _additive_mask
+from .HWGATE import _SUPPORTED_WIDTHS
 
 
-class Model(_base.Model):
+class Model(FamilyModel):
     _attn_kind = "band"
 
     def __init__(self, kp_dim=26, num_kps=64, temporal_dim=256, num_classes=1000, embed_dim=64, pe=False,
                  depths=16, num_heads=8, window_size=16, ff_ratio=4., adj_mat=None, drop_rate=0.,
                  attn_drop_rate=0., norm_layer=nn.LayerNorm, device=None) -> None:
-        nn.Module.__init__(self)
         window_size = int(window_size)
         if not 1 <= window_size <= 32:
             raise NotImplementedError(f"window_size {window_size}: the WGATE HIP backend takes part windows of at most 32 "
                                       f"joints (one 32-slot frame per window in the band attention kernels)")
+        super().__init__(kp_dim, num_kps, temporal_dim, num_classes, embed_dim, pe, int(depths), int(num_heads),
+                         embed_dim, drop_rate, attn_drop_rate, ff_ratio, norm_layer)
         if window_size != 16:
             self._attn_kind = "wband"                  # W = 16 stays on the "band" kernels, unchanged
-        if not 0.0 <= float(attn_drop_rate) < 1.0:
-            raise ValueError("attn_drop_rate must be in [0, 1)")
-        self.attn_drop_rate = float(attn_drop_rate)          # nn.Dropout on the attention probabilities (WGATE.py:81,103)
-        if norm_layer is not nn.LayerNorm:
-            raise NotImplementedError("norm_layer must be nn.LayerNorm")
         if adj_mat is None:
             raise NotImplementedError("WGATE needs its (nW, T*W, T*W) adjacency (the reference dereferences it too)")
         assert num_kps % window_size == 0, "window size and number of kps are incompatible"
         d = embed_dim
-        if d not in _base._SUPPORTED_WIDTHS or d % num_heads or (d // num_heads) not in (16, 32):
+        if d not in _SUPPORTED_WIDTHS or d % num_heads or (d // num_heads) not in (16, 32):
             raise NotImplementedError(f"width {d} / heads {num_heads} not supported by the HIP kernels "
                                       "(band attention: head_dim 16 or 32)")
-        self.kp_dim, self.num_kps, self.temporal_dim = kp_dim, num_kps, temporal_dim
-        self.num_classes, self.embed_dim, self.pe = num_classes, embed_dim, pe
-        self.depths, self.num_heads = int(depths), int(num_heads)
-        self.drop_rate, self.ff_ratio = float(drop_rate), ff_ratio
         self.window_size = window_size
-        self.num_features = embed_dim
         self.n_windows = num_kps // window_size
 
         # either builder validates the structure its kernel relies on
@@ -59,59 +50,8 @@ class Model(_base.Model):
                 else HF.wband_mask_rows(adj_mat, temporal_dim, window_size))
         if rows.shape[0] != self.n_windows:
             raise ValueError(f"adjacency has {rows.shape[0]} windows, num_kps / window_size = {self.n_windows}")
-        self.adj_mask_name = "adj_mask"                        # WGATE.py:190-196: 0 -> -10000, 1 -> 0
-        self.register_buffer("adj_mask", adj_mat.to(torch.float32).masked_fill(adj_mat == 0, float(-10000))
-                             .masked_fill(adj_mat == 1, float(0)))
-        self.B = nn.Parameter(torch.normal(0.0, 1.0, (embed_dim // 2, kp_dim)) * 10, requires_grad=False)
-        if pe:
-            self.pos_encoder = _base._Slot()
-            self.pos_encoder.register_buffer("pe", _base._sinusoid(temporal_dim, embed_dim))
-        self.layers = nn.ModuleList()
-        for _ in range(self.depths):
-            blk = _base._Slot()
-            blk.norm1 = nn.LayerNorm(d)
-            blk.attn = _base._Slot()
-            blk.attn.qkv = nn.Linear(d, 3 * d)
-            blk.attn.proj = nn.Linear(d, d)
-            blk.norm2 = nn.LayerNorm(d)
-            blk.ff = _base._Slot()
-            blk.ff.fc1 = nn.Linear(d, int(d * ff_ratio))
-            blk.ff.fc2 = nn.Linear(int(d * ff_ratio), d)
-            self.layers.append(blk)
-        self.norm = nn.LayerNorm(d)
-        self.head = nn.Linear(d, num_classes) if num_classes > 0 else nn.Identity()
-
-        for m in self.modules():                       # reference WGATE.py:229-236
-            if isinstance(m, nn.Linear):
-                nn.init.trunc_normal_(m.weight, std=.02)
-                nn.init.zeros_(m.bias)
-
-        self.adj_mat = adj_mat
-        self.register_buffer("_mask_bits", rows, persistent=False)
-        self.part_index = None
-        self.activation_dtype = torch.float32
-        self.threshold_override = None
-        self._drop_calls = 0
-        self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)   # see HWGATE.Model
-        self.device_seed_counter = False
-        self._call_base = None
-        self.deterministic_eval = True
-        if device is not None:
-            self.to(device)
-
-    def block_list(self):
-        return list(self.layers)
-
-    def forward_features(self, x):
-        h = self._embed(x)
-        hand = HF.HandOver(last_block=self.depths - 1, deterministic=self._deterministic())
-        hand.prep = HF.weight_prep(self, self.block_list(), self.activation_dtype, torch.is_grad_enabled())
-        hand.seed_base = self._call_base if self.training else None       # the copy _embed took (DeviceSeeds._next_step_seed)
-        for k in range(self.depths):                   # every block but the last feeds the next block's LayerNorm
-            hand.plan[k] = (k < self.depths - 1, False)
-        for k, blk in enumerate(self.layers):          # PartAttentionBlock.forward, WGATE.py:150-160
-            h = self._block(h, blk, self.num_heads, False, None, k, hand)
-        if hand.of is h and hand.carrier is not None:
-            return HF.ln_mean_pool(h, self.norm.weight, self.norm.bias, carrier=hand.carrier, up=hand.up, book=hand.book,
-                                   deterministic=hand.deterministic, seed_base=hand.seed_base)
-        return HF.ln_mean_pool(h, self.norm.weight, self.norm.bias, deterministic=hand.deterministic)
+        self.adj_mask_name = "adj_mask"
+        self.register_buffer("adj_mask", _additive_mask(adj_mat))              # (nW, T*W, T*W), WGATE.py:190-196
+        self._build_input()
+        self.layers = nn.ModuleList(self._new_block(d) for _ in range(self.depths))     # PartAttentionBlock, WGATE.py:150-160
+        self._finish(adj_mat, rows, device)

@@ -1,11 +1,12 @@
-"""The device-resident dropout seed of a model (shared by HWGATE / HGATE / WGATE and the Transformer baseline).
+"""The device-resident dropout seed of a model (shared by the graph-attention family, models/_family.py, and the baselines).
 
 Every seeded kernel hashes with  site seed + the call's base seed, which it reads on the device when it runs
 (include/hwgat_hip.h, "dropout seeds") from the per-call copy of `_seed_state[1]` that `_next_step_seed` takes, so a train
 step captured in a HIP graph (train.GraphedTrainStep) replays with fresh masks and a backward regenerates its own
 forward's masks whatever train forwards ran in between.  A model class mixes DeviceSeeds in front of nn.Module and calls
-`_init_device_seeds()` in its constructor; train.TrainStep, train.GraphedTrainStep and serve.GraphedEval use
-`_seed_state`, `_drop_calls`, `_seeds` and `device_seed_counter`.
+`_init_device_seeds()` in its constructor -- the only place these fields are assigned, there are no class-level
+fallbacks; train.TrainStep, train.GraphedTrainStep and serve.GraphedEval use `_seed_state`, `_drop_calls`, `_seeds` and
+`device_seed_counter`.
 """
 import torch
 
@@ -60,8 +61,6 @@ class DeviceSeeds:
         self._drop_calls += 1
         self._call_base = self._seed_state[1:2].clone()
         return self._call_base
-
-    deterministic_train = False
 
     def _deterministic(self):
         """bit-reproducible arithmetic for this call: eval() by default (`deterministic_eval`); train() on request
