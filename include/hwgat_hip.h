@@ -62,7 +62,8 @@ extern "C" {
  *         hwgat_dgcn_abs_sum, hwgat_dgcn_draw, hwgat_dgcn_mask_{spatial,temporal}, hwgat_dgcn_merge(_bwd),
  *         hwgat_dgcn_masked_sum
  *         later additions under the same number (additions only, no existing signature changed): hwgat_sce_{fwd,bwd}, the
- *         fused smoothed cross-entropy; hwgat_eval_accumulate, hwgat_eval_acc_bytes, the device-side evaluation accumulators */
+ *         fused smoothed cross-entropy; hwgat_eval_accumulate, hwgat_eval_acc_bytes, the device-side evaluation accumulators;
+ *         hwgat_ln_param_grads_from_g, the first block's norm1 / qkv parameter gradients without an input gradient */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -147,6 +148,16 @@ int hwgat_ln_bwd_det(const void* dy, const void* x, const float* mean, const flo
                      const float* beta, const void* dres, void* dx, float* dgamma, float* dbeta, int64_t N, int d,
                      int dtype, void* dx_masked, uint32_t mask_seed, float mask_p, void* xn,
                      const uint32_t* seed_base, float* ws, int64_t ws_bytes, void* stream);
+
+/* Parameter gradients of a LayerNorm -> Linear pair (y = (xhat gamma + beta) W^T + b, xhat = (x - mean) rstd) when the
+ * gradient of x itself is not wanted (the first block: its input comes from the parameter-free embedding).  From
+ * G[N,K] = dY^T xhat and db[N] = colsum(dY) -- one hwgat_linear_tn_* launch with gamma = 1, beta = 0 -- this ACCUMULATES
+ *   dW[i][j]  += G[i][j] gamma[j] + db[i] beta[j]
+ *   dgamma[j] += sum_i W[i][j] G[i][j]          dbeta[j] += sum_i db[i] W[i][j]
+ * which replaces the dX GEMM and the LayerNorm-backward pass over the tokens.  All fp32; K % 32 == 0.  The sums over i run
+ * in a fixed order (no atomics): the result is bit-reproducible. */
+int hwgat_ln_param_grads_from_g(const float* G, const float* db, const float* W, const float* gamma, const float* beta,
+                                float* dW, float* dgamma, float* dbeta, int N, int K, void* stream);
 
 /* ---- a-4/a-5/a-6/a-10: fused window attention (MSA.forward, HWGATE.py:89-114)
  * over the body-part joint graph, with partition/roll/reverse as index math.
@@ -449,7 +460,8 @@ int hwgat_linear_tn_bf16_det(const void* A, const void* B, float* dW, float* db,
                              int64_t ws_bytes, void* stream);
 
 /* hwgat_linear_tn_f32 with a caller-owned workspace of hwgat_linear_tn_f32_ws_bytes(M, N, K) bytes: where the 256x256-tile
- * kernel takes the shape (N, K multiples of 256, more than one tile) the partial dW tiles of the M slices go to slabs and a
+ * kernel (N, K multiples of 256) or the whole-weight kernel of the narrow layers ((N, K) = (384,128), (256,128), (128,256),
+ * (128,128); M % 32 == 0) takes the shape, the partial dW tiles of the M slices go to slabs and a
  * second launch adds them in a FIXED order instead of 64 MB of global float atomics (~25 us less per launch, dW
  * bit-reproducible).  Every argument as in hwgat_linear_tn_f32; ws == NULL, too small, or the query returned 0: identical
  * to hwgat_linear_tn_f32. */

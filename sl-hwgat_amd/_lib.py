@@ -25,6 +25,7 @@ _SIGS = {
     "hwgat_is_lab_build": [],
     "hwgat_seed_advance": [_P, _P],
     "hwgat_ln_bwd_det_bytes": [_I],
+    "hwgat_ln_param_grads_from_g": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "hwgat_ln_bwd_det": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _U, _F, _P, _P, _P, _L, _P],
     "hwgat_linear_tn_det_bytes": [_L, _I, _I],
     "hwgat_linear_tn_f32_det": [_P, _P, _P, _P, _L, _I, _I, _U, _F, _P, _P, _P, _P, _P, _P, _L, _P],

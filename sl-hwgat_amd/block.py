@@ -16,7 +16,8 @@ forward  (4 GEMM launches + 1 attention; the reference runs ~40 ATen ops):
 saved for backward: x, qkv, o, y, h1, u and the row statistics (10 E floats); LN outputs and
 all dropout masks are recomputed (masks are a hash of (seed, element index)).
 
-backward (4 dW/db GEMMs, 4 dX GEMMs, attention backward, 2 LN backward launches).
+backward (4 dW/db GEMMs, 4 dX GEMMs, attention backward, 2 LN backward launches; where x needs no gradient -- the first
+block, fp32 -- 3 dX GEMMs, 1 LN backward launch and one small launch that turns dqkv^T xhat into norm1's and qkv's gradients).
 """
 from typing import Any, NamedTuple, Optional, Tuple
 
@@ -188,6 +189,13 @@ class _FusedBlock(torch.autograd.Function):
         # zero-filled buffer and views of it instead of 12 fill launches
         hid = w1.shape[0]
         sizes = [d, d, d, d, 3 * d * d, d * d, hid * d, d * hid, 3 * d, d, d, hid]
+        # The input needs no gradient (the first block: x comes from the parameter-free embedding), fp32, nothing to send
+        # up: norm1's and qkv's parameter gradients are formed from G = dqkv^T xhat -- no dX GEMM for d_xn, no norm1
+        # backward pass over the tokens.  (Deterministic weight gradients need whole 32-row stages: the pass below then.)
+        no_dx = (not ctx.needs_input_grad[0] and dt == torch.float32 and not ctx.send_up
+                 and not (det and (x.numel() // d) % 32))
+        if no_dx:
+            sizes.append(3 * d * d)               # G, zero-filled with the rest
         flat = torch.zeros(sum(sizes), device=x.device, dtype=torch.float32)
         parts = torch.split(flat, sizes)
         dn1w, dn1b, dn2w, dn2b = parts[0], parts[1], parts[2], parts[3]
@@ -230,11 +238,20 @@ class _FusedBlock(torch.autograd.Function):
                                epi=HF.EPI_NONE, out=d_z, seed_base=sb)
         dqkv = torch.empty_like(qkv)
         HF.attn_bwd(kind, qkv, d_o, dqkv, bits, thr, n_heads, shifted, (seeds[3], attn_p, sb) if attn_p > 0.0 else None)
+        if no_dx:
+            # qkv = (xhat g + b) Wqkv^T + bqkv with xhat = (x - m1) r1.  One dW launch with gamma = 1, beta = 0 gives
+            # G = dqkv^T xhat and dbqkv = colsum(dqkv); then, exactly (only the rounding order differs from the pass below),
+            #   dWqkv[i][j] = G[i][j] g[j] + dbqkv[i] b[j],  dg[j] = sum_i Wqkv[i][j] G[i][j],  db[j] = sum_i dbqkv[i] Wqkv[i][j]
+            # -- sums of 3d terms in index order (hwgat_ln_param_grads_from_g), the same bits every run.
+            g_qkv = parts[12].view(3 * d, d)
+            ones, zeros = HF.ln_identity(x.device, d)
+            dwq.run(lambda: HF.linear_tn(dqkv, x, g_qkv, dbqkv, ln=(m1, r1, ones, zeros), deterministic=det))
+            dwq.run(lambda: HF.ln_param_grads_from_g(g_qkv, dbqkv, wqkv, n1w, n1b, dwqkv, dn1w, dn1b))
+            dwq.join()
+            return (None, None, None, None, None, dn1w, dn1b, dwqkv, dbqkv, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2, None)
         if not xn_path:
             dwq.run(lambda: HF.linear_tn(dqkv, x, dwqkv, dbqkv, ln=(m1, r1, n1w, n1b), deterministic=det))
         d_xn = HF.linear_nt(dqkv, wT("wqkvT", wqkv), None, epi=HF.EPI_NONE, out=d_o)
-        # (the first block's input comes from the parameter-free embedding: its dx is still produced because
-        # dgamma / dbeta of norm1 fall out of the same LayerNorm-backward pass)
         dxm = None
         if ctx.send_up:           # the block that produced x gets dropmask3(its seed) * dx through the carrier's gradient
             if xn_path:

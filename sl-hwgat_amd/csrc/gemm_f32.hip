@@ -715,12 +715,14 @@ extern "C" int hwgat_linear_nt_f32(const float* A, const float* W, const float* 
 }
 
 static bool tn256_takes(int64_t M, int N, int K, float pro_p, const float* mean) {
-    return M % 32 == 0 && N % 256 == 0 && K % 256 == 0 && (int64_t)N * K > 256 * 256 && !(pro_p > 0.f && mean);
+    return M % 32 == 0 && N % 256 == 0 && K % 256 == 0 && (int64_t)N * K >= 256 * 256 && !(pro_p > 0.f && mean);
 }
 
 extern "C" int64_t hwgat_linear_tn_f32_ws_bytes(int64_t M, int N, int K) {
     if (hwgat_tn64_takes(N, K)) return hwgat_tn64_ws_bytes(M, N, K);          // 64x64 dW tiles (gemm_tn64.hip)
-    if (M <= 0 || N <= 0 || K <= 0 || !tn256_takes(M, N, K, 0.f, nullptr)) return 0;
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    if (hwgat_tnw_takes(M, N, K, 0.f, nullptr)) return hwgat_tnw_ws_floats(M, N, K) * 4;   // whole-weight tiles (gemm_f32_tnw.hip)
+    if (!tn256_takes(M, N, K, 0.f, nullptr)) return 0;
     return hwgat_tn256_ws_floats(M, N, K) * 4;
 }
 
@@ -734,9 +736,10 @@ extern "C" int hwgat_linear_tn_f32_ws(const float* A, const float* B, float* dW,
     if (hwgat_tn64_takes(N, K))
         return hwgat_tn64_run(HWGAT_F32, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base,
                               ws && ws_bytes >= hwgat_tn64_ws_bytes(M, N, K) ? ws : nullptr, ws_bytes, (hipStream_t)stream);
-    if (ws && ws_bytes > 0 && N % 128 == 0 && K % 128 == 0 && tn256_takes(M, N, K, pro_p, mean)) {
+    if (ws && ws_bytes > 0 && (hwgat_tnw_takes(M, N, K, pro_p, mean) || tn256_takes(M, N, K, pro_p, mean))) {
         TnArgs a{A, B, dW, db, mean, rstd, gamma, beta, M, N, K, 0, 0, pro_seed, pro_p, 0};
         a.seed_base = seed_base;
+        if (hwgat_tnw_takes(M, N, K, pro_p, mean)) return hwgat_launch_tnw(a, (hipStream_t)stream, ws, ws_bytes / 4);
         return hwgat_launch_tn256(a, (hipStream_t)stream, ws, ws_bytes / 4);
     }
     return hwgat_linear_tn_f32(A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, stream);
@@ -765,11 +768,12 @@ static int tn_f32_impl(const float* A, const float* B, float* dW, float* db, int
         if (pro_p > 0.f) return mean ? launch_tn<PRO_DROP, true, TnSmall, true>(t, st) : launch_tn<PRO_DROP, false, TnSmall, true>(t, st);
         return mean ? launch_tn<PRO_NONE, true, TnSmall, true>(t, st) : launch_tn<PRO_NONE, false, TnSmall, true>(t, st);
     }
-    // 256-aligned multi-tile outputs: the one-wave-per-SIMD 256x256 kernel with pinned MFMA/memory
+    // The narrow layers' weights (128 ... 384 wide): one workgroup per M slice holds the whole dW (gemm_f32_tnw.hip).
+    if (hwgat_tnw_takes(M, N, K, pro_p, mean)) return hwgat_launch_tnw(a, st);
+    // 256-aligned outputs: the one-wave-per-SIMD 256x256 kernel with pinned MFMA/memory
     // interleave (gemm_f32_tn256.hip; +2..8 % over the variants below, e.g. 131 vs 121-126 TF on
-    // 1536x512).  Single 256x256 outputs and everything else: 128x128 blocks, two per CU.
-    if (N % 256 == 0 && K % 256 == 0 && (int64_t)N * K > 256 * 256 && !(pro_p > 0.f && mean))
-        return hwgat_launch_tn256(a, st);
+    // 1536x512).  Everything else: 128x128 blocks, two per CU.
+    if (tn256_takes(M, N, K, pro_p, mean)) return hwgat_launch_tn256(a, st);
     if (pro_p > 0.f) return mean ? launch_tn<PRO_DROP, true, TnSmall>(a, st) : launch_tn<PRO_DROP, false, TnSmall>(a, st);
     return mean ? launch_tn<PRO_NONE, true, TnSmall>(a, st) : launch_tn<PRO_NONE, false, TnSmall>(a, st);
 }

@@ -674,3 +674,50 @@ extern "C" int hwgat_lnwpool_bwd_masked(const float* g, const float* wtok, const
 #undef SW
     HWGAT_LAUNCH_CHECK();
 }
+
+// ---- parameter gradients of a LayerNorm -> Linear pair from G = dY^T xhat (N x K) and db = colsum(dY) (N), for the block
+// whose input needs no gradient: no dX GEMM and no LayerNorm-backward pass over the tokens (see hwgat_ln_param_grads_from_g).
+// One workgroup per 32 columns: 8 row groups of consecutive rows, each summed in row order by one thread per column, the 8
+// partial sums then added in group order -- no atomics, the same bits every run.
+namespace {
+__global__ __launch_bounds__(256) void ln_param_grads_from_g_k(const float* __restrict__ G, const float* __restrict__ db,
+                                                               const float* __restrict__ W, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float* __restrict__ dW,
+                                                               float* __restrict__ dgamma, float* __restrict__ dbeta, int N,
+                                                               int K) {
+    __shared__ float red[2][8][32];
+    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int j = blockIdx.x * 32 + c;
+    const int per = (N + 7) / 8;
+    const int i0 = g * per, i1 = i0 + per < N ? i0 + per : N;
+    const float gj = gamma[j], bj = beta[j];
+    float sg = 0.f, sb = 0.f;
+#pragma unroll 8
+    for (int i = i0; i < i1; ++i) {
+        const int64_t at = (int64_t)i * K + j;
+        const float gv = G[at], w = W[at], d = db[i];
+        dW[at] += gv * gj + d * bj;
+        sg += w * gv;
+        sb += d * w;
+    }
+    red[0][g][c] = sg;
+    red[1][g][c] = sb;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int which = threadIdx.x >> 5;
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += red[which][q][c];
+        (which ? dbeta : dgamma)[j] += s;
+    }
+}
+}  // namespace
+
+extern "C" int hwgat_ln_param_grads_from_g(const float* G, const float* db, const float* W, const float* gamma,
+                                           const float* beta, float* dW, float* dgamma, float* dbeta, int N, int K,
+                                           void* stream) {
+    if (!G || !db || !W || !gamma || !beta || !dW || !dgamma || !dbeta || N <= 0 || K <= 0) return HWGAT_EINVAL;
+    if (K % 32) return HWGAT_ESHAPE;
+    ln_param_grads_from_g_k<<<K / 32, 256, 0, (hipStream_t)stream>>>(G, db, W, gamma, beta, dW, dgamma, dbeta, N, K);
+    HWGAT_LAUNCH_CHECK();
+}

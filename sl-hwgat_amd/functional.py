@@ -794,7 +794,7 @@ def linear_tn(A, Bm, dW, db=None, *, pro_seed=0, pro_p=0.0, ln=None, seed_base=N
             return
     mean, rstd, gamma, beta = ln if ln is not None else (None, None, None, None)
     if A.dtype == torch.float32:
-        # fp32, 256-aligned multi-tile outputs: slabs + fixed-order reduction as well (any prologue)
+        # fp32, 256-aligned outputs and the narrow layers' whole-weight tiles: slabs + fixed-order reduction as well (any prologue)
         need = _lib.lib().hwgat_linear_tn_f32_ws_bytes(M, N, K)
         if need > 0:
             ws = torch.empty(need // 4, device=A.device, dtype=torch.float32)
@@ -848,6 +848,32 @@ def ln_backward(dy, x, mean, rstd, gamma, dres, dgamma, dbeta, mask=None, beta=N
     call("hwgat_ln_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx),
          ptr(dgamma), ptr(dbeta), x.numel() // d, d, dtype_code(x), stream())
     return dx
+
+
+_LN_IDENTITY = {}
+
+
+def ln_identity(device, d):
+    """(ones, zeros) of width d, fp32: the gamma / beta with which a LayerNorm prologue yields the bare xhat.  Kept per
+    device and width; while a stream is being captured nothing is cached (a tensor from a graph's private pool must not
+    outlive the capture), the two fills become nodes of that graph instead."""
+    key = (device.type, device.index, d)
+    if key in _LN_IDENTITY:
+        return _LN_IDENTITY[key]
+    if torch.cuda.is_current_stream_capturing():
+        return torch.ones(d, device=device), torch.zeros(d, device=device)
+    # host tensors copied over: the copy has completed when .to() returns, so every stream may read them
+    pair = (torch.ones(d).to(device), torch.zeros(d).to(device))
+    _LN_IDENTITY[key] = pair
+    return pair
+
+
+def ln_param_grads_from_g(G, db, W, gamma, beta, dW, dgamma, dbeta):
+    """dW += G gamma + db (x) beta, dgamma += colsum(W * G), dbeta += db W, with G = dY^T xhat and db = colsum(dY): the
+    parameter gradients of a LayerNorm -> Linear pair whose input needs no gradient (hwgat_ln_param_grads_from_g)."""
+    N, K = dW.shape
+    call("hwgat_ln_param_grads_from_g", ptr(G), ptr(db), ptr(W), ptr(gamma), ptr(beta), ptr(dW), ptr(dgamma), ptr(dbeta),
+         N, K, stream())
 
 
 def dw_wants_xn(x):
