@@ -63,7 +63,8 @@ extern "C" {
  *         hwgat_dgcn_masked_sum
  *         later additions under the same number (additions only, no existing signature changed): hwgat_sce_{fwd,bwd}, the
  *         fused smoothed cross-entropy; hwgat_eval_accumulate, hwgat_eval_acc_bytes, the device-side evaluation accumulators;
- *         hwgat_ln_param_grads_from_g, the first block's norm1 / qkv parameter gradients without an input gradient */
+ *         hwgat_ln_param_grads_from_g, the first block's norm1 / qkv parameter gradients without an input gradient;
+ *         hwgat_optim_{set,advance,step}, Adam / AdamW over a device table with device-resident hyper-parameters */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -487,6 +488,46 @@ typedef struct {
     int32_t N, K, op, first_block;
 } hwgat_prep_entry;
 int hwgat_weight_prep(const hwgat_prep_entry* table, int n, int total_blocks, int dtype, void* stream);
+
+/* ---- Adam / AdamW for all parameter tensors of a model in one launch (reference: torch.optim.AdamW / Adam as
+ * hwgat/utils.py:71-82 builds them and utils.py:93-116 steps them; amsgrad = maximize = False).  Parameters, gradients
+ * and both moments are fp32.  Every value that changes between steps lives in DEVICE memory and is read when the kernels
+ * run, so the three launches below can be captured in a HIP graph and replayed under a learning-rate schedule.
+ *
+ * table: `n` entries in DEVICE memory, sorted by first_block; entry i owns workgroups [first_block, next entry's
+ *   first_block) of hwgat_optim_step, ceil(n_i / HWGAT_OPTIM_CHUNK) of them, workgroup b covering elements
+ *   [b * CHUNK, min(n_i, (b + 1) * CHUNK)).  `step` points at the tensor's own step count, one fp32 device word (torch's
+ *   state["step"] of a capturable optimizer); `group` selects the hyper-parameter block.  A tensor whose p, g, m and v are
+ *   all 16-byte aligned moves in 16-byte vectors, any other (e.g. a gradient that is a view into a flat bucket) element
+ *   by element; both give the same bits.
+ * hyper: HWGAT_OPTIM_NHYPER fp64 words per group: { lr, beta1, beta2, eps, weight_decay, coupled (0 = AdamW, decoupled
+ *   decay; 1 = Adam, decay added to the gradient), 0, 0 }.
+ * derived: HWGAT_OPTIM_NDERIVED fp32 words per table entry, scratch that hwgat_optim_advance writes and hwgat_optim_step
+ *   reads: the per-tensor scalars of the update rounded from fp64 once (lr wd, wd, 1 - beta1, beta2, 1 - beta2,
+ *   lr / (1 - beta1^t), sqrt(1 - beta2^t), eps).
+ *
+ * hwgat_optim_set:     one thread writes group `group` of `hyper` from the host doubles given as arguments (no copy, no
+ *                      host buffer: stream-ordered like hwgat_seed_set).  decoupled != 0: AdamW.
+ * hwgat_optim_advance: one thread per entry: *step += 1 (t), then the entry's derived block from its group's hyper block
+ *                      and t, in fp64.  A launch of its own: the workgroups of one entry must all see the same t.
+ * hwgat_optim_step:    for each element, in fp32 (fused multiply-adds as written, nothing else contracted):
+ *                        p = p - (lr wd) p                       AdamW   |   g = g + wd p    Adam
+ *                        m = m + (1 - beta1) (g - m)
+ *                        v = ((1 - beta2) g) g + beta2 v
+ *                        p = p - (lr / (1 - beta1^t)) (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ *                      total_blocks = the sum of the entries' workgroups.  No atomics, no reductions: bit-reproducible. */
+#define HWGAT_OPTIM_CHUNK 4096
+#define HWGAT_OPTIM_NHYPER 8
+#define HWGAT_OPTIM_NDERIVED 8
+typedef struct {
+    float* p; const float* g; float* m; float* v; float* step;
+    int64_t n;
+    int32_t group, first_block;
+} hwgat_optim_entry;
+int hwgat_optim_set(double* hyper, int group, double lr, double beta1, double beta2, double eps, double weight_decay,
+                    int decoupled, void* stream);
+int hwgat_optim_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived, void* stream);
+int hwgat_optim_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks, void* stream);
 
 /* the dropout mask the fused kernels use: out[i] = keep(seed, i) ? 1/(1-p) : 0 */
 int hwgat_dropout_mask_f32(float* out, int64_t n, uint32_t seed, float p, const uint32_t* seed_base, void* stream);

@@ -12,6 +12,7 @@ from . import functional
 from . import checkpoint
 from . import augment
 from . import evaluate
+from . import optim
 from .parts import part_table
 from .models.HWGATE import Model
 from .models.HGATE import Model as HGATEModel
@@ -26,4 +27,4 @@ from .models.model_params import (HWGATEParams, HGATEParams, WGATEParams, GATEPa
 __all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
            "TransformerModel",
            "TransformerParams", "STGCNModel", "STGCNParams", "DecoupledGCNModel", "DecoupledGCNParams", "functional",
-           "part_table", "_lib", "checkpoint", "augment", "evaluate"]
+           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim"]

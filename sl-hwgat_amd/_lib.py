@@ -19,7 +19,7 @@ _ERR = {-1: "HWGAT_EINVAL (null pointer / bad size)", -2: "HWGAT_ESHAPE (unsuppo
         -3: "HWGAT_EDTYPE (unknown dtype)"}
 
 _P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-_U, _F = ctypes.c_uint32, ctypes.c_float
+_U, _F, _D = ctypes.c_uint32, ctypes.c_float, ctypes.c_double
 _SIGS = {
     "hwgat_abi_version": [],
     "hwgat_is_lab_build": [],
@@ -127,6 +127,9 @@ _SIGS = {
     "hwgat_sce_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
     "hwgat_eval_acc_bytes": [_I, _I, _L],
     "hwgat_eval_accumulate": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _L, _P],
+    "hwgat_optim_set": [_P, _I, _D, _D, _D, _D, _D, _I, _P],
+    "hwgat_optim_advance": [_P, _I, _P, _P, _P],
+    "hwgat_optim_step": [_P, _I, _P, _I, _P],
 }
 _lib = None
 

@@ -19,8 +19,11 @@ import torch
 _LISTS = ("train_loss_list", "val_loss_list", "train_acc_list", "val_acc_list")
 
 
-def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused: Optional[bool] = None):
-    """utils.py:71-82 (configs.py:84: lr 5e-4, 'adamw').  `fused=True` selects torch's single-launch AdamW on a GPU."""
+def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused: Optional[bool] = None,
+                  device_step: bool = False):
+    """utils.py:71-82 (configs.py:84: lr 5e-4, 'adamw').  `fused=True` selects torch's single-launch AdamW on a GPU.
+    `device_step=True` returns optim.DeviceAdamW for 'adamw' / 'adam' (torch's defaults: weight decay 0.01 / 0), the HIP
+    optimizer that train.GraphedTrainStep captures inside its graph; 'nadam' / 'sgd' have no such kernels."""
     # ALL parameters, as the reference passes them (utils.py:76: model.parameters()): the frozen Fourier matrix `B`
     # is an nn.Parameter and therefore entry 0 of the param group, so optimizer_state_dict files interchange with the
     # reference's AdamW (param-group sizes must match).  AdamW skips parameters whose grad is None: B gets no update.
@@ -28,6 +31,12 @@ def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused:
     kinds = {"adamw": torch.optim.AdamW, "adam": torch.optim.Adam, "nadam": torch.optim.NAdam, "sgd": torch.optim.SGD}
     if optimizer_type not in kinds:
         raise ValueError(f"optimizer_type {optimizer_type!r}: one of {sorted(kinds)}")
+    if device_step:
+        if optimizer_type not in ("adamw", "adam"):
+            raise ValueError(f"device_step=True: optimizer_type {optimizer_type!r} has no HIP kernels ('adamw' or 'adam')")
+        from .optim import DeviceAdamW
+        adamw = optimizer_type == "adamw"
+        return DeviceAdamW(params, lr=lr, weight_decay=1e-2 if adamw else 0.0, decoupled_weight_decay=adamw)
     kw = {"fused": fused} if fused is not None and optimizer_type in ("adamw", "adam") else {}
     return kinds[optimizer_type](params, lr=lr, **kw)
 

@@ -91,8 +91,8 @@ class TrainStep:
 
 
 class GraphedTrainStep:
-    """The train step -- seed advance, forward, loss, backward -- captured ONCE in a HIP graph and replayed per call, the
-    fused AdamW step issued right after the replay: a few launches instead of ~400 issued one by one from Python
+    """The train step -- seed advance, forward, loss, backward and, with an `optim.DeviceAdamW`, the optimizer step --
+    captured ONCE in a HIP graph and replayed per call: one graph launch instead of ~400 kernels issued one by one from Python
     (reference loop: hwgat/utils.py:93-116, which issues its ~40 ATen ops per block the same way).  Why it matters here: the bf16 steps
     of the sibling models are 10-17 ms, within 10 % of what one Python thread can issue, and a node runs 8 such ranks
     (SURVEY 8e); a replay needs no host work between kernels.
@@ -104,12 +104,19 @@ class GraphedTrainStep:
     records it like torch's own kernels.  Capture follows the torch.cuda.graphs recipe (warm-up on a side stream, then
     `torch.cuda.graph`), in THIS process: nothing is re-launched or exec'ed.
 
-    The optimizer step stays out of the graph so that it reads the param groups' hyper-parameters when it runs: a float
-    lr captured in the graph would be frozen there (an lr scheduler would change nothing), and a tensor lr is read by
-    torch's fused AdamW as float32 -- the float lr rounded, updates that differ from the eager step's.  Out of the graph
-    it is the eager step's own call on the gradients the replay wrote, so a replay and an eager TrainStep step agree bit
-    for bit under `deterministic_train`, with any scheduler.  The optimizer must be AdamW / Adam(fused=True,
-    capturable=True): its step counts live on the device, and nothing in the step waits on the host.
+    The optimizer.  With `optim.DeviceAdamW` the step is two more nodes of the graph (hwgat_optim_advance,
+    hwgat_optim_step): its hyper-parameters are fp64 device words that the kernels read when they run, so `__call__` only
+    pushes the param groups' values when they changed (hwgat_optim_set, one tiny launch, e.g. after `scheduler.step()`) and
+    replays; the optimizer's Python `step` is not entered, and a replay is the whole train step.  The kernels and their
+    inputs are the eager step's, so a replay and an eager TrainStep step agree bit for bit under `deterministic_train`,
+    with any scheduler (tests/test_gpu_optim.py).
+
+    With any other optimizer the step stays out of the graph and is issued right after the replay, so that it reads the
+    param groups' hyper-parameters when it runs: a float lr captured in the graph would be frozen there (an lr scheduler
+    would change nothing), and a tensor lr is read by torch's fused AdamW as float32 -- the float lr rounded, updates that
+    differ from the eager step's.  Out of the graph it is the eager step's own call on the gradients the replay wrote,
+    so the same bit-equality holds.  That optimizer must be AdamW / Adam(fused=True, capturable=True): its step counts
+    live on the device, and nothing in the step waits on the host.
 
     Inputs are copied into static buffers; `loss` / `correct` are static device tensors rewritten by every replay.
     Shapes are fixed at capture.  Parameters must not be reallocated afterwards (same rule as serve.GraphedEval).
@@ -128,6 +135,7 @@ class GraphedTrainStep:
             if not grp.get("capturable", False):
                 raise ValueError("the optimizer must be built with capturable=True (its step count then lives on the device)")
         self.model, self.opt, self.reducer = model, optimizer, reducer
+        self.in_graph = isinstance(optimizer, importlib.import_module(__package__ + ".optim").DeviceAdamW)
         self.criterion = criterion or SmoothedCrossEntropyLoss()
         self.x, self.y = x.detach().clone(), y.detach().clone()
         start = int(model._drop_calls)
@@ -156,8 +164,15 @@ class GraphedTrainStep:
         model.device_seed_counter = True                 # from here on the device counts the steps itself
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
-            self.loss, self.correct = self._one(step=False)
+        if self.in_graph:
+            optimizer.push_hyper()
+            optimizer.begin_capture()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.loss, self.correct = self._one(step=self.in_graph)
+        finally:
+            # the table the captured optimizer launches read: uploaded now (capture executed nothing), owned by this object
+            self._opt_table = optimizer.end_capture() if self.in_graph else None
         # capture executed nothing: put the device counter where the host mirror says the caller left it
         model._drop_calls = start
         HF.seed_set(model._seed_state, start, torch.initial_seed(), getattr(model, "rank_salt", 0))
@@ -191,10 +206,15 @@ class GraphedTrainStep:
             self.x.copy_(x, non_blocking=True)
         if y.data_ptr() != self.y.data_ptr():
             self.y.copy_(y, non_blocking=True)
+        if self.in_graph:
+            self.opt.push_hyper()                        # launches only when a param group's values changed
         self.graph.replay()
         self.model._drop_calls += 1                      # host mirror of the device counter (model._seeds() in tests)
         for p, g in self._grads:
             if p.grad is not g:
                 p.grad = g
-        self.opt.step()                                  # on the gradients the replay wrote, with the current lr
+        if self.in_graph:
+            self.opt._opt_called = True                  # what torch's LR schedulers look for before their first step
+        else:
+            self.opt.step()                              # on the gradients the replay wrote, with the current lr
         return self.loss
