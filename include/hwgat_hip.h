@@ -64,7 +64,8 @@ extern "C" {
  *         later additions under the same number (additions only, no existing signature changed): hwgat_sce_{fwd,bwd}, the
  *         fused smoothed cross-entropy; hwgat_eval_accumulate, hwgat_eval_acc_bytes, the device-side evaluation accumulators;
  *         hwgat_ln_param_grads_from_g, the first block's norm1 / qkv parameter gradients without an input gradient;
- *         hwgat_optim_{set,advance,step}, Adam / AdamW over a device table with device-resident hyper-parameters */
+ *         hwgat_optim_{set,advance,step}, Adam / AdamW over a device table with device-resident hyper-parameters;
+ *         hwgat_head_{fwd,bwd_dx,bwd_dw}, the classifier head */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -765,6 +766,25 @@ int64_t hwgat_eval_acc_bytes(int C, int k_max, int64_t cap);
 int hwgat_eval_accumulate(void* acc, const float* row_loss, const int32_t* rank, const int32_t* pred,
                           const int64_t* target, const float* loss, const int32_t* n_valid, int64_t B, int C, int k_max,
                           int64_t cap, void* stream);
+
+/* ---- the classifier head (csrc/head.hip; reference: the `head` / `classifier` nn.Linear of every model,
+ * hwgat/models/HWGATE.py:331,372).  Everything fp32 and row-major; W is (N, K) as nn.Linear stores it.
+ *   hwgat_head_fwd:    Y[M, N]  = X[M, K] W^T + bias      (bias may be NULL: no bias)
+ *   hwgat_head_bwd_dx: dX[M, K] = dY[M, N] W
+ *   hwgat_head_bwd_dw: dW[N, K] = dY^T X,  db[N] = column sums of dY      (db may be NULL: not computed)
+ * Shapes: M >= 1 rows (the batch), 1 <= N <= 65536 classes (the range of hwgat_sce_fwd), K % 64 == 0 and 64 <= K <= 1024
+ * (every stage width of the models); anything else HWGAT_ESHAPE.  A NULL required pointer, a non-positive M or N, or an
+ * X, W, dX or dW that is not 16-byte aligned (those are read and written 16 bytes at a time; Y, dY, bias and db need
+ * 4) is HWGAT_EINVAL.  Both are decided before any HIP call.
+ * Outputs are overwritten, never accumulated into: nothing needs zeroing, there is no workspace and no state.  Nothing
+ * outside [0, M) x [0, N) of Y (and likewise of the other outputs) is written.
+ * Exact fp32 on v_mfma_f32_16x16x4_f32, no float atomic.  Each output element is summed in a fixed order that depends
+ * only on the length of its reduction (K for Y, N for dX, M for dW and db): row m of Y is a function of X[m, :], W and
+ * bias alone and has the same bits in a batch of 64 as in a batch of 1 (dX and dY likewise), and two runs are bit-equal.
+ * Non-finite inputs propagate as in the dense product; no part of a product is skipped for what an operand holds. */
+int hwgat_head_fwd(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, void* stream);
+int hwgat_head_bwd_dx(const float* dY, const float* W, float* dX, int M, int N, int K, void* stream);
+int hwgat_head_bwd_dw(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, void* stream);
 
 #ifdef __cplusplus
 }

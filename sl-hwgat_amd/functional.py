@@ -1357,3 +1357,106 @@ def smooth_ce(logits, target, eps, n_valid=None):
     """(loss, rank, pred): the batch-mean smoothed cross-entropy as an autograd node (forward two launches, backward one),
     with the detached rank of the target in a stable descending sort and the arg-max (both int32)"""
     return _SmoothCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_valid)
+
+
+# ---------------------------------------------------------------- the classifier head (csrc/head.hip)
+# logits = feat W^T + bias on the project's own kernels: exact fp32, fixed summation order, so a clip's logits have the same
+# bits at any batch size.  Opt-in per model (`model.hip_head = True`, seeding.DeviceSeeds._classify).
+HEAD_K_STEP, HEAD_K_MAX, HEAD_N_MAX = 64, 1024, 65536
+
+
+def head_supported(K):
+    """the feature widths the head kernels take: every multiple of 64 from 64 to 1024"""
+    return HEAD_K_STEP <= int(K) <= HEAD_K_MAX and int(K) % HEAD_K_STEP == 0
+
+
+def _head_check(rows, weight, what):
+    """`rows` is feat (B, K) or the logits' gradient (B, N); returns (B, N, K)"""
+    for name, t in ((what, rows), ("weight", weight)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"head: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"head: {name} must be fp32, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"head: {name} must be 2-d, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"head: {name} must be contiguous")
+    N, K = weight.shape
+    if rows.shape[1] != (K if what == "feat" else N):
+        raise ValueError(f"head: {what} {tuple(rows.shape)} does not match weight (N, K) = {tuple(weight.shape)}")
+    if rows.shape[0] < 1 or not 1 <= N <= HEAD_N_MAX:
+        raise ValueError(f"head: needs at least one row and 1..{HEAD_N_MAX} classes, got {rows.shape[0]} rows, {N} classes")
+    if not head_supported(K):
+        raise ValueError(f"head: K = {K} features: the kernels take multiples of {HEAD_K_STEP} up to {HEAD_K_MAX}")
+    return rows.shape[0], N, K
+
+
+def _head_out(out, shape, like, name):
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"head: {name} must be a contiguous fp32 {tuple(shape)} tensor")
+    return out
+
+
+def head_forward(feat, weight, bias=None, out=None):
+    """feat (B, K) @ weight (N, K)^T + bias (N,) -> (B, N); one launch"""
+    B, N, K = _head_check(feat, weight, "feat")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (N,)):
+        raise ValueError(f"head: bias must be fp32 ({N},), got {bias.dtype} {tuple(bias.shape)}")
+    y = _head_out(out, (B, N), feat, "out")
+    call("hwgat_head_fwd", ptr(feat), ptr(weight), ptr(bias), ptr(y), B, N, K, stream())
+    return y
+
+
+def head_backward_dx(dy, weight, out=None):
+    """dy (B, N) @ weight (N, K) -> (B, K); one launch"""
+    B, N, K = _head_check(dy, weight, "dy")
+    dx = _head_out(out, (B, K), dy, "out")
+    call("hwgat_head_bwd_dx", ptr(dy), ptr(weight), ptr(dx), B, N, K, stream())
+    return dx
+
+
+def head_backward_dw(dy, feat, want_db=True, out=None, out_db=None):
+    """(dy (B, N)^T @ feat (B, K) -> (N, K), the column sums of dy -> (N,) or None); one launch for both"""
+    for name, t in (("dy", dy), ("feat", feat)):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"head: {name} must be a contiguous fp32 matrix")
+    if dy.shape[0] != feat.shape[0]:
+        raise ValueError(f"head: dy {tuple(dy.shape)} and feat {tuple(feat.shape)} differ in rows")
+    (B, N), K = dy.shape, feat.shape[1]
+    if B < 1 or not 1 <= N <= HEAD_N_MAX or not head_supported(K):
+        raise ValueError(f"head: unsupported gradient shape B = {B}, N = {N}, K = {K}")
+    dw = _head_out(out, (N, K), dy, "out")
+    db = _head_out(out_db, (N,), dy, "out_db") if want_db else None
+    call("hwgat_head_bwd_dw", ptr(dy), ptr(feat), ptr(dw), ptr(db), B, N, K, stream())
+    return dw, db
+
+
+class _HeadLinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, weight, bias):
+        ctx.save_for_backward(feat, weight)
+        ctx.has_bias = bias is not None
+        return head_forward(feat, weight, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        feat, weight = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = head_backward_dx(dy, weight) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = head_backward_dw(dy, feat, want_db=ctx.has_bias and ctx.needs_input_grad[2])
+        return dx, (dw if ctx.needs_input_grad[1] else None), db
+
+
+def head_linear(feat, weight, bias=None):
+    """the classifier head as ONE autograd node: forward one launch (hwgat_head_fwd); backward hwgat_head_bwd_dw for the
+    weight and bias gradients together and hwgat_head_bwd_dx only when `feat` needs a gradient.  feat (B, K) fp32
+    contiguous on the device, weight (N, K) fp32, bias (N,) fp32 or None; the gradients are fresh contiguous fp32
+    tensors that autograd accumulates as it does nn.Linear's."""
+    _head_check(feat, weight, "feat")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],)):
+        raise ValueError(f"head: bias must be an fp32 ({weight.shape[0]},) tensor or None")
+    return _HeadLinear.apply(feat, weight, bias)

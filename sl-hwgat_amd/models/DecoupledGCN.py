@@ -257,4 +257,4 @@ class Model(DeviceSeeds, nn.Module):
         return mean_pool(h.view(N, -1, h.shape[-1]), p, self._site_seeds(HEAD_SITE)[0], seed_base)
 
     def forward(self, x, keep_prob=0.9):
-        return self.head.classifier(self.forward_features(x, keep_prob))
+        return self._classify(self.head.classifier, self.forward_features(x, keep_prob))

@@ -184,4 +184,4 @@ class Model(DeviceSeeds, nn.Module):
         return mean_pool(h.view(N, -1, h.shape[-1]), p, self._site_seeds(HEAD_SITE)[0], seed_base)
 
     def forward(self, x):
-        return self.head.classifier(self.forward_features(x))
+        return self._classify(self.head.classifier, self.forward_features(x))

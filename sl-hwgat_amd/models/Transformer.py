@@ -150,7 +150,7 @@ class Model(DeviceSeeds, nn.Module):
         return hn.reshape(B, T * self.d_model).float()
 
     def forward(self, src):
-        return self.classifier(self.forward_features(src))
+        return self._classify(self.classifier, self.forward_features(src))
 
 
 class _Embed(torch.autograd.Function):

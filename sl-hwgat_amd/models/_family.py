@@ -210,4 +210,4 @@ class FamilyModel(DeviceSeeds, nn.Module):
 
     def forward(self, x):
         feat = self.forward_features(x)
-        return self.head(feat)
+        return self._classify(self.head, feat)

@@ -9,6 +9,7 @@ fallbacks; train.TrainStep, train.GraphedTrainStep and serve.GraphedEval use `_s
 `device_seed_counter`.
 """
 import torch
+from torch import nn
 
 from . import functional as HF
 
@@ -23,6 +24,7 @@ class DeviceSeeds:
         self._call_base = None                                    # the latest train forward's copy of the base seed
         self.deterministic_eval = True                            # eval(): fixed-order sums, bit-reproducible logits
         self.deterministic_train = False                          # train(): the same for the whole step (slower: no float atomics anywhere)
+        self.hip_head = False                                     # True: the classifier nn.Linear runs on csrc/head.hip (_classify)
 
     def _site_seeds(self, k):
         """four dropout-SITE seeds of block k (host integers that never change): proj, fc1, fc2 outputs
@@ -67,3 +69,12 @@ class DeviceSeeds:
         (`deterministic_train = True`: fixed-order row statistics, pooled sum and parameter gradients -- the reference's
         single-device training repeats itself bit for bit with fixed seeds, this is the mode that does the same)"""
         return bool(self.deterministic_train if self.training else self.deterministic_eval)
+
+    def _classify(self, linear, feat):
+        """the model's last layer.  With `hip_head` set, an nn.Linear whose width the head kernels take
+        (functional.head_supported) runs on them: exact fp32 in a fixed order, so a clip's logits do not depend on the
+        batch it came in.  Everything else -- the switch off (the default), nn.Identity for num_classes == 0, the
+        Transformer's nn.Sequential 'concat' head -- is the module call it has always been."""
+        if self.hip_head and isinstance(linear, nn.Linear) and HF.head_supported(linear.in_features):
+            return HF.head_linear(feat, linear.weight, linear.bias)
+        return linear(feat)

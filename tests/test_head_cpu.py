@@ -1,0 +1,152 @@
+"""CPU: the opt-in HIP classifier head (csrc/head.hip; reference: the `head` / `classifier` nn.Linear of every model,
+hwgat/models/HWGATE.py:331,372) -- header <-> bindings <-> exports of the three entry points, their argument checks
+(decided on the host before any HIP call), the `hip_head` switch of every model (off by default), the routing of
+`DeviceSeeds._classify`, and the refusals of functional.head_linear that need no device."""
+import ctypes
+import importlib
+
+import pytest
+import torch
+from torch import nn
+
+hw = importlib.import_module("sl-hwgat_amd")
+seeding = importlib.import_module("sl-hwgat_amd.seeding")
+HF = hw.functional
+CPU = torch.device("cpu")
+HEAD_SYMBOLS = {"hwgat_head_fwd", "hwgat_head_bwd_dx", "hwgat_head_bwd_dw"}
+EINVAL, ESHAPE = -1, -2
+MODELS = {"hwgate": (hw.Model, hw.HWGATEParams), "hgate": (hw.HGATEModel, hw.HGATEParams),
+          "wgate": (hw.WGATEModel, hw.WGATEParams), "gate": (hw.GATEModel, hw.GATEParams),
+          "transformer": (hw.TransformerModel, hw.TransformerParams), "stgcn": (hw.STGCNModel, hw.STGCNParams),
+          "dgcn": (hw.DecoupledGCNModel, hw.DecoupledGCNParams)}
+
+
+def _build(name):
+    """the small configuration of tests/test_family_cpu.py"""
+    Model, Params = MODELS[name]
+    hp = Params({"src_len": 32, "num_class": 7}, 2, CPU)
+    if name in ("hwgate", "hgate", "wgate", "gate"):
+        hp.embed_dim = 128
+    return Model(*hp.get_model_params())
+
+
+def test_entry_points_declared_bound_and_exported():
+    assert HEAD_SYMBOLS <= set(hw._lib.declared_symbols())
+    assert HEAD_SYMBOLS == {n for n in hw._lib._SIGS if n.startswith("hwgat_head_")}
+    handle = hw._lib.lib()
+    for n in HEAD_SYMBOLS:
+        assert getattr(handle, n) is not None
+    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4006
+
+
+def _calls():
+    """(entry point, its pointer arguments' count, the indices of the required ones); the pointers are never read"""
+    L = hw._lib.lib()
+    return [(L.hwgat_head_fwd, 4, (0, 1, 3)),           # X, W, bias (optional), Y
+            (L.hwgat_head_bwd_dx, 3, (0, 1, 2)),        # dY, W, dX
+            (L.hwgat_head_bwd_dw, 4, (0, 1, 2))]        # dY, X, dW, db (optional)
+
+
+def test_arguments_are_refused_before_any_hip_call():
+    buf = ctypes.create_string_buffer(128)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)            # 16-byte aligned, as a device allocation is
+    for fn, nptr, required in _calls():
+        assert fn(*([None] * nptr), 4, 10, 64, None) == EINVAL
+        for hole in required:
+            args = [p] * nptr
+            args[hole] = None
+            assert fn(*args, 4, 10, 64, None) == EINVAL, (fn.__name__, hole)
+        for M, N in ((0, 10), (-2, 10), (4, 0), (4, -1)):
+            assert fn(*([p] * nptr), M, N, 64, None) == EINVAL, (fn.__name__, M, N)
+        for K in (96, 32, 1088, 0, -64):
+            assert fn(*([p] * nptr), 4, 10, K, None) == ESHAPE, (fn.__name__, K)
+        assert fn(*([p] * nptr), 4, 65537, 64, None) == ESHAPE, fn.__name__
+        # an optional pointer that is NULL is not what gets a call refused: the shape still decides
+        optional = [i for i in range(nptr) if i not in required]
+        for hole in optional:
+            args = [p] * nptr
+            args[hole] = None
+            assert fn(*args, 4, 10, 96, None) == ESHAPE, (fn.__name__, hole)
+            assert fn(*args, 4, 65537, 64, None) == ESHAPE, (fn.__name__, hole)
+
+
+def test_misaligned_vector_operands_are_refused():
+    """X, W, dX and dW are read and written 16 bytes at a time"""
+    buf = ctypes.create_string_buffer(128)
+    base = (ctypes.addressof(buf) + 15) & ~15
+    p, odd = ctypes.c_void_p(base), ctypes.c_void_p(base + 4)
+    L = hw._lib.lib()
+    assert L.hwgat_head_fwd(odd, p, p, p, 4, 10, 64, None) == EINVAL
+    assert L.hwgat_head_fwd(p, odd, p, p, 4, 10, 64, None) == EINVAL
+    assert L.hwgat_head_bwd_dx(p, odd, p, 4, 10, 64, None) == EINVAL
+    assert L.hwgat_head_bwd_dx(p, p, odd, 4, 10, 64, None) == EINVAL
+    assert L.hwgat_head_bwd_dw(p, odd, p, p, 4, 10, 64, None) == EINVAL
+    assert L.hwgat_head_bwd_dw(p, p, odd, p, 4, 10, 64, None) == EINVAL
+
+
+@pytest.mark.parametrize("name", list(MODELS))
+def test_switch_is_off_on_a_fresh_model(name):
+    model = _build(name)
+    assert model.hip_head is False
+    assert "hip_head" in vars(model) and "hip_head" not in vars(seeding.DeviceSeeds)
+
+
+def test_head_supported_states_the_width_rule():
+    assert all(HF.head_supported(K) for K in (64, 448, 1024))
+    assert not any(HF.head_supported(K) for K in (32, 96, 1088, 0))
+
+
+def _refuse(*a, **k):
+    raise AssertionError("functional.head_linear must not be reached")
+
+
+def test_classify_off_calls_the_module(monkeypatch):
+    monkeypatch.setattr(HF, "head_linear", _refuse)
+    model = _build("hwgate")
+    lin = nn.Linear(64, 5)
+    feat = torch.randn(3, 64)
+    assert torch.equal(model._classify(lin, feat), lin(feat))
+
+
+def test_classify_on_has_no_cpu_fallback():
+    model = _build("stgcn")
+    model.hip_head = True
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        model._classify(nn.Linear(64, 5), torch.randn(3, 64))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        model._classify(nn.Linear(64, 5, bias=False), torch.randn(3, 64))
+
+
+def test_classify_on_keeps_what_is_not_a_supported_linear_on_the_module(monkeypatch):
+    monkeypatch.setattr(HF, "head_linear", _refuse)
+    model = _build("transformer")
+    model.hip_head = True
+    feat = torch.randn(3, 96)
+    assert model._classify(nn.Identity(), feat) is feat                         # num_classes == 0
+    seq = nn.Sequential(nn.Linear(96, 4))                                       # the Transformer's 'concat' head
+    assert torch.equal(model._classify(seq, feat), seq(feat))
+    lin = nn.Linear(96, 4)                                                      # a width the kernels do not take
+    assert torch.equal(model._classify(lin, feat), lin(feat))
+    feat64 = torch.randn(3, 64)
+    seq64 = nn.Sequential(nn.Linear(64, 4))                                     # a Sequential stays one at any width
+    assert torch.equal(model._classify(seq64, feat64), seq64(feat64))
+
+
+def test_head_linear_input_checks():
+    w, b = torch.randn(5, 64), torch.randn(5)
+    with pytest.raises(TypeError, match="fp32"):
+        HF.head_linear(torch.randn(3, 64).bfloat16(), w, b)
+    with pytest.raises(ValueError, match="contiguous"):
+        HF.head_linear(torch.randn(64, 3).t(), w, b)
+    with pytest.raises(ValueError, match="does not match"):
+        HF.head_linear(torch.randn(3, 128), w, b)
+    with pytest.raises(ValueError, match="2-d"):
+        HF.head_linear(torch.randn(3, 2, 64), w, b)
+    with pytest.raises(ValueError, match="bias"):
+        HF.head_linear(torch.randn(3, 64), w, torch.randn(4))
+    with pytest.raises(ValueError, match="multiples of 64"):
+        HF.head_linear(torch.randn(3, 96), torch.randn(5, 96), b)
+    with pytest.raises(TypeError, match="fp32"):
+        HF.head_linear(torch.randn(3, 64), w.double(), b)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):                  # and never torch arithmetic instead
+        HF.head_linear(torch.randn(3, 64), w, b)
