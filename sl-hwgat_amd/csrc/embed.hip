@@ -43,7 +43,9 @@ __global__ __launch_bounds__(256) void embed_fwd_k(const float* __restrict__ x, 
             const float* xrow = x + bt * J * C;
             T* orow = out + bt * K * (int64_t)d0;
             float pes = 0.f, pec = 0.f;
-            if (pe) { pes = pe[t * d0 + m]; pec = pe[t * d0 + half + m]; }
+            // (lanes past `half` of a ragged last trip -- d0 = 64, 192, 320, ... -- would read past the row, and on the last
+            // frame past the (T, d0) table)
+            if (pe && act) { pes = pe[t * d0 + m]; pec = pe[t * d0 + half + m]; }
 #pragma unroll 4
             for (int k = 0; k < K; ++k) {
                 const int j = idx ? idx[k] : k;

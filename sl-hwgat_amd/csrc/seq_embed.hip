@@ -7,7 +7,7 @@
 // hwgat_seq_embed_bwd: dW[n,f] = sum_m g[m,n] x[m,f], db[n] = sum_m g[m,n] with g = dout * mask * sqrt(d): per-split
 //   images of 64 columns x all F over a fixed row range each, then added in split order -- no atomics, bit-reproducible.
 // hwgat_seq_maxpool_fwd / _bwd: max over T of (B, T, d) -> (B, d) fp32 with the first index of the maximum (as
-//   torch.max), and its backward (the gradient lands on that index only).
+//   torch.max: a NaN is the maximum, at the first NaN's index), and its backward (the gradient lands on that index only).
 #include "common.h"
 #include "fused_ops.h"
 
@@ -147,7 +147,8 @@ __global__ __launch_bounds__(256) void seq_maxpool_fwd_k(const T* __restrict__ x
     int bi = 0;
     for (int t = 1; t < Tn; ++t) {
         const float v = io<T>::ld(src + (int64_t)t * d);
-        if (v > best) { best = v; bi = t; }
+        // a NaN wins over every number and the first NaN keeps its place, as in torch.max
+        if (v > best || (v != v && best == best)) { best = v; bi = t; }
     }
     out[g] = best;
     idx[g] = bi;
