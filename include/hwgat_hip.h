@@ -358,6 +358,8 @@ int hwgat_unmerge_masked(const void* in, void* out, void* out_masked, int B, int
  *   on 128x64 tiles, every pro / epi code; the _ex statistics / merged store are not built for it (HWGAT_ESHAPE).
  *   pro: 0 none | 1 LayerNorm: (A-mean[m])*rstd[m]*gamma[k]+beta[k] | 2 dropout mask on A
  *        (keep-scale 1/(1-pro_p), element index m*K+k, seed pro_seed)
+ *        (pro 2 with pro_p == 0 is pro 0, fp32 and bf16 alike: it is rewritten BEFORE the arguments are checked, so
+ *        an eval-mode call may carry it where a rule below says "pro 0 only")
  *        | 3 folded LayerNorm (hwgat_ln_fold below): A is the un-normalised input, W = W o gamma, gamma = s[N],
  *        beta = c[N], bias ignored; the epilogue forms rstd[m] (acc - mean[m] s[n]) + c[n] -- the value of pro 1 up
  *        to rounding, with the per-element normalisation out of the load path; epi 0 or 2 only, M % 128 == 0

@@ -17,8 +17,9 @@
 #include <stdlib.h>
 #include "common.h"
 #include "fused_ops.h"
+#include <type_traits>
 #include "gemm_bf16.h"
-#include "gemm_tn64.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -505,84 +506,27 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_bf16_k(TnArgsB p) {
     }
 }
 
-template <int PRO, typename C, bool RAGGED = false>
-int launch_nt_b(const NtArgsB& a, int epi, hipStream_t st, bool fold = false) {
-    const int64_t tiles = ((a.M + C::BM - 1) / C::BM) * (a.N / C::BN);
-    const int grid = (int)(tiles < C::SLOTS ? tiles : C::SLOTS);
-    if (fold) {                                                 // PRO_LN_FOLD: plain loaders, row-affine epilogue
-        if constexpr (PRO == PRO_NONE) {
-            if (epi == EPI_BIAS) gemm_nt_bf16_k<PRO_NONE, EPI_BIAS, C, RAGGED, X_LNFOLD><<<grid, C::THREADS, 0, st>>>(a);
-            else if (epi == EPI_BIAS_GELU_DROP) gemm_nt_bf16_k<PRO_NONE, EPI_BIAS_GELU_DROP, C, RAGGED, X_LNFOLD><<<grid, C::THREADS, 0, st>>>(a);
-            else if (epi == EPI_BIAS_GELU_DROP_G) gemm_nt_bf16_k<PRO_NONE, EPI_BIAS_GELU_DROP_G, C, RAGGED, X_LNFOLD><<<grid, C::THREADS, 0, st>>>(a);
-            else return HWGAT_EINVAL;
+// the bf16 family for the shared validation and routing (gemm_dispatch.h)
+struct NtBf16 {
+    using T = bf16_t;
+    static constexpr int K_GRANULE = 64;
+    using Tile = NtB64;
+    using Heavy = NtB64;                                        // no K16 tile: see the alternatives measured at NtB64
+    using N64 = NtB64N64;
+    template <typename C, bool RAGGED>
+    static int launch(const NtArgsB& a, int pro, int epi, hipStream_t st) {
+        const int64_t tiles = ((a.M + C::BM - 1) / C::BM) * (a.N / C::BN);
+        const int grid = (int)(tiles < C::SLOTS ? tiles : C::SLOTS);
+        return nt_dispatch<true, !RAGGED>(pro, epi, a.stat_sum != nullptr, a.mg_K > 0, [&](auto p, auto e, auto x) {
+            gemm_nt_bf16_k<decltype(p)::value, decltype(e)::value, C, RAGGED, decltype(x)::value><<<grid, C::THREADS, 0, st>>>(a);
             HWGAT_LAUNCH_CHECK();
-        }
-        return HWGAT_EINVAL;
+        });
     }
-    if (a.stat_sum != nullptr) {                                // validated by the caller: PRO_NONE, EPI_BIAS_DROP_RES, whole tiles
-        if constexpr (PRO == PRO_NONE && !RAGGED) {
-            if (a.mg_K > 0) gemm_nt_bf16_k<PRO_NONE, EPI_BIAS_DROP_RES, C, false, 2><<<grid, C::THREADS, 0, st>>>(a);
-            else gemm_nt_bf16_k<PRO_NONE, EPI_BIAS_DROP_RES, C, false, 1><<<grid, C::THREADS, 0, st>>>(a);
-            HWGAT_LAUNCH_CHECK();
-        }
-        return HWGAT_EINVAL;
+    // the eight-wave LDS-DMA kernel (gemm_bf16_nt8w.hip) where it applies, else the one-wave-per-SIMD kernel
+    static int launch256(const NtArgsB& b, int pro, int epi, hipStream_t st) {
+        return hwgat_nt8w_bf16_takes(b, pro, epi) ? hwgat_launch_nt8w_bf16(b, pro, epi, st) : hwgat_launch_nt256_bf16(b, pro, epi, st);
     }
-    switch (epi) {
-        case EPI_BIAS: gemm_nt_bf16_k<PRO, EPI_BIAS, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_DROP_RES: gemm_nt_bf16_k<PRO, EPI_BIAS_DROP_RES, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_GELU_DROP: gemm_nt_bf16_k<PRO, EPI_BIAS_GELU_DROP, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_GELU_BWD: gemm_nt_bf16_k<PRO, EPI_GELU_BWD, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_GELU_DROP_G: gemm_nt_bf16_k<PRO, EPI_BIAS_GELU_DROP_G, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_MUL_AUX: gemm_nt_bf16_k<PRO, EPI_MUL_AUX, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_NONE: gemm_nt_bf16_k<PRO, EPI_NONE, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_RELU_DROP:
-            if constexpr (PRO == PRO_NONE) { gemm_nt_bf16_k<PRO_NONE, EPI_BIAS_RELU_DROP, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
-            return HWGAT_EINVAL;
-        case EPI_RELU_BWD:
-            if constexpr (PRO == PRO_NONE) { gemm_nt_bf16_k<PRO_NONE, EPI_RELU_BWD, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
-            return HWGAT_EINVAL;
-        default: return HWGAT_EINVAL;
-    }
-    HWGAT_LAUNCH_CHECK();
-}
-
-// the same launch restricted to rows [r0, r0 + rows) of every M-indexed operand
-NtArgsB nt_rows_b(NtArgsB a, int64_t r0, int64_t rows) {
-    a.A += r0 * a.K;
-    a.C += r0 * a.N;
-    if (a.C2) a.C2 += r0 * a.N;
-    if (a.res) a.res += r0 * a.N;
-    if (a.aux) a.aux += r0 * a.N;
-    if (a.mean) { a.mean += r0; a.rstd += r0; }
-    a.M = rows;
-    a.row0 = r0;
-    return a;
-}
-
-// N % 128 == 64: the 128x64 tile over the whole 128-row blocks, then a RAGGED launch for the last M % 128 rows
-int launch_nt_b_n64(const NtArgsB& a, int pro, int epi, hipStream_t st) {
-    const int64_t m_bulk = a.M / 128 * 128;
-    if (m_bulk) {
-        NtArgsB b = a;
-        b.M = m_bulk;
-        int rc;
-        switch (pro) {
-            case PRO_NONE: rc = launch_nt_b<PRO_NONE, NtB64N64>(b, epi, st); break;
-            case PRO_LN_FOLD: rc = launch_nt_b<PRO_NONE, NtB64N64>(b, epi, st, true); break;
-            case PRO_LN: rc = launch_nt_b<PRO_LN, NtB64N64>(b, epi, st); break;
-            case PRO_DROP: rc = launch_nt_b<PRO_DROP, NtB64N64>(b, epi, st); break;
-            default: return HWGAT_EINVAL;
-        }
-        if (rc || m_bulk == a.M) return rc;
-    }
-    const NtArgsB t = nt_rows_b(a, m_bulk, a.M - m_bulk);
-    switch (pro) {
-        case PRO_NONE: return launch_nt_b<PRO_NONE, NtB64N64, true>(t, epi, st);
-        case PRO_LN: return launch_nt_b<PRO_LN, NtB64N64, true>(t, epi, st);
-        case PRO_DROP: return launch_nt_b<PRO_DROP, NtB64N64, true>(t, epi, st);
-        default: return HWGAT_EINVAL;
-    }
-}
+};
 
 }  // namespace
 
@@ -591,78 +535,9 @@ extern "C" int hwgat_linear_nt_bf16_ex(const void* A, const void* W, const float
                                        const float* beta, uint32_t pro_seed, float pro_p, int epi, const void* res,
                                        void* C2, const void* aux, uint32_t epi_seed, float epi_p, float* stat_sum,
                                        float* stat_sq, int merge_F, int merge_K, const uint32_t* seed_base, void* stream) {
-    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return HWGAT_EINVAL;
-    if (N % 64 || K % 64 || ((M + 127) / 128) * (int64_t)(N / 64) > 0x7fffffff) return HWGAT_ESHAPE;   // any M
-    if ((pro == PRO_LN || pro == PRO_LN_FOLD) && (!mean || !rstd || !gamma || !beta)) return HWGAT_EINVAL;
-    if (pro == PRO_LN_FOLD) {                                      // gamma = s[N], beta = c[N] of hwgat_ln_fold; whole tiles
-        if (epi != EPI_BIAS && epi != EPI_BIAS_GELU_DROP && epi != EPI_BIAS_GELU_DROP_G) return HWGAT_EINVAL;
-        if (M % 128) return HWGAT_ESHAPE;
-    }
-    if (epi == EPI_BIAS_DROP_RES && !res) return HWGAT_EINVAL;
-    if ((epi == EPI_BIAS_GELU_DROP || epi == EPI_BIAS_GELU_DROP_G) && !C2) return HWGAT_EINVAL;
-    if ((epi == EPI_GELU_BWD || epi == EPI_MUL_AUX || epi == EPI_RELU_BWD) && !aux) return HWGAT_EINVAL;
-    if (pro_p < 0.f || pro_p >= 1.f || epi_p < 0.f || epi_p >= 1.f) return HWGAT_EINVAL;
-    if (pro == PRO_DROP && pro_p == 0.f) pro = PRO_NONE;          // eval mode: no mask to hash
-    if (epi_is_relu(epi) && pro != PRO_NONE) return HWGAT_EINVAL;
-    const bool stat = stat_sum != nullptr || stat_sq != nullptr || merge_K > 0;
-    if (stat) {
-        if (!stat_sum || !stat_sq || pro != PRO_NONE || epi != EPI_BIAS_DROP_RES) return HWGAT_EINVAL;
-        if (M % 256) return HWGAT_ESHAPE;
-        if (merge_K > 0 && (merge_F <= 0 || (merge_F & 1) || M % ((int64_t)merge_F * merge_K))) return HWGAT_EINVAL;
-    }
-    NtArgsB a{(const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, (bf16_t*)C2, (const bf16_t*)res,
-              (const bf16_t*)aux, mean, rstd, gamma, beta, M, N, K, pro_seed, epi_seed, pro_p, epi_p, 0, stat_sum, stat_sq, merge_K > 0 ? merge_F : 0, merge_K > 0 ? merge_K : 0};
-    a.seed_base = seed_base;
-    hipStream_t st = (hipStream_t)stream;
-    if (N % 128) {                                              // N % 128 == 64: the 128x64 tile
-        if (stat) return HWGAT_ESHAPE;
-        return launch_nt_b_n64(a, pro, epi, st);
-    }
-    const int64_t m_bulk = M / 128 * 128;                       // ragged token count: bulk launch + RAGGED tail launch
-    if (m_bulk != M) {
-        if (m_bulk) {
-            const int rc = hwgat_linear_nt_bf16(A, W, bias, C, m_bulk, N, K, pro, mean, rstd, gamma, beta, pro_seed, pro_p,
-                                                epi, res, C2, aux, epi_seed, epi_p, seed_base, stream);
-            if (rc) return rc;
-        }
-        const NtArgsB t = nt_rows_b(a, m_bulk, M - m_bulk);
-        switch (pro) {
-            case PRO_NONE: return launch_nt_b<PRO_NONE, NtB64, true>(t, epi, st);
-            case PRO_LN: return launch_nt_b<PRO_LN, NtB64, true>(t, epi, st);
-            case PRO_DROP: return launch_nt_b<PRO_DROP, NtB64, true>(t, epi, st);
-            default: return HWGAT_EINVAL;
-        }
-    }
-    // outputs whose width is a multiple of 256: the 256x256 one-wave-per-SIMD kernel (gemm_bf16_nt256.hip: half the
-    // L2 -> LDS stream of the 128x128 tile) over the 256-aligned rows
-    // (fewer than 128 such tiles: the 128 x 128 kernel spreads a serving-size launch over four times as many CUs)
-    if (!epi_is_relu(epi) && N % 256 == 0 && K >= 128 && M >= 256 &&
-        ((M / 256) * (N / 256) >= 128 || a.stat_sum != nullptr)) {     // (the row statistics of the 256-wide kernels are the order-fixed ones: eval determinism)
-        const int64_t m256 = M / 256 * 256;
-        NtArgsB b = a;
-        b.M = m256;
-        // ... on the eight-wave LDS-DMA kernel (gemm_bf16_nt8w.hip) where it applies, else the one-wave-per-SIMD kernel
-        const int rc = hwgat_nt8w_bf16_takes(b, pro, epi) ? hwgat_launch_nt8w_bf16(b, pro, epi, st)
-                                                          : hwgat_launch_nt256_bf16(b, pro, epi, st);
-        if (rc || m256 == M) return rc;
-        const NtArgsB t = nt_rows_b(a, m256, M - m256);   // 128 rows left: RAGGED instantiation (global row index in the dropout hash)
-        switch (pro) {
-            case PRO_NONE: return launch_nt_b<PRO_NONE, NtB64, true>(t, epi, st);
-            case PRO_LN_FOLD: return launch_nt_b<PRO_NONE, NtB64, true>(t, epi, st, true);
-            case PRO_LN: return launch_nt_b<PRO_LN, NtB64, true>(t, epi, st);
-            case PRO_DROP: return launch_nt_b<PRO_DROP, NtB64, true>(t, epi, st);
-            default: return HWGAT_EINVAL;
-        }
-    }
-#define NTB_GO(P) return launch_nt_b<P, NtB64>(a, epi, st)
-    switch (pro) {
-        case PRO_NONE: NTB_GO(PRO_NONE);
-        case PRO_LN_FOLD: return launch_nt_b<PRO_NONE, NtB64>(a, epi, st, true);
-        case PRO_LN: NTB_GO(PRO_LN);
-        case PRO_DROP: NTB_GO(PRO_DROP);
-        default: return HWGAT_EINVAL;
-    }
-#undef NTB_GO
+    return linear_nt_ex<NtBf16>((const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K, pro, mean, rstd, gamma, beta, pro_seed,
+                                pro_p, epi, (const bf16_t*)res, (bf16_t*)C2, (const bf16_t*)aux, epi_seed, epi_p, stat_sum, stat_sq,
+                                merge_F, merge_K, seed_base, stream);
 }
 
 extern "C" int hwgat_linear_nt_bf16(const void* A, const void* W, const float* bias, void* C, int64_t M, int N,
@@ -702,6 +577,23 @@ static int tn_bf16_impl(const void* A, const void* B, float* dW, float* db, int6
     if (mean && (!rstd || !gamma || !beta)) return HWGAT_EINVAL;
     if (N % 128 || K % 128) return HWGAT_ESHAPE;                 // any M
     if (pro_p < 0.f || pro_p >= 1.f) return HWGAT_EINVAL;
+    TnArgsB a{(const bf16_t*)A, (const bf16_t*)B, dW, db, mean, rstd, gamma, beta, M, N, K, 1, M, pro_seed, pro_p, 0};
+    a.seed_base = seed_base;
+    a.det_dw = det.dw; a.det_db = det.db; a.det_cap = det.cap;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_tiles = (N / 128) * (K / 128);
+    auto launch = [&](const TnArgsB& r, auto ragged) {
+        constexpr bool RAGGED = decltype(ragged)::value;
+        const int grid = ((r.n_split + 7) / 8) * 8 * n_tiles;
+        if (pro_p > 0.f) {
+            if (mean) gemm_tn_bf16_k<PRO_DROP, true, RAGGED><<<grid, 256, 0, st>>>(r);
+            else gemm_tn_bf16_k<PRO_DROP, false, RAGGED><<<grid, 256, 0, st>>>(r);
+        } else {
+            if (mean) gemm_tn_bf16_k<PRO_NONE, true, RAGGED><<<grid, 256, 0, st>>>(r);
+            else gemm_tn_bf16_k<PRO_NONE, false, RAGGED><<<grid, 256, 0, st>>>(r);
+        }
+        HWGAT_LAUNCH_CHECK();
+    };
     const int64_t m_bulk = M / TMB * TMB;
     if (m_bulk != M) {                                          // bulk launch + one RAGGED stage for the last M % 32 rows
         if (det.dw) return HWGAT_ESHAPE;                        // deterministic mode: whole 32-row stages only (one launch, one reduction)
@@ -709,72 +601,28 @@ static int tn_bf16_impl(const void* A, const void* B, float* dW, float* db, int6
             const int rc = hwgat_linear_tn_bf16(A, B, dW, db, m_bulk, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, stream);
             if (rc) return rc;
         }
-        const int64_t rows_t = M - m_bulk;
-        TnArgsB t{(const bf16_t*)A + m_bulk * N, (const bf16_t*)B + m_bulk * K, dW, db, mean ? mean + m_bulk : nullptr,
-                  mean ? rstd + m_bulk : nullptr, gamma, beta, rows_t, N, K, 1, TMB, pro_seed, pro_p, m_bulk};
-        t.seed_base = seed_base;
-        const int grid_t = 8 * (N / 128) * (K / 128);
-        hipStream_t stt = (hipStream_t)stream;
-        if (pro_p > 0.f) {
-            if (mean) gemm_tn_bf16_k<PRO_DROP, true, true><<<grid_t, 256, 0, stt>>>(t);
-            else gemm_tn_bf16_k<PRO_DROP, false, true><<<grid_t, 256, 0, stt>>>(t);
-        } else {
-            if (mean) gemm_tn_bf16_k<PRO_NONE, true, true><<<grid_t, 256, 0, stt>>>(t);
-            else gemm_tn_bf16_k<PRO_NONE, false, true><<<grid_t, 256, 0, stt>>>(t);
-        }
-        HWGAT_LAUNCH_CHECK();
+        TnArgsB t = tn_rows(a, m_bulk, M - m_bulk);
+        t.rows_per_split = TMB;
+        return launch(t, std::true_type{});
     }
     // dW at least 256 x 256: the 128x128-wave-tile kernel (gemm_bf16_tn256.hip)
     // ... where its tiles fill the 256 CUs in whole rounds of equal blocks (tile count a divisor of 256: 1, 2, 4, 8 ...);
     // 3 or 12 tiles (the qkv weight) need three rounds of short M slices and lose to the 128x128 kernel:
     // stage 2 dWqkv 492 vs 454 us, stage 1 349 vs 272 (same box, tools/tn_lab.py)
     // plain operands, whole 256x256 tiles: the eight-wave LDS-DMA kernel (gemm_bf16_tn8w.hip)
-    if (hwgat_tn8w_bf16_takes(M, N, K, pro_p, mean)) {
-        TnArgsB a{(const bf16_t*)A, (const bf16_t*)B, dW, db, nullptr, nullptr, nullptr, nullptr, M, N, K, 1, M, pro_seed, pro_p, 0};
-        a.det_dw = det.dw; a.det_db = det.db; a.det_cap = det.cap;
-        return hwgat_launch_tn8w_bf16(a, (hipStream_t)stream);
-    }
+    if (hwgat_tn8w_bf16_takes(M, N, K, pro_p, mean)) return hwgat_launch_tn8w_bf16(a, st);
     const int t256 = (N / 256) * (K / 256);
-    if (N % 256 == 0 && K % 256 == 0 && M % 32 == 0 && 256 % t256 == 0 && !(pro_p > 0.f && mean)) {
-        TnArgsB a{(const bf16_t*)A, (const bf16_t*)B, dW, db, mean, rstd, gamma, beta, M, N, K, 1, M, pro_seed, pro_p, 0};
-        a.seed_base = seed_base;
-        a.det_dw = det.dw; a.det_db = det.db; a.det_cap = det.cap;
-        return hwgat_launch_tn256_bf16(a, (hipStream_t)stream);
-    }
-    const int n_tiles = (N / 128) * (K / 128);
-    auto gcd = [](int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; };
+    if (N % 256 == 0 && K % 256 == 0 && M % 32 == 0 && 256 % t256 == 0 && !(pro_p > 0.f && mean)) return hwgat_launch_tn256_bf16(a, st);
     // three 128x128 blocks per CU (40 KB of LDS, <= 168 registers), ONE round: every block ends in 64 KB of float atomics, so
     // fewer, longer M slices are cheaper (tools/tnb_sweep.sh, stage 0 of config 3 per step: 512 blocks x 2 rounds 1.20 ms,
     // 512 x 1 1.13, 768 x 1 1.09, 768 x 2 1.24, 1024 x 1 1.26)
     static const int slots = [] { const char* e = lab_env("HWGAT_TNB_SLOTS"); return e ? atoi(e) : 768; }();      // blocks of one round
     static const int min_rounds = [] { const char* e = lab_env("HWGAT_TNB_ROUNDS"); return e ? atoi(e) : 1; }();
-    const int r_min = n_tiles / gcd(n_tiles, slots);
-    int r = r_min;
-    while (r < min_rounds) r += r_min;
-    int64_t want = (int64_t)slots * r / n_tiles;
-    const int64_t max_split = M / (TMB * 16) > 0 ? M / (TMB * 16) : 1;
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    int64_t rows = (M + want - 1) / want;
-    rows = (rows + TMB - 1) / TMB * TMB;
-    const int n_split = (int)((M + rows - 1) / rows);
-    TnArgsB a{(const bf16_t*)A, (const bf16_t*)B, dW, db, mean, rstd, gamma, beta, M, N, K, n_split, rows,
-              pro_seed, pro_p, 0};
-    a.seed_base = seed_base;
-    if (det.dw) {
-        if (n_split > det.cap) return HWGAT_ESHAPE;
-        a.det_dw = det.dw; a.det_db = det.db; a.det_cap = det.cap;
-    }
-    const int grid = ((n_split + 7) / 8) * 8 * n_tiles;
-    hipStream_t st = (hipStream_t)stream;
-    if (pro_p > 0.f) {
-        if (mean) gemm_tn_bf16_k<PRO_DROP, true><<<grid, 256, 0, st>>>(a);
-        else gemm_tn_bf16_k<PRO_DROP, false><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (mean) gemm_tn_bf16_k<PRO_NONE, true><<<grid, 256, 0, st>>>(a);
-        else gemm_tn_bf16_k<PRO_NONE, false><<<grid, 256, 0, st>>>(a);
-    }
-    HWGAT_LAUNCH_CHECK();
+    const TnSplit sp = tn_m_split(M, n_tiles, slots, TMB, TMB, min_rounds);
+    a.n_split = sp.n_split;
+    a.rows_per_split = sp.rows_per_split;
+    if (det.dw && a.n_split > det.cap) return HWGAT_ESHAPE;
+    return launch(a, std::false_type{});
 }
 
 extern "C" int hwgat_linear_tn_bf16(const void* A, const void* B, float* dW, float* db, int64_t M, int N, int K,
@@ -786,24 +634,10 @@ extern "C" int hwgat_linear_tn_bf16(const void* A, const void* B, float* dW, flo
     return tn_bf16_impl(A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, DetWs{nullptr, nullptr, 0}, stream);
 }
 
-// Deterministic form: the same kernels, but every block stores its partial dW tile / bias gradient into its M split's
-// image of the caller's ZERO-FILLED workspace and one fixed-order pass adds the images: run-to-run identical bits.
-// ws_bytes >= hwgat_linear_tn_det_bytes(M, N, K); M % 32 == 0.
+// Deterministic form (linear_tn_det, gemm_dispatch.h): ws_bytes >= hwgat_linear_tn_det_bytes(M, N, K); M % 32 == 0.
 extern "C" int hwgat_linear_tn_bf16_det(const void* A, const void* B, float* dW, float* db, int64_t M, int N, int K,
                                         uint32_t pro_seed, float pro_p, const float* mean, const float* rstd,
                                         const float* gamma, const float* beta, const uint32_t* seed_base, float* ws,
                                         int64_t ws_bytes, void* stream) {
-    if (!ws || N <= 0 || K <= 0) return HWGAT_EINVAL;
-    if (hwgat_tn64_takes(N, K))
-        return hwgat_tn64_run(HWGAT_BF16, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, ws,
-                              ws_bytes, (hipStream_t)stream);
-    const int64_t per = (int64_t)N * K + N;
-    const int64_t cap = ws_bytes / 4 / per;
-    if (cap < 1) return HWGAT_ESHAPE;
-    const DetWs det{ws, ws + cap * (int64_t)N * K, (int)(cap > 0x7fffffff ? 0x7fffffff : cap)};
-    int rc = tn_bf16_impl(A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, det, stream);
-    if (rc) return rc;
-    rc = hwgat_tn_det_reduce(det.dw, dW, det.cap, (int64_t)N * K, (int64_t)N * K, (hipStream_t)stream);
-    if (rc || !db) return rc;
-    return hwgat_tn_det_reduce(det.db, db, det.cap, N, N, (hipStream_t)stream);
+    return linear_tn_det(HWGAT_BF16, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, ws, ws_bytes, stream, tn_bf16_impl);
 }

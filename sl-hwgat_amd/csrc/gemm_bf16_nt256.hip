@@ -16,6 +16,7 @@
 #include "common.h"
 #include "fused_ops.h"
 #include "gemm_bf16.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -328,39 +329,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_bf16_k(NtArgsB p) {
     }
 }
 
-template <int PRO>
-int launch(const NtArgsB& a, int epi, int grid, hipStream_t st, bool fold = false) {
-    if (a.stat_sum != nullptr) {                                // validated by the caller: PRO_NONE, EPI_BIAS_DROP_RES
-        if constexpr (PRO == PRO_NONE) {
-            if (a.mg_K > 0) gemm_nt256_bf16_k<PRO_NONE, EPI_BIAS_DROP_RES, 2><<<grid, 256, 0, st>>>(a);
-            else gemm_nt256_bf16_k<PRO_NONE, EPI_BIAS_DROP_RES, 1><<<grid, 256, 0, st>>>(a);
-            HWGAT_LAUNCH_CHECK();
-        }
-        return HWGAT_EINVAL;
-    }
-    if (fold) {                                                 // PRO_LN_FOLD: plain loaders, row-affine epilogue
-        if constexpr (PRO == PRO_NONE) {
-            if (epi == EPI_BIAS) gemm_nt256_bf16_k<PRO_NONE, EPI_BIAS, X_LNFOLD><<<grid, 256, 0, st>>>(a);
-            else if (epi == EPI_BIAS_GELU_DROP) gemm_nt256_bf16_k<PRO_NONE, EPI_BIAS_GELU_DROP, X_LNFOLD><<<grid, 256, 0, st>>>(a);
-            else if (epi == EPI_BIAS_GELU_DROP_G) gemm_nt256_bf16_k<PRO_NONE, EPI_BIAS_GELU_DROP_G, X_LNFOLD><<<grid, 256, 0, st>>>(a);
-            else return HWGAT_EINVAL;
-            HWGAT_LAUNCH_CHECK();
-        }
-        return HWGAT_EINVAL;
-    }
-    switch (epi) {
-        case EPI_BIAS: gemm_nt256_bf16_k<PRO, EPI_BIAS><<<grid, 256, 0, st>>>(a); break;
-        case EPI_BIAS_DROP_RES: gemm_nt256_bf16_k<PRO, EPI_BIAS_DROP_RES><<<grid, 256, 0, st>>>(a); break;
-        case EPI_BIAS_GELU_DROP: gemm_nt256_bf16_k<PRO, EPI_BIAS_GELU_DROP><<<grid, 256, 0, st>>>(a); break;
-        case EPI_GELU_BWD: gemm_nt256_bf16_k<PRO, EPI_GELU_BWD><<<grid, 256, 0, st>>>(a); break;
-        case EPI_BIAS_GELU_DROP_G: gemm_nt256_bf16_k<PRO, EPI_BIAS_GELU_DROP_G><<<grid, 256, 0, st>>>(a); break;
-        case EPI_MUL_AUX: gemm_nt256_bf16_k<PRO, EPI_MUL_AUX><<<grid, 256, 0, st>>>(a); break;
-        case EPI_NONE: gemm_nt256_bf16_k<PRO, EPI_NONE><<<grid, 256, 0, st>>>(a); break;
-        default: return HWGAT_EINVAL;
-    }
-    HWGAT_LAUNCH_CHECK();
-}
-
 }  // namespace
 
 int hwgat_launch_nt256_bf16(const NtArgsB& a, int pro, int epi, hipStream_t st) {
@@ -368,11 +336,8 @@ int hwgat_launch_nt256_bf16(const NtArgsB& a, int pro, int epi, hipStream_t st) 
     const int64_t tiles = (a.M / BT) * (a.N / BT);
     if (tiles > 0x7fffffff) return HWGAT_ESHAPE;
     const int grid = (int)(tiles < 256 ? tiles : 256);          // persistent: one block per CU
-    switch (pro) {
-        case PRO_NONE: return launch<PRO_NONE>(a, epi, grid, st);
-        case PRO_LN_FOLD: return launch<PRO_NONE>(a, epi, grid, st, true);
-        case PRO_LN: return launch<PRO_LN>(a, epi, grid, st);
-        case PRO_DROP: return launch<PRO_DROP>(a, epi, grid, st);
-        default: return HWGAT_EINVAL;
-    }
+    return nt_dispatch<false, true>(pro, epi, a.stat_sum != nullptr, a.mg_K > 0, [&](auto p, auto e, auto x) {
+        gemm_nt256_bf16_k<decltype(p)::value, decltype(e)::value, decltype(x)::value><<<grid, 256, 0, st>>>(a);
+        HWGAT_LAUNCH_CHECK();
+    });
 }

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "fused_ops.h"
 #include "gemm_bf16.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -278,19 +279,10 @@ int hwgat_launch_tn256_bf16(TnArgsB a, hipStream_t st) {
     const int n_tiles = (a.N / BT) * (a.K / BT);
     // equal-sized blocks, one resident per CU: n_split * n_tiles an exact multiple of 256 where the tile count allows,
     // the split count a multiple of 8 (split s lives on XCD s % 8) -- the rule of hwgat_launch_tn256 (gemm_f32_tn256.hip)
-    auto gcd = [](int x, int y) { while (y) { int t = x % y; x = y; y = t; } return x; };
-    const int r_min = n_tiles / gcd(n_tiles, 256);
     static const int min_rounds = [] { const char* e = lab_env("HWGAT_TN_ROUNDS"); return e ? atoi(e) : 1; }();
-    int r = r_min;
-    while (r < min_rounds) r += r_min;
-    int64_t want = (int64_t)256 * r / n_tiles;
-    const int64_t max_split = a.M / (TMB * 16) > 0 ? a.M / (TMB * 16) : 1;
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    int64_t rows = (a.M + want - 1) / want;
-    rows = (rows + TMB - 1) / TMB * TMB;
-    a.n_split = (int)((a.M + rows - 1) / rows);
-    a.rows_per_split = rows;
+    const TnSplit sp = tn_m_split(a.M, n_tiles, 256, TMB, TMB, min_rounds);
+    a.n_split = sp.n_split;
+    a.rows_per_split = sp.rows_per_split;
     if (a.det_dw && a.n_split > a.det_cap) return HWGAT_ESHAPE;
     const int grid = ((a.n_split + 7) / 8) * 8 * n_tiles;
     const bool drop = a.pro_p > 0.f, ln = a.mean != nullptr;

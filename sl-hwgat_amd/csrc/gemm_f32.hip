@@ -30,7 +30,7 @@
 #include "common.h"
 #include "fused_ops.h"
 #include "gemm_f32.h"
-#include "gemm_tn64.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -493,116 +493,38 @@ __global__ void transpose_k(const float* __restrict__ in, float* __restrict__ ou
         if (c0 + i < C && r0 + threadIdx.x < R) out[(int64_t)(c0 + i) * R + r0 + threadIdx.x] = tile[threadIdx.x][i];
 }
 
-template <int PRO, typename C, bool RAGGED = false>
-int launch_nt(const NtArgs& a, int epi, hipStream_t st, bool fold = false) {
-    const int64_t tiles = ((a.M + C::BM - 1) / C::BM) * (a.N / C::BN);
-    const int grid = (int)(tiles < C::SLOTS ? tiles : C::SLOTS);      // persistent over tiles
-    if (fold) {                                                         // PRO_LN_FOLD: plain loaders, row-affine epilogue
-        if constexpr (PRO == PRO_NONE) {
-            if (epi == EPI_BIAS) gemm_nt_k<PRO_NONE, EPI_BIAS, C, RAGGED, X_LNFOLD><<<grid, C::THREADS, 0, st>>>(a);
-            else if (epi == EPI_BIAS_GELU_DROP) gemm_nt_k<PRO_NONE, EPI_BIAS_GELU_DROP, C, RAGGED, X_LNFOLD><<<grid, C::THREADS, 0, st>>>(a);
-            else if (epi == EPI_BIAS_GELU_DROP_G) gemm_nt_k<PRO_NONE, EPI_BIAS_GELU_DROP_G, C, RAGGED, X_LNFOLD><<<grid, C::THREADS, 0, st>>>(a);
-            else return HWGAT_EINVAL;
+// the fp32 family for the shared validation and routing (gemm_dispatch.h)
+struct NtF32 {
+    using T = float;
+    static constexpr int K_GRANULE = 32;
+    using Tile = NtSmall;
+    using Heavy = NtK16;                                        // heavy epilogues: K slabs of 16, three blocks per CU
+    using N64 = NtN64;
+    template <typename C, bool RAGGED>
+    static int launch(const NtArgs& a, int pro, int epi, hipStream_t st) {
+        const int64_t tiles = ((a.M + C::BM - 1) / C::BM) * (a.N / C::BN);
+        const int grid = (int)(tiles < C::SLOTS ? tiles : C::SLOTS);      // persistent over tiles
+        return nt_dispatch<true, !RAGGED>(pro, epi, a.stat_sum != nullptr, a.mg_K > 0, [&](auto p, auto e, auto x) {
+            gemm_nt_k<decltype(p)::value, decltype(e)::value, C, RAGGED, decltype(x)::value><<<grid, C::THREADS, 0, st>>>(a);
             HWGAT_LAUNCH_CHECK();
-        }
-        return HWGAT_EINVAL;
+        });
     }
-    if (a.stat_sum != nullptr) {                                        // validated by the caller: PRO_NONE, EPI_BIAS_DROP_RES, M % 128 == 0
-        if constexpr (PRO == PRO_NONE && !RAGGED) {
-            if (a.mg_K > 0) gemm_nt_k<PRO_NONE, EPI_BIAS_DROP_RES, C, false, 2><<<grid, C::THREADS, 0, st>>>(a);
-            else gemm_nt_k<PRO_NONE, EPI_BIAS_DROP_RES, C, false, 1><<<grid, C::THREADS, 0, st>>>(a);
-            HWGAT_LAUNCH_CHECK();
-        }
-        return HWGAT_EINVAL;
-    }
-    switch (epi) {
-        case EPI_BIAS: gemm_nt_k<PRO, EPI_BIAS, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_DROP_RES: gemm_nt_k<PRO, EPI_BIAS_DROP_RES, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_GELU_DROP: gemm_nt_k<PRO, EPI_BIAS_GELU_DROP, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_GELU_BWD: gemm_nt_k<PRO, EPI_GELU_BWD, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_GELU_DROP_G: gemm_nt_k<PRO, EPI_BIAS_GELU_DROP_G, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_MUL_AUX: gemm_nt_k<PRO, EPI_MUL_AUX, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_NONE: gemm_nt_k<PRO, EPI_NONE, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break;
-        case EPI_BIAS_RELU_DROP:
-            if constexpr (PRO == PRO_NONE) { gemm_nt_k<PRO_NONE, EPI_BIAS_RELU_DROP, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
-            return HWGAT_EINVAL;
-        case EPI_RELU_BWD:
-            if constexpr (PRO == PRO_NONE) { gemm_nt_k<PRO_NONE, EPI_RELU_BWD, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a); break; }
-            return HWGAT_EINVAL;
-        default: return HWGAT_EINVAL;
-    }
-    HWGAT_LAUNCH_CHECK();
-}
-
-// the same launch restricted to rows [r0, r0 + rows) of every M-indexed operand
-NtArgs nt_rows(NtArgs a, int64_t r0, int64_t rows) {
-    a.A += r0 * a.K;
-    a.C += r0 * a.N;
-    if (a.C2) a.C2 += r0 * a.N;
-    if (a.res) a.res += r0 * a.N;
-    if (a.aux) a.aux += r0 * a.N;
-    if (a.mean) { a.mean += r0; a.rstd += r0; }
-    a.M = rows;
-    a.row0 = r0;
-    return a;
-}
-TnArgs tn_rows(TnArgs a, int64_t r0, int64_t rows) {
-    a.A += r0 * a.N;
-    a.B += r0 * a.K;
-    if (a.mean) { a.mean += r0; a.rstd += r0; }
-    a.M = rows;
-    a.row0 = r0;
-    return a;
-}
-
-// N % 128 == 64: the 128x64 tile over the whole 128-row blocks, then a RAGGED launch for the last M % 128 rows
-// (row statistics / merged store are not built for this tile: the caller takes the separate statistics pass)
-int launch_nt_n64(const NtArgs& a, int pro, int epi, hipStream_t st) {
-    const int64_t m_bulk = a.M / 128 * 128;
-    if (m_bulk) {
-        NtArgs b = a;
-        b.M = m_bulk;
-        int rc;
-        switch (pro) {
-            case PRO_NONE: rc = launch_nt<PRO_NONE, NtN64>(b, epi, st); break;
-            case PRO_LN_FOLD: rc = launch_nt<PRO_NONE, NtN64>(b, epi, st, true); break;
-            case PRO_LN: rc = launch_nt<PRO_LN, NtN64>(b, epi, st); break;
-            case PRO_DROP: rc = launch_nt<PRO_DROP, NtN64>(b, epi, st); break;
-            default: return HWGAT_EINVAL;
-        }
-        if (rc || m_bulk == a.M) return rc;
-    }
-    const NtArgs t = nt_rows(a, m_bulk, a.M - m_bulk);
-    switch (pro) {
-        case PRO_NONE: return launch_nt<PRO_NONE, NtN64, true>(t, epi, st);
-        case PRO_LN: return launch_nt<PRO_LN, NtN64, true>(t, epi, st);
-        case PRO_DROP: return launch_nt<PRO_DROP, NtN64, true>(t, epi, st);
-        default: return HWGAT_EINVAL;
-    }
-}
+    // (an eight-wave ping-pong twin of the bf16 kernel gemm_bf16_nt8w.hip was built and measured in round 3: the same
+    // time within +-2 % on every launch, 55.14 vs 55.39 ms per step -- fp32 MFMA launches are bound by the matrix
+    // pipe at the clock the chip sustains, not by staging or epilogue issue; it lives in tools/f32_nt8w/, not here)
+    static int launch256(const NtArgs& b, int pro, int epi, hipStream_t st) { return hwgat_launch_nt256(b, pro, epi, st); }
+};
 
 template <int PRO, bool BLN, typename C, bool RAGGED = false>
 int launch_tn(TnArgs a, hipStream_t st) {
     constexpr int TM = C::BK;
     const int n_tiles = (a.N / C::BM) * (a.K / C::BM);
-    // Blocks are equal-sized and fill C::SLOTS resident slots, so they execute in rounds: pick the
-    // number of M slices so that blocks = n_split * n_tiles is an exact multiple of the slots (no
-    // nearly-empty last round), >= 2 rounds, and every slice is >= 16 LDS stages deep.
-    auto gcd = [](int x, int y) { while (y) { int t = x % y; x = y; y = t; } return x; };
-    const int r_min = n_tiles / gcd(n_tiles, C::SLOTS);
     // one round where the tiles fill the slots (nearly) evenly -- a second round only doubles the atomic traffic at the
     // end of the M slices (see hwgat_launch_tn256); HWGAT_TN_ROUNDS=2 restores the round-1 rule for A/B runs
     static const int min_rounds = [] { const char* e = lab_env("HWGAT_TN_ROUNDS"); return e ? atoi(e) : 1; }();
-    int r = r_min;
-    while (r < min_rounds) r += r_min;
-    int64_t want = (int64_t)C::SLOTS * r / n_tiles;
-    const int64_t max_split = a.M / (TM * 16) > 0 ? a.M / (TM * 16) : 1;
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    int64_t rows = (a.M + want - 1) / want;
-    rows = (rows + TM - 1) / TM * TM;
-    a.n_split = (int)((a.M + rows - 1) / rows);
-    a.rows_per_split = rows;
+    const TnSplit sp = tn_m_split(a.M, n_tiles, C::SLOTS, TM, TM, min_rounds);
+    a.n_split = sp.n_split;
+    a.rows_per_split = sp.rows_per_split;
     if (a.det_dw && a.n_split > a.det_cap) return HWGAT_ESHAPE;
     const int grid = ((a.n_split + 7) / 8) * 8 * n_tiles;
     gemm_tn_k<PRO, BLN, C, RAGGED><<<grid, C::THREADS, 0, st>>>(a);
@@ -617,92 +539,8 @@ extern "C" int hwgat_linear_nt_f32_ex(const float* A, const float* W, const floa
                                       int epi, const float* res, float* C2, const float* aux, uint32_t epi_seed,
                                       float epi_p, float* stat_sum, float* stat_sq, int merge_F, int merge_K,
                                       const uint32_t* seed_base, void* stream) {
-    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return HWGAT_EINVAL;
-    if (N % 64 || K % 32 || ((M + 127) / 128) * (int64_t)(N / 64) > 0x7fffffff) return HWGAT_ESHAPE;   // any M
-    if ((pro == PRO_LN || pro == PRO_LN_FOLD) && (!mean || !rstd || !gamma || !beta)) return HWGAT_EINVAL;
-    if (pro == PRO_LN_FOLD) {                                      // gamma = s[N], beta = c[N] of hwgat_ln_fold; whole tiles
-        if (epi != EPI_BIAS && epi != EPI_BIAS_GELU_DROP && epi != EPI_BIAS_GELU_DROP_G) return HWGAT_EINVAL;
-        if (M % 128) return HWGAT_ESHAPE;
-    }
-    if (epi == EPI_BIAS_DROP_RES && !res) return HWGAT_EINVAL;
-    if ((epi == EPI_BIAS_GELU_DROP || epi == EPI_BIAS_GELU_DROP_G) && !C2) return HWGAT_EINVAL;
-    if ((epi == EPI_GELU_BWD || epi == EPI_MUL_AUX || epi == EPI_RELU_BWD) && !aux) return HWGAT_EINVAL;
-    if (pro_p < 0.f || pro_p >= 1.f || epi_p < 0.f || epi_p >= 1.f) return HWGAT_EINVAL;
-    if (epi_is_relu(epi) && pro != PRO_NONE) return HWGAT_EINVAL;
-    const bool stat = stat_sum != nullptr || stat_sq != nullptr || merge_K > 0;
-    if (stat) {
-        if (!stat_sum || !stat_sq || pro != PRO_NONE || epi != EPI_BIAS_DROP_RES) return HWGAT_EINVAL;
-        if (M % 256) return HWGAT_ESHAPE;                          // whole tiles of either kernel only
-        if (merge_K > 0 && (merge_F <= 0 || (merge_F & 1) || M % ((int64_t)merge_F * merge_K))) return HWGAT_EINVAL;
-    }
-    if (pro == PRO_DROP && pro_p == 0.f) pro = PRO_NONE;          // eval mode: no mask to hash
-    NtArgs a{A, W, bias, C, C2, res, aux, mean, rstd, gamma, beta, M, N, K, pro_seed, epi_seed, pro_p, epi_p, 0, stat_sum, stat_sq, merge_K > 0 ? merge_F : 0, merge_K > 0 ? merge_K : 0};
-    a.seed_base = seed_base;
-    hipStream_t st = (hipStream_t)stream;
-    if (N % 128) {                                                 // N % 128 == 64: the 128x64 tile
-        if (stat) return HWGAT_ESHAPE;
-        return launch_nt_n64(a, pro, epi, st);
-    }
-    // a token count that is not a multiple of the 128-row tile: bulk launch over the aligned rows with the
-    // unmodified kernels, then one small RAGGED launch for the last M % 128 rows
-    const int64_t m_bulk = M / 128 * 128;
-    if (m_bulk != M) {
-        if (m_bulk) {
-            const int rc = hwgat_linear_nt_f32(A, W, bias, C, m_bulk, N, K, pro, mean, rstd, gamma, beta, pro_seed, pro_p,
-                                               epi, res, C2, aux, epi_seed, epi_p, seed_base, stream);
-            if (rc) return rc;
-        }
-        const NtArgs t = nt_rows(a, m_bulk, M - m_bulk);
-        switch (pro) {
-            case PRO_NONE: return launch_nt<PRO_NONE, NtSmall, true>(t, epi, st);
-            case PRO_LN: return launch_nt<PRO_LN, NtSmall, true>(t, epi, st);
-            case PRO_DROP: return launch_nt<PRO_DROP, NtSmall, true>(t, epi, st);
-            default: return HWGAT_EINVAL;
-        }
-    }
-    // Tile choice, measured on MI355X (profiles/r01f_gemm_tile_ab.txt):
-    //  - an 8-wave 256x256 tile lost to two independent 128x128 blocks per CU (110 vs 129 TF at
-    //    K=512) and was removed;
-    //  - four resident blocks (K16, 128 VGPRs) are 2-3 % slower than two; K slabs of 16 with THREE
-    //    resident blocks per CU are ~1 % slower for plain epilogues but
-    //    7-15 % faster when the epilogue is heavy (dropout+residual, GELU, GELU backward): the third
-    //    block's MFMAs cover the epilogue's loads/stores.
-    // (prologue-carrying launches gain nothing from K16: 570.5 vs 571.1 clips/s)
-    // Outputs whose width is a multiple of 256: the 256x256 one-wave-per-SIMD kernel (gemm_f32_nt256.hip) over the
-    // 256-aligned rows.  Same box, TFLOP/s, 128x128 kernels -> this one (tools/nt_lab.py, profiles/r02b_nt_lab_*.txt):
-    // stage 2 plain dX 131.7 -> 143.2 and 130.4 -> 141.1, LN-prologue qkv 120.6 -> 132.1, fc1 107.8 -> 121.0, fc2 125.9 ->
-    // 136.0, GELU-backward 102.7 -> 114.7, dropout-prologue dX 111.1 -> 124.3, projection 119.1 -> 126.4; stage 1 (K = 256
-    // ... 768) +1 ... +10 %; stage 0 (N = 256, K = 128) +3 ... +5 %.
-    // (serving batches: fewer than 128 tiles of 256 x 256 leave most of the 256 CUs without a tile -- the 128 x 128 kernel
-    //  has four times as many; B = 1 eval forward 3.96 -> see profiles/r03_serve_lab.txt)
-    if (!epi_is_relu(epi) && N % 256 == 0 && K >= 128 && M >= 256 &&
-        ((M / 256) * (N / 256) >= 128 || a.stat_sum != nullptr)) {     // (the row statistics of the 256-wide kernels are the order-fixed ones: eval determinism)
-        const int64_t m256 = M / 256 * 256;
-        NtArgs b = a;
-        b.M = m256;
-        // (an eight-wave ping-pong twin of the bf16 kernel gemm_bf16_nt8w.hip was built and measured in round 3: the same
-        // time within +-2 % on every launch, 55.14 vs 55.39 ms per step -- fp32 MFMA launches are bound by the matrix
-        // pipe at the clock the chip sustains, not by staging or epilogue issue; it lives in tools/f32_nt8w/, not here)
-        const int rc = hwgat_launch_nt256(b, pro, epi, st);
-        if (rc || m256 == M) return rc;
-        const NtArgs t = nt_rows(a, m256, M - m256);      // 128 rows left: the RAGGED instantiation hashes dropout
-        switch (pro) {                                     // masks with the global row index (row0)
-            case PRO_NONE: return launch_nt<PRO_NONE, NtSmall, true>(t, epi, st);
-            case PRO_LN_FOLD: return launch_nt<PRO_NONE, NtSmall, true>(t, epi, st, true);
-            case PRO_LN: return launch_nt<PRO_LN, NtSmall, true>(t, epi, st);
-            case PRO_DROP: return launch_nt<PRO_DROP, NtSmall, true>(t, epi, st);
-            default: return HWGAT_EINVAL;
-        }
-    }
-    const bool heavy = epi == EPI_BIAS_DROP_RES || epi == EPI_BIAS_GELU_DROP || epi == EPI_GELU_BWD || epi == EPI_BIAS_GELU_DROP_G || epi == EPI_MUL_AUX ||
-                       epi_is_relu(epi);
-    switch (pro) {                                               // heavy epilogues: K slabs of 16, three blocks per CU
-        case PRO_NONE: return heavy ? launch_nt<PRO_NONE, NtK16>(a, epi, st) : launch_nt<PRO_NONE, NtSmall>(a, epi, st);
-        case PRO_LN_FOLD: return heavy ? launch_nt<PRO_NONE, NtK16>(a, epi, st, true) : launch_nt<PRO_NONE, NtSmall>(a, epi, st, true);
-        case PRO_LN: return heavy ? launch_nt<PRO_LN, NtK16>(a, epi, st) : launch_nt<PRO_LN, NtSmall>(a, epi, st);
-        case PRO_DROP: return heavy ? launch_nt<PRO_DROP, NtK16>(a, epi, st) : launch_nt<PRO_DROP, NtSmall>(a, epi, st);
-        default: return HWGAT_EINVAL;
-    }
+    return linear_nt_ex<NtF32>(A, W, bias, C, M, N, K, pro, mean, rstd, gamma, beta, pro_seed, pro_p, epi, res, C2, aux, epi_seed,
+                               epi_p, stat_sum, stat_sq, merge_F, merge_K, seed_base, stream);
 }
 
 extern "C" int hwgat_linear_nt_f32(const float* A, const float* W, const float* bias, float* C, int64_t M,
@@ -812,19 +650,20 @@ int hwgat_tn_det_reduce(const float* ws, float* out, int cap, int64_t stride, in
     HWGAT_LAUNCH_CHECK();
 }
 
-// M splits any dW kernel may choose for this shape (an upper bound over the kernels of both dtypes), + margin
+// M splits any dW kernel may choose for this shape (an upper bound over the kernels of both dtypes), + margin: the
+// whole-round split counts (tn_round_splits, before a launcher clamps them to the rows it has) of the 128x128-tile
+// kernels at 2, 3 and 4 resident blocks per CU and of the 256x256-tile kernels, whose count is a multiple of 8, at least 8
 static int64_t tn_det_cap(int64_t M, int N, int K) {
-    auto gcd = [](int64_t x, int64_t y) { while (y) { int64_t t = x % y; x = y; y = t; } return x; };
     const int64_t t128 = (int64_t)(N / 128) * (K / 128);
     int64_t cap = 0;
-    for (int64_t slots : {512, 768, 1024}) {                    // fp32 / bf16 128x128-tile kernels (2, 3, 4 resident blocks per CU)
-        const int64_t r = t128 / gcd(t128, slots);
-        cap = cap > slots * r / t128 ? cap : slots * r / t128;
-    }
-    if (N % 256 == 0 && K % 256 == 0) {                         // 256x256-tile kernels: multiples of 8, at least 8
-        const int64_t t256 = (int64_t)(N / 256) * (K / 256), r = t256 / gcd(t256, 256);
-        const int64_t w = 256 * r / t256 > 8 ? 256 * r / t256 : 8;
+    for (int64_t slots : {512, 768, 1024}) {
+        const int64_t w = tn_round_splits(t128, slots, 1);
         cap = cap > w ? cap : w;
+    }
+    if (N % 256 == 0 && K % 256 == 0) {
+        const int64_t w = tn_round_splits((int64_t)(N / 256) * (K / 256), 256, 1);
+        cap = cap > w ? cap : w;
+        cap = cap > 8 ? cap : 8;
     }
     const int64_t by_rows = M / 32 + 1;                          // never more splits than 32-row stages
     cap = cap < by_rows ? cap : by_rows;
@@ -836,25 +675,13 @@ extern "C" int64_t hwgat_linear_tn_det_bytes(int64_t M, int N, int K) {
     return tn_det_cap(M, N, K) * ((int64_t)N * K + N) * 4;
 }
 
-// Deterministic form of hwgat_linear_tn_f32 (see hwgat_linear_tn_bf16_det): zero-filled workspace of
+// Deterministic form of hwgat_linear_tn_f32 (linear_tn_det, gemm_dispatch.h): zero-filled workspace of
 // hwgat_linear_tn_det_bytes(M, N, K) bytes, M % 32 == 0.
 extern "C" int hwgat_linear_tn_f32_det(const float* A, const float* B, float* dW, float* db, int64_t M, int N,
                                        int K, uint32_t pro_seed, float pro_p, const float* mean,
                                        const float* rstd, const float* gamma, const float* beta,
                                        const uint32_t* seed_base, float* ws, int64_t ws_bytes, void* stream) {
-    if (!ws || N <= 0 || K <= 0) return HWGAT_EINVAL;
-    if (hwgat_tn64_takes(N, K))
-        return hwgat_tn64_run(HWGAT_F32, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, ws,
-                              ws_bytes, (hipStream_t)stream);
-    const int64_t per = (int64_t)N * K + N;
-    const int64_t cap = ws_bytes / 4 / per;
-    if (cap < 1) return HWGAT_ESHAPE;
-    const DetWs det{ws, ws + cap * (int64_t)N * K, (int)(cap > 0x7fffffff ? 0x7fffffff : cap)};
-    int rc = tn_f32_impl(A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, det, stream);
-    if (rc) return rc;
-    rc = hwgat_tn_det_reduce(det.dw, dW, det.cap, (int64_t)N * K, (int64_t)N * K, (hipStream_t)stream);
-    if (rc || !db) return rc;
-    return hwgat_tn_det_reduce(det.db, db, det.cap, N, N, (hipStream_t)stream);
+    return linear_tn_det(HWGAT_F32, A, B, dW, db, M, N, K, pro_seed, pro_p, mean, rstd, gamma, beta, seed_base, ws, ws_bytes, stream, tn_f32_impl);
 }
 
 extern "C" int hwgat_transpose_f32(const float* in, float* out, int R, int C, void* stream) {

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "fused_ops.h"
 #include "gemm_f32.h"
+#include "gemm_dispatch.h"
 
 namespace {
 
@@ -233,11 +234,8 @@ __global__ __launch_bounds__(256) void tn256_reduce_k(const float* __restrict__ 
 
 }  // namespace
 
-// the M split of a launch: equal-sized blocks, one resident per CU (256 slots)
+// the M split of a launch: equal-sized blocks, one resident per CU (256 slots), whole pairs of 16-row stages
 static void tn256_split(int64_t M, int n_tiles, int& n_split, int64_t& rows_per_split) {
-    // blocks = n_split * n_tiles an exact multiple of 256
-    auto gcd = [](int x, int y) { while (y) { int t = x % y; x = y; y = t; } return x; };
-    const int r_min = n_tiles / gcd(n_tiles, 256);
     // The smallest whole number of rounds that fills every slot with equal blocks -- ONE round when the tile count
     // divides 256.  Every M slice ends in n_tiles x 256 KB of partial sums; the round-1 rule (at least two rounds) doubled
     // that traffic for nothing: stage 2 dWproj 112.5 -> 118.6, dW1 124.3 -> 128.0, dW2 120.0 -> 123.2 TFLOP/s on one box;
@@ -245,16 +243,9 @@ static void tn256_split(int64_t M, int n_tiles, int& n_split, int64_t& rows_per_
     // M slice through that XCD's L2), and 21 splits x 12 tiles put 36 blocks on five of the XCDs' 32 CUs -- twice the
     // time (measured).
     static const int min_rounds = [] { const char* e = lab_env("HWGAT_TN_ROUNDS"); return e ? atoi(e) : 1; }();
-    int r = r_min;
-    while (r < min_rounds) r += r_min;
-    int64_t want = (int64_t)256 * r / n_tiles;
-    const int64_t max_split = M / (TM * 16) > 0 ? M / (TM * 16) : 1;
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    int64_t rows = (M + want - 1) / want;
-    rows = (rows + 2 * TM - 1) / (2 * TM) * (2 * TM);
-    n_split = (int)((M + rows - 1) / rows);
-    rows_per_split = rows;
+    const TnSplit sp = tn_m_split(M, n_tiles, 256, TM, 2 * TM, min_rounds);
+    n_split = sp.n_split;
+    rows_per_split = sp.rows_per_split;
 }
 
 // floats of workspace hwgat_launch_tn256 wants for the slab form of this shape (0: the shape does not take the kernel)

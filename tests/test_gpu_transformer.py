@@ -171,6 +171,20 @@ def test_relu_epilogues(M, N, K, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_relu_epilogue_after_an_eval_mode_dropout_prologue(dtype):
+    """PRO_DROP with pro_p == 0 is PRO_NONE before the arguments are checked (eval mode: no mask to hash), so the ReLU
+    epilogue, which takes no prologue, accepts it -- bit for bit the PRO_NONE launch, bulk rows and ragged tail alike"""
+    M, N, K = 128 + 29, 128, 64
+    g = torch.Generator().manual_seed(M + N)
+    A, W, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.1, torch.randn(N, generator=g)
+    Ad, Wd, bd = A.to(DEV, dtype), W.to(DEV, dtype), b.to(DEV)
+    ref = HF.linear_nt(Ad, Wd, bd, pro=HF.PRO_NONE, epi=HF.EPI_BIAS_RELU_DROP, epi_seed=77, epi_p=0.1)
+    got = HF.linear_nt(Ad, Wd, bd, pro=HF.PRO_DROP, pro_seed=5, pro_p=0.0, epi=HF.EPI_BIAS_RELU_DROP, epi_seed=77, epi_p=0.1)
+    assert torch.equal(got, ref)
+    assert 0.3 < float((ref == 0).float().mean()) < 0.8                    # a ReLU output with a mask, not zeros
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_max_pool(dtype):
     g = torch.Generator().manual_seed(3)
     x = torch.randn(3, 37, 128, generator=g).to(dtype)

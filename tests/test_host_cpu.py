@@ -1,6 +1,7 @@
 """CPU: host logic of the backend -- C-ABI exports, drop-in boundary, mask rows."""
 import ctypes
 import importlib
+import os
 
 import numpy as np
 import pytest
@@ -97,6 +98,123 @@ def test_c_abi_rejects_bad_arguments_without_launching():
     assert L.hwgat_linear_tn_f32(p, p, p, None, 64, 128, 100, 0, 0.0, None, None, None, None, None, None) == -2
     assert L.hwgat_embed_fwd(p, None, p, None, p, 1, 4, 29, 64, 2, 128, 0, 0, 0.0, None, None) == -2   # J != K without a table
     assert L.hwgat_merge(p, p, 1, 3, 16, 128, 0, 0, None) == -2
+
+
+EINVAL, ESHAPE = -1, -2
+_DUMMY = (ctypes.c_float * 64)()
+_P = ctypes.cast(_DUMMY, ctypes.c_void_p)
+# prologues / epilogues of csrc/fused_ops.h
+PRO_NONE, PRO_LN, PRO_DROP, PRO_LN_FOLD = 0, 1, 2, 3
+(EPI_BIAS, EPI_BIAS_DROP_RES, EPI_BIAS_GELU_DROP, EPI_GELU_BWD, EPI_NONE, EPI_BIAS_GELU_DROP_G, EPI_MUL_AUX,
+ EPI_BIAS_RELU_DROP, EPI_RELU_BWD) = range(9)
+_LN = dict(mean=_P, rstd=_P, gamma=_P, beta=_P)
+_STAT = dict(M=256, epi=EPI_BIAS_DROP_RES, res=_P, stat_sum=_P, stat_sq=_P)        # a valid statistics call, then one fault
+_NT_ORDER = ("A", "W", "bias", "C", "M", "N", "K", "pro", "mean", "rstd", "gamma", "beta", "pro_seed", "pro_p", "epi", "res",
+             "C2", "aux", "epi_seed", "epi_p", "stat_sum", "stat_sq", "merge_F", "merge_K", "seed_base", "stream")
+_NT_DEFAULT = dict(A=_P, W=_P, C=_P, M=128, N=128, K=128, pro=PRO_NONE, pro_seed=0, pro_p=0.0, epi=EPI_BIAS, epi_seed=0,
+                   epi_p=0.0, merge_F=0, merge_K=0)
+_TN_ORDER = ("A", "B", "dW", "db", "M", "N", "K", "pro_seed", "pro_p", "mean", "rstd", "gamma", "beta", "seed_base")
+_TN_DEFAULT = dict(A=_P, B=_P, dW=_P, M=64, N=128, K=128, pro_seed=0, pro_p=0.0)
+_ONE_IMAGE = (128 * 128 + 128) * 4                                                   # bytes of one dW + db image at N = K = 128
+
+# (over-rides of a valid call, status) -- every case fails a check that runs before the first launch
+_NT_CASES = {
+    "A_null": (dict(A=None), EINVAL), "W_null": (dict(W=None), EINVAL), "C_null": (dict(C=None), EINVAL),
+    "M_zero": (dict(M=0), EINVAL), "N_zero": (dict(N=0), EINVAL), "K_negative": (dict(K=-128), EINVAL),
+    "N_not_64": (dict(N=100), ESHAPE),
+    "ln_without_stats": (dict(pro=PRO_LN, gamma=_P, beta=_P), EINVAL),
+    "ln_fold_without_stats": (dict(pro=PRO_LN_FOLD, mean=_P, rstd=_P), EINVAL),
+    "ln_fold_other_epilogue": (dict(pro=PRO_LN_FOLD, epi=EPI_BIAS_DROP_RES, res=_P, **_LN), EINVAL),
+    "ln_fold_ragged_M": (dict(pro=PRO_LN_FOLD, M=192, **_LN), ESHAPE),
+    "drop_res_without_res": (dict(epi=EPI_BIAS_DROP_RES), EINVAL),
+    "gelu_drop_without_C2": (dict(epi=EPI_BIAS_GELU_DROP), EINVAL),
+    "gelu_drop_g_without_C2": (dict(epi=EPI_BIAS_GELU_DROP_G), EINVAL),
+    "gelu_bwd_without_aux": (dict(epi=EPI_GELU_BWD), EINVAL),
+    "mul_aux_without_aux": (dict(epi=EPI_MUL_AUX), EINVAL),
+    "relu_bwd_without_aux": (dict(epi=EPI_RELU_BWD), EINVAL),
+    "pro_p_negative": (dict(pro=PRO_DROP, pro_p=-0.1), EINVAL), "pro_p_one": (dict(pro=PRO_DROP, pro_p=1.0), EINVAL),
+    "epi_p_negative": (dict(epi_p=-0.5), EINVAL), "epi_p_one": (dict(epi_p=1.0), EINVAL),
+    "relu_with_ln": (dict(epi=EPI_BIAS_RELU_DROP, pro=PRO_LN, **_LN), EINVAL),
+    "relu_bwd_with_dropout_prologue": (dict(epi=EPI_RELU_BWD, aux=_P, pro=PRO_DROP, pro_p=0.5), EINVAL),
+    "stat_sum_only": (dict(_STAT, stat_sq=None), EINVAL), "stat_sq_only": (dict(_STAT, stat_sum=None), EINVAL),
+    "merge_without_buffers": (dict(_STAT, stat_sum=None, stat_sq=None, merge_F=2, merge_K=4), EINVAL),
+    "stat_with_prologue": (dict(_STAT, pro=PRO_LN, **_LN), EINVAL),
+    "stat_other_epilogue": (dict(_STAT, epi=EPI_BIAS), EINVAL),
+    "stat_M_not_256": (dict(_STAT, M=128), ESHAPE),
+    "stat_N_odd_64": (dict(_STAT, N=192), ESHAPE),
+    "merge_F_zero": (dict(_STAT, merge_F=0, merge_K=4), EINVAL), "merge_F_odd": (dict(_STAT, merge_F=3, merge_K=4), EINVAL),
+    "merge_M_not_whole_clips": (dict(_STAT, merge_F=2, merge_K=3), EINVAL),
+}
+_TN_CASES = {
+    "A_null": (dict(A=None), EINVAL), "B_null": (dict(B=None), EINVAL), "dW_null": (dict(dW=None), EINVAL),
+    "M_zero": (dict(M=0), EINVAL), "N_not_128": (dict(N=100), ESHAPE), "K_not_128": (dict(K=100), ESHAPE),
+    "ln_without_rstd": (dict(mean=_P, gamma=_P, beta=_P), EINVAL), "pro_p_one": (dict(pro_p=1.0), EINVAL),
+}
+_DET_CASES = {
+    "ws_null": (dict(ws=None), EINVAL), "ws_below_one_image": (dict(ws_bytes=_ONE_IMAGE - 4), ESHAPE),
+    "ragged_M": (dict(M=48), ESHAPE),
+}
+
+
+def _nt_ex(dtype, over):
+    a = dict(_NT_DEFAULT, **over)
+    return getattr(hw._lib.lib(), "hwgat_linear_nt_%s_ex" % dtype)(*[a.get(k) for k in _NT_ORDER])
+
+
+def _tn(dtype, det, over):
+    a = dict(_TN_DEFAULT, **(dict(ws=_P, ws_bytes=_ONE_IMAGE) if det else {}))
+    a.update(over)
+    order = _TN_ORDER + (("ws", "ws_bytes", "stream") if det else ("stream",))
+    return getattr(hw._lib.lib(), "hwgat_linear_tn_%s%s" % (dtype, "_det" if det else ""))(*[a.get(k) for k in order])
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("case", list(_NT_CASES))
+def test_linear_nt_ex_rejects_before_launching(dtype, case):
+    """one case per validation rule of hwgat_linear_nt_{f32,bf16}_ex; the pointers are a 64-float dummy, so every case
+    is one that returns before a launch (the file also runs on GPU machines)"""
+    over, status = _NT_CASES[case]
+    assert _nt_ex(dtype, over) == status
+
+
+def test_linear_nt_ex_k_granule():
+    """K is a multiple of 32 (fp32) / 64 (bf16): K = 32 passes the fp32 shape check (and is then stopped by the missing
+    LayerNorm statistics, so nothing launches) where bf16 refuses the shape; K = 48 is no fp32 shape either"""
+    probe = dict(pro=PRO_LN)
+    assert _nt_ex("f32", dict(probe, K=32)) == EINVAL
+    assert _nt_ex("f32", dict(probe, K=48)) == ESHAPE
+    assert _nt_ex("bf16", dict(probe, K=32)) == ESHAPE
+    assert _nt_ex("bf16", dict(probe, K=64)) == EINVAL
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("det", [False, True], ids=["atomic", "det"])
+@pytest.mark.parametrize("case", list(_TN_CASES))
+def test_linear_tn_rejects_before_launching(dtype, det, case):
+    over, status = _TN_CASES[case]
+    assert _tn(dtype, det, over) == status
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("case", list(_DET_CASES))
+def test_linear_tn_det_rejects_before_launching(dtype, case):
+    """the deterministic form wants a workspace of at least one image and whole 32-row stages"""
+    over, status = _DET_CASES[case]
+    assert _tn(dtype, True, over) == status
+
+
+def test_linear_sizing_functions_return_the_recorded_values():
+    """hwgat_linear_tn_{f32,bf16}_ws_bytes and hwgat_linear_tn_det_bytes over the grid of
+    tests/golden/make_fixtures_linear_sizes.py: the numbers follow from the M-split rules of the dW launchers, and the
+    file was recorded from the library that still carried one hand-written copy of the rule per kernel"""
+    L = hw._lib.lib()
+    funcs = ("hwgat_linear_tn_f32_ws_bytes", "hwgat_linear_tn_bf16_ws_bytes", "hwgat_linear_tn_det_bytes")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "linear_sizes.txt")) as fh:
+        rows = [[int(v) for v in ln.split()] for ln in fh if not ln.startswith("#")]
+    assert len(rows) == 8 * 12
+    assert any(r[3] > 0 for r in rows) and any(r[4] > 0 for r in rows) and all(r[5] > 0 for r in rows)
+    got = [[M, N, K] + [getattr(L, f)(M, N, K) for f in funcs] for M, N, K, *_ in rows]
+    assert got == rows, [(g, r) for g, r in zip(got, rows) if g != r][:4]
 
 
 @pytest.mark.parametrize("family", ["HWGATE", "HGATE", "WGATE"])
