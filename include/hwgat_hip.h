@@ -65,6 +65,7 @@ extern "C" {
  *         fused smoothed cross-entropy; hwgat_eval_accumulate, hwgat_eval_acc_bytes, the device-side evaluation accumulators;
  *         hwgat_ln_param_grads_from_g, the first block's norm1 / qkv parameter gradients without an input gradient;
  *         hwgat_optim_{set,advance,step}, Adam / AdamW over a device table with device-resident hyper-parameters;
+ *         hwgat_sgd_{set,advance,step} and hwgat_nadam_{set,advance,step}, SGD and NAdam in the same form;
  *         hwgat_head_{fwd,bwd_dx,bwd_dw}, the classifier head */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
@@ -531,6 +532,62 @@ int hwgat_optim_set(double* hyper, int group, double lr, double beta1, double be
                     int decoupled, void* stream);
 int hwgat_optim_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived, void* stream);
 int hwgat_optim_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks, void* stream);
+
+/* ---- SGD and NAdam in the same form (reference: cfg.optimizer_type 'sgd' / 'nadam', hwgat/utils.py:73-84; torch.optim.SGD
+ * and torch.optim.NAdam with maximize = False).  With hwgat_optim_* above, every optimizer type of the reference has a
+ * set / advance / step triple whose launches can be captured in a HIP graph.  Parameters, gradients and state are fp32.
+ *
+ * table: `n` hwgat_opt_entry records in DEVICE memory, sorted by first_block, workgroups assigned as for hwgat_optim_step
+ *   (HWGAT_OPTIM_CHUNK elements each).  s0 / s1 are the tensor's state arrays, w0 / w1 its own scalar device words:
+ *     SGD    s0 = momentum buffer, w0 = "stepped before" word (0.0f = never, anything else = yes); s1 = w1 = NULL.
+ *            s0 = w0 = NULL for a tensor of a group without momentum: nothing but p and g is touched then.
+ *     NAdam  s0 = exp_avg, s1 = exp_avg_sq, w0 = step count, w1 = mu_product (torch's state["step"] and
+ *            state["mu_product"] of a capturable NAdam); all four required.
+ *   A tensor whose p, g and state arrays are all 16-byte aligned moves in 16-byte vectors, any other element by element;
+ *   both give the same bits.
+ * hyper: HWGAT_OPTIM_NHYPER fp64 words per group:
+ *     SGD    { lr, momentum, dampening, weight_decay, nesterov (0 / 1), 0, 0, 0 }
+ *     NAdam  { lr, beta1, beta2, eps, weight_decay, coupled (0 = decoupled decay, 1 = decay added to the gradient),
+ *              momentum_decay, 0 }
+ * derived: HWGAT_OPT_NDERIVED fp32 words per table entry, written by *_advance and read by *_step.
+ *
+ * hwgat_sgd_set / hwgat_nadam_set: one thread writes group `group` of `hyper` from the host doubles given as arguments.
+ * hwgat_sgd_advance:   one thread per entry: when the group's momentum != 0 and the entry has a buffer, first = (*w0 == 0),
+ *                      then *w0 = 1; the entry's fp32 scalars (lr, weight_decay, momentum, 1 - dampening, flags) rounded
+ *                      from fp64 once.
+ * hwgat_sgd_step:      for each element, in fp32 (fused multiply-adds as written, nothing else contracted):
+ *                        g' = g + wd p
+ *                        with a buffer:   buf = first ? g' : (1 - dampening) g' + momentum buf   (a select: the old
+ *                                         contents of a never-stepped buffer are not used, as torch clones the gradient)
+ *                                         d = nesterov ? g' + momentum buf : buf
+ *                        without:         d = g'
+ *                        p = p - lr d
+ *                      12 bytes per element without a buffer, 20 with one.
+ * hwgat_nadam_advance: one thread per entry, in fp64: t = *w0 + 1, *w0 = t; mu = beta1 (1 - 0.5 * 0.96^(t momentum_decay)),
+ *                      mu' the same at t + 1; *w1 = (float)(*w1 * mu); then the entry's fp32 scalars, among them
+ *                      1 - beta2^t, cg = lr (1 - mu) / (1 - *w1) and cm = lr mu' / (1 - *w1 mu').
+ * hwgat_nadam_step:    for each element, in fp32:
+ *                        p = p - (lr wd) p                       decoupled   |   g = g + wd p    coupled
+ *                        m = m + (1 - beta1) (g - m)
+ *                        v = ((1 - beta2) g) g + beta2 v
+ *                        denom = sqrt(v / (1 - beta2^t)) + eps
+ *                        p = p - cg (g / denom);   p = p - cm (m / denom)
+ *                      28 bytes per element.
+ * total_blocks = the sum of the entries' workgroups.  No atomics, no reductions: bit-reproducible. */
+#define HWGAT_OPT_NDERIVED 16
+typedef struct {
+    float* p; const float* g; float* s0; float* s1; float* w0; float* w1;
+    int64_t n;
+    int32_t group, first_block;
+} hwgat_opt_entry;
+int hwgat_sgd_set(double* hyper, int group, double lr, double momentum, double dampening, double weight_decay,
+                  int nesterov, void* stream);
+int hwgat_sgd_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream);
+int hwgat_sgd_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream);
+int hwgat_nadam_set(double* hyper, int group, double lr, double beta1, double beta2, double eps, double weight_decay,
+                    double momentum_decay, int decoupled, void* stream);
+int hwgat_nadam_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream);
+int hwgat_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream);
 
 /* the dropout mask the fused kernels use: out[i] = keep(seed, i) ? 1/(1-p) : 0 */
 int hwgat_dropout_mask_f32(float* out, int64_t n, uint32_t seed, float p, const uint32_t* seed_base, void* stream);

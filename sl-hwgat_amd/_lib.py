@@ -130,6 +130,12 @@ _SIGS = {
     "hwgat_optim_set": [_P, _I, _D, _D, _D, _D, _D, _I, _P],
     "hwgat_optim_advance": [_P, _I, _P, _P, _P],
     "hwgat_optim_step": [_P, _I, _P, _I, _P],
+    "hwgat_sgd_set": [_P, _I, _D, _D, _D, _D, _I, _P],
+    "hwgat_sgd_advance": [_P, _I, _P, _P, _P],
+    "hwgat_sgd_step": [_P, _I, _P, _I, _P],
+    "hwgat_nadam_set": [_P, _I, _D, _D, _D, _D, _D, _D, _I, _P],
+    "hwgat_nadam_advance": [_P, _I, _P, _P, _P],
+    "hwgat_nadam_step": [_P, _I, _P, _I, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

@@ -11,6 +11,7 @@ checkpoint written by either side loads on the other:
                                                    key exists in the model AND the shapes agree, reports the rest
   load_checkpoint               utils.py:216-237   weights as above + optimizer / scheduler state, start epoch, 4 lists
   get_optimizer / get_scheduler utils.py:71-88     AdamW(lr) by default; CosineAnnealingLR(T_max=20, last_epoch=-1)
+  get_device_optimizer          utils.py:71-82     the same four optimizer types on this backend's HIP kernels
 """
 from typing import Optional
 
@@ -23,7 +24,8 @@ def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused:
                   device_step: bool = False):
     """utils.py:71-82 (configs.py:84: lr 5e-4, 'adamw').  `fused=True` selects torch's single-launch AdamW on a GPU.
     `device_step=True` returns optim.DeviceAdamW for 'adamw' / 'adam' (torch's defaults: weight decay 0.01 / 0), the HIP
-    optimizer that train.GraphedTrainStep captures inside its graph; 'nadam' / 'sgd' have no such kernels."""
+    optimizer that train.GraphedTrainStep captures inside its graph; for 'nadam' / 'sgd' this keyword raises: use
+    `get_device_optimizer`, which covers all four types."""
     # ALL parameters, as the reference passes them (utils.py:76: model.parameters()): the frozen Fourier matrix `B`
     # is an nn.Parameter and therefore entry 0 of the param group, so optimizer_state_dict files interchange with the
     # reference's AdamW (param-group sizes must match).  AdamW skips parameters whose grad is None: B gets no update.
@@ -33,12 +35,31 @@ def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused:
         raise ValueError(f"optimizer_type {optimizer_type!r}: one of {sorted(kinds)}")
     if device_step:
         if optimizer_type not in ("adamw", "adam"):
-            raise ValueError(f"device_step=True: optimizer_type {optimizer_type!r} has no HIP kernels ('adamw' or 'adam')")
+            raise ValueError(f"device_step=True: only 'adamw' or 'adam', not {optimizer_type!r}; "
+                             "get_device_optimizer() returns the HIP optimizer of every type")
         from .optim import DeviceAdamW
         adamw = optimizer_type == "adamw"
         return DeviceAdamW(params, lr=lr, weight_decay=1e-2 if adamw else 0.0, decoupled_weight_decay=adamw)
     kw = {"fused": fused} if fused is not None and optimizer_type in ("adamw", "adam") else {}
     return kinds[optimizer_type](params, lr=lr, **kw)
+
+
+def get_device_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw"):
+    """utils.py:71-82 on the HIP optimizers (optim.DeviceAdamW / DeviceNAdam / DeviceSGD), which train.GraphedTrainStep
+    captures inside its graph: ALL parameters in one group, as `get_optimizer` passes them, and the values the reference's
+    `Class(model.parameters(), lr=cfg.lr)` leaves at torch's defaults -- AdamW weight decay 0.01, Adam and NAdam 0, SGD
+    without momentum."""
+    from . import optim
+    params = list(model.parameters())
+    if optimizer_type == "adamw":
+        return optim.DeviceAdamW(params, lr=lr, weight_decay=1e-2, decoupled_weight_decay=True)
+    if optimizer_type == "adam":
+        return optim.DeviceAdamW(params, lr=lr, weight_decay=0.0, decoupled_weight_decay=False)
+    if optimizer_type == "nadam":
+        return optim.DeviceNAdam(params, lr=lr)
+    if optimizer_type == "sgd":
+        return optim.DeviceSGD(params, lr=lr)
+    raise ValueError(f"optimizer_type {optimizer_type!r}: one of ['adam', 'adamw', 'nadam', 'sgd']")
 
 
 def get_scheduler(optimizer, scheduler: Optional[str] = "CosineAnnealingLR"):

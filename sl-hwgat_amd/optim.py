@@ -1,14 +1,16 @@
-"""AdamW / Adam on the HIP kernels of csrc/optim.hip (reference: the torch.optim.AdamW that hwgat/utils.py:71-82 builds
-and utils.py:93-116 steps).  One launch updates every parameter tensor of the model from a table in device memory, and
-every hyper-parameter is a device word the kernels read when they run, so `train.GraphedTrainStep` captures this
-optimizer's step inside its graph: a replay is the whole train step, under any torch LR scheduler.
+"""The reference's optimizer types on HIP kernels (reference: hwgat/utils.py:73-84 builds `Class(model.parameters(),
+lr=cfg.lr)` for cfg.optimizer_type 'adamw' / 'adam' / 'nadam' / 'sgd', utils.py:93-116 steps it): DeviceAdamW (AdamW and
+Adam, csrc/optim.hip), DeviceSGD and DeviceNAdam (csrc/optim_family.hip).  One launch updates every parameter tensor of
+the model from a table in device memory, and every hyper-parameter is a device word the kernels read when they run, so
+`train.GraphedTrainStep` captures any of these optimizers' step inside its graph: a replay is the whole train step, under
+any torch LR scheduler.
 
-The state is torch's: `param_groups` carry the keys of torch.optim.AdamW, `state[p]` is {"step": 0-d fp32 device
-tensor, "exp_avg", "exp_avg_sq"}, and those ARE the tensors the kernels read and write (a caller may seat them itself
-before the first step, e.g. as views of one flat arena), so `state_dict()` interchanges
-with torch.optim.AdamW (and the reference's) in both directions and `checkpoint.save_checkpoint` / `load_checkpoint`
-work unchanged.  There is no CPU fallback: the object can be built, inspected and (de)serialised on CPU tensors, `step()`
-on them raises.
+The state is torch's: `param_groups` carry the keys of the torch class, `state[p]` is what that class keeps ({"step": 0-d
+fp32 device tensor, "exp_avg", "exp_avg_sq"} for AdamW, the same plus "mu_product" for NAdam, {"momentum_buffer"} for SGD
+with momentum, nothing for SGD without), and those ARE the tensors the kernels read and write (a caller may seat them
+itself before the first step, e.g. as views of one flat arena), so `state_dict()` interchanges with the torch class (and
+the reference's) in both directions and `checkpoint.save_checkpoint` / `load_checkpoint` work unchanged.  There is no CPU
+fallback: the objects can be built, inspected and (de)serialised on CPU tensors, `step()` on them raises.
 """
 import struct
 
@@ -16,38 +18,51 @@ import torch
 
 from ._lib import call, ptr, stream
 
-CHUNK = 4096            # HWGAT_OPTIM_CHUNK: elements per workgroup of hwgat_optim_step
+CHUNK = 4096            # HWGAT_OPTIM_CHUNK: elements per workgroup of a step kernel
 NHYPER = 8              # HWGAT_OPTIM_NHYPER: fp64 words per group
-NDERIVED = 8            # HWGAT_OPTIM_NDERIVED: fp32 words per table entry
+NDERIVED = 8            # HWGAT_OPTIM_NDERIVED: fp32 words per table entry of hwgat_optim_*
 # hwgat_optim_entry: p, g, m, v, step (pointers), n (int64), group, first_block (int32)
 ENTRY = struct.Struct("<5QqIi")
 ENTRY_BYTES = ENTRY.size
-_STATE_KEYS = ("step", "exp_avg", "exp_avg_sq")
+FAMILY_NDERIVED = 16    # HWGAT_OPT_NDERIVED: fp32 words per table entry of hwgat_sgd_* / hwgat_nadam_*
+# hwgat_opt_entry: p, g, s0, s1, w0, w1 (pointers), n (int64), group, first_block (int32)
+FAMILY_ENTRY = struct.Struct("<6QqIi")
+FAMILY_ENTRY_BYTES = FAMILY_ENTRY.size
 
 
-def build_table(records, chunk=CHUNK):
-    """records: (p, g, m, v, step addresses, n, group) per tensor that has a gradient, n > 0.  Returns (the packed
-    hwgat_optim_entry array as bytes, [first_block per entry], total_blocks): entry i owns ceil(n_i / chunk) workgroups
-    from first_block_i on."""
+def _pack_table(records, entry, chunk):
     blob, first, total = bytearray(), [], 0
-    for p, g, m, v, step, n, group in records:
+    for rec in records:
+        n = rec[-2]
         if n <= 0:
             raise ValueError("an empty tensor has no table entry")
         first.append(total)
-        blob += ENTRY.pack(p, g, m, v, step, n, group, total)
+        blob += entry.pack(*rec, total)
         total += (n + chunk - 1) // chunk
     if total >= 2 ** 31:
         raise ValueError("more workgroups than one launch holds")
     return bytes(blob), first, total
 
 
+def build_table(records, chunk=CHUNK):
+    """records: (p, g, m, v, step addresses, n, group) per tensor that has a gradient, n > 0.  Returns (the packed
+    hwgat_optim_entry array as bytes, [first_block per entry], total_blocks): entry i owns ceil(n_i / chunk) workgroups
+    from first_block_i on."""
+    return _pack_table(records, ENTRY, chunk)
+
+
+def build_family_table(records, chunk=CHUNK):
+    """the same for hwgat_opt_entry: records are (p, g, s0, s1, w0, w1 addresses -- 0 for an unused one --, n, group)"""
+    return _pack_table(records, FAMILY_ENTRY, chunk)
+
+
 class _Table:
     """one device table + its derived block; `records` is what the device holds (or, while `pending`, will hold)"""
 
-    def __init__(self, capacity, device):
+    def __init__(self, capacity, device, entry_bytes=ENTRY_BYTES, nderived=NDERIVED):
         self.capacity = capacity
-        self.buf = torch.zeros(max(1, capacity) * ENTRY_BYTES, dtype=torch.uint8, device=device)
-        self.derived = torch.zeros(max(1, capacity) * NDERIVED, dtype=torch.float32, device=device)
+        self.buf = torch.zeros(max(1, capacity) * entry_bytes, dtype=torch.uint8, device=device)
+        self.derived = torch.zeros(max(1, capacity) * nderived, dtype=torch.float32, device=device)
         self.records, self.n, self.total, self.pending = None, 0, 0, None
 
     def upload(self, blob):
@@ -55,12 +70,16 @@ class _Table:
         self.pending = None
 
 
-class DeviceAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW (decoupled_weight_decay=True) or Adam (False) with amsgrad = maximize = False on fp32
-    parameters.  `step()`: pushes the param-group values that differ from what the device holds (hwgat_optim_set, one
-    tiny launch per changed group), revalidates the table against the current (parameter, gradient) addresses -- a tuple
-    compare; rebuilt and uploaded only on change -- then issues hwgat_optim_advance and hwgat_optim_step.  A parameter
-    whose grad is None is skipped and gets no state, as in torch.
+class DeviceOptimizer(torch.optim.Optimizer):
+    """What the device optimizers share: the fp32 / one-device checks, the fp64 hyper-parameter block with its host
+    mirror (`push_hyper`), the device table keyed by the (parameter, gradient) addresses, `begin_capture` / `end_capture`,
+    `load_state_dict` into the live tensors, and `snapshot_state` / `restore_state`.  A subclass names its three entry
+    points and its record, says which tensors a parameter's state consists of, and turns a param group into the values
+    its `set` entry point takes.
+
+    `step()`: pushes the param-group values that differ from what the device holds (one tiny `set` launch per changed
+    group), revalidates the table against the current addresses -- a tuple compare; rebuilt and uploaded only on change --
+    then issues `advance` and `step`.  A parameter whose grad is None is skipped and gets no state, as in torch.
 
     Capturing `step()` in a HIP graph: the gradients of a capture come from the graph's pool, so the table the graph's
     launches read is a new one.  `begin_capture()` (before the capture; allocates it) ... the capture, with `step()`
@@ -69,142 +88,147 @@ class DeviceAdamW(torch.optim.Optimizer):
     capture (`push_hyper()`), and before each replay call `push_hyper()` again: it launches only when something changed.
     `train.GraphedTrainStep` does all of this."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled_weight_decay=True,
-                 amsgrad=False, maximize=False):
-        if amsgrad:
-            raise ValueError("DeviceAdamW: amsgrad=True is not supported")
-        if maximize:
-            raise ValueError("DeviceAdamW: maximize=True is not supported")
-        if not 0.0 <= float(lr):
-            raise ValueError(f"invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"invalid epsilon: {eps}")
-        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"invalid betas: {betas}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"invalid weight_decay: {weight_decay}")
-        # exactly the keys torch's own class writes into a state_dict, whatever the torch version
-        like = torch.optim.AdamW if decoupled_weight_decay else torch.optim.Adam
-        defaults = dict(like([torch.nn.Parameter(torch.zeros(1))]).defaults)
-        defaults.update(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        capturable=True, decoupled_weight_decay=bool(decoupled_weight_decay))
+    _SET = _ADVANCE = _STEP = None       # entry points
+    _PACK = staticmethod(build_table)
+    _ENTRY_BYTES, _NDERIVED = ENTRY_BYTES, NDERIVED
+    _STATE_KEYS = ()                     # state[p], in torch's order
+    _SCALAR_KEYS = ()                    # those of them that are one fp32 word
+    _PRIVATE_KEYS = ()                   # per-tensor device words that are not part of state[p] / state_dict()
+    _INITIAL = {}                        # fresh value of a key; 0 when absent
+    _CAPTURABLE = True                   # the torch class has a `capturable` key
+    _REFILL_ON_LOAD = True               # a load without state for a live parameter exposes its zeroed tensors again
+
+    def __init__(self, params, defaults):
         self._dev = None
-        self._live = {}              # parameter -> (step, exp_avg, exp_avg_sq): the tensors the device tables point at
-        self._key = None             # ((p address, g address) ...) of the eager table
+        self._live = {}              # parameter -> {key: tensor}: the tensors the device tables point at
+        self._key = None             # what the eager table was built from
         self._table = None
         self._capture = None
         self._hyper = None           # device block, NHYPER fp64 per group
         self._held = []              # host mirror of it, one tuple per group
         super().__init__(params, defaults)
 
+    @property
+    def _name(self):
+        return type(self).__name__
+
     # ---- construction-time checks
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
         for p in self.param_groups[-1]["params"]:
             if p.dtype != torch.float32:
-                raise ValueError(f"DeviceAdamW needs float32 parameters, got {p.dtype}")
+                raise ValueError(f"{self._name} needs float32 parameters, got {p.dtype}")
         self._key = self._dev = None
 
     def _params(self):
         return [p for g in self.param_groups for p in g["params"]]
-
-    # ---- hyper-parameters
-    @staticmethod
-    def _group_values(group):
-        if group.get("amsgrad", False):
-            raise ValueError("DeviceAdamW: amsgrad=True is not supported")
-        if group.get("maximize", False):
-            raise ValueError("DeviceAdamW: maximize=True is not supported")
-        b1, b2 = group["betas"]
-        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                bool(group.get("decoupled_weight_decay", True)))
 
     def _device(self):
         if self._dev is not None:
             return self._dev
         ps = self._params()
         if not ps or not all(p.is_cuda for p in ps):
-            raise RuntimeError("DeviceAdamW.step needs its parameters on an MI355X device; there is no CPU fallback")
+            raise RuntimeError(f"{self._name}.step needs its parameters on an MI355X device; there is no CPU fallback")
         if any(p.device != ps[0].device for p in ps):
-            raise ValueError("DeviceAdamW needs all parameters on one device")
+            raise ValueError(f"{self._name} needs all parameters on one device")
         self._dev = ps[0].device                 # checked once per set of parameters
         return self._dev
 
+    # ---- hyper-parameters
+    def _set_args(self, vals):
+        """the arguments of the `set` entry point between `group` and `stream`, from a `_group_values` tuple"""
+        raise NotImplementedError
+
     def push_hyper(self):
-        """make the device block hold what `param_groups` say: one hwgat_optim_set launch per group that changed"""
+        """make the device block hold what `param_groups` say: one `set` launch per group that changed"""
         n = len(self.param_groups)
         if self._hyper is None or self._hyper.numel() < n * NHYPER:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("DeviceAdamW: take one eager step (or push_hyper()) before capturing")
+                raise RuntimeError(f"{self._name}: take one eager step (or push_hyper()) before capturing")
             self._hyper = torch.zeros(n * NHYPER, dtype=torch.float64, device=self._device())
             self._held = [None] * n
         for i, group in enumerate(self.param_groups):
             vals = self._group_values(group)
             if vals != self._held[i]:
                 if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("DeviceAdamW: a hyper-parameter changed inside a capture; push_hyper() before it")
-                call("hwgat_optim_set", ptr(self._hyper), i, *vals[:5], int(vals[5]), stream())
+                    raise RuntimeError(f"{self._name}: a hyper-parameter changed inside a capture; push_hyper() before it")
+                call(self._SET, ptr(self._hyper), i, *self._set_args(vals), stream())
                 self._held[i] = vals
 
-    def device_hyper(self):
-        """what the device block holds, read back: per group {lr, betas, eps, weight_decay, decoupled_weight_decay}"""
-        h = self._hyper.cpu().view(-1, NHYPER).tolist()
-        return [dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], decoupled_weight_decay=r[5] == 0.0)
-                for r in h[:len(self.param_groups)]]
+    def _hyper_rows(self):
+        return self._hyper.cpu().view(-1, NHYPER).tolist()[:len(self.param_groups)]
 
     # ---- state and table
+    def _wants_state(self, group):
+        return True
+
+    def _fresh(self, p, key):
+        shape = () if key in self._SCALAR_KEYS or key in self._PRIVATE_KEYS else p.shape
+        return torch.full(shape, self._INITIAL.get(key, 0.0), dtype=torch.float32, device=p.device)
+
+    def _reset(self, live):
+        for k, t in live.items():
+            t.fill_(self._INITIAL.get(k, 0.0))
+
     def _state_of(self, p, create):
         st = self.state[p]
         if len(st) == 0:
             if not create:
-                raise RuntimeError("DeviceAdamW: a parameter would get its state inside a capture; warm up with one eager step")
+                raise RuntimeError(f"{self._name}: a parameter would get its state inside a capture; warm up with one eager step")
             if p in self._live:                  # had state before (a load_state_dict without it): same tensors, fresh
                 live = self._live[p]
-                for t in live:
-                    t.zero_()
+                self._reset(live)
             else:
-                live = (torch.zeros((), dtype=torch.float32, device=p.device),
-                        torch.zeros_like(p, memory_format=torch.contiguous_format),
-                        torch.zeros_like(p, memory_format=torch.contiguous_format))
+                live = {k: self._fresh(p, k) for k in self._STATE_KEYS + self._PRIVATE_KEYS}
                 self._live[p] = live
-            st.update(zip(_STATE_KEYS, live))
+            st.update((k, live[k]) for k in self._STATE_KEYS)
         elif p not in self._live:                # state seated by the caller (e.g. views of a flat arena): adopt it
-            live = tuple(st[k] for k in _STATE_KEYS)
-            step, m, v = live
-            if not (step.dtype == m.dtype == v.dtype == torch.float32 and step.numel() == 1 and m.shape == v.shape == p.shape
-                    and m.is_contiguous() and v.is_contiguous() and step.device == m.device == v.device == p.device):
-                raise ValueError("DeviceAdamW: state tensors must be float32 on the parameter's device, the moments "
-                                 "contiguous and of its shape, the step count one element")
+            live = {k: st[k] for k in self._STATE_KEYS}
+            for k, t in live.items():
+                ok = t.dtype == torch.float32 and t.device == p.device
+                ok = ok and (t.numel() == 1 if k in self._SCALAR_KEYS else t.shape == p.shape and t.is_contiguous())
+                if not ok:
+                    raise ValueError(f"{self._name}: state tensors must be float32 on the parameter's device, the arrays "
+                                     "contiguous and of its shape, the scalars one element")
+            live.update((k, self._fresh(p, k)) for k in self._PRIVATE_KEYS)
             self._live[p] = live
         return st
 
+    def _record(self, p, g, live, gi):
+        """one table record, (addresses ..., n, group); `live` is None for a tensor without state"""
+        raise NotImplementedError
+
     def table_records(self, create=True):
-        """(p, g, m, v, step addresses, n, group) of every non-empty parameter that has a gradient, in group order;
-        creates the state of a parameter the first time it has one"""
+        """the table record of every non-empty parameter that has a gradient, in group order; creates the state of a
+        parameter the first time it has one"""
         recs = []
         for gi, group in enumerate(self.param_groups):
+            wants = self._wants_state(group)
             for p in group["params"]:
                 g = p.grad
                 if g is None or p.numel() == 0:
                     continue
                 if g.is_sparse:
-                    raise ValueError("DeviceAdamW does not support sparse gradients")
+                    raise ValueError(f"{self._name} does not support sparse gradients")
                 if g.dtype != torch.float32 or not g.is_contiguous() or not p.is_contiguous() or g.shape != p.shape:
-                    raise ValueError("DeviceAdamW needs contiguous float32 parameters and gradients of one shape")
-                st = self._state_of(p, create)
-                recs.append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                             st["step"].data_ptr(), p.numel(), gi))
+                    raise ValueError(f"{self._name} needs contiguous float32 parameters and gradients of one shape")
+                if wants:
+                    self._state_of(p, create)
+                recs.append(self._record(p, g, self._live[p] if wants else None, gi))
         return recs
 
     def _address_key(self):
         return tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in self._params())
+
+    def _new_table(self, capacity, device):
+        return _Table(capacity, device, self._ENTRY_BYTES, self._NDERIVED)
 
     def _fill(self, table, defer):
         recs = self.table_records(create=not defer)
         table.records = recs
         table.n = len(recs)
         if recs:
-            blob, _, table.total = build_table(recs)
+            blob, _, table.total = self._PACK(recs)
             if defer:
                 table.pending = blob
             else:
@@ -213,7 +237,7 @@ class DeviceAdamW(torch.optim.Optimizer):
     def begin_capture(self):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("begin_capture() goes before the capture")
-        self._capture = _Table(len(self._params()), self._device())
+        self._capture = self._new_table(len(self._params()), self._device())
 
     def end_capture(self):
         """upload the table the captured launches read; returns it (the graph's owner keeps it alive)"""
@@ -235,47 +259,281 @@ class DeviceAdamW(torch.optim.Optimizer):
         if torch.cuda.is_current_stream_capturing():
             table = self._capture
             if table is None:
-                raise RuntimeError("DeviceAdamW: begin_capture() before a capture that holds step()")
+                raise RuntimeError(f"{self._name}: begin_capture() before a capture that holds step()")
             if table.records is None:
                 self._fill(table, defer=True)
             elif self.table_records(create=False) != table.records:   # a later step of the same capture: same tensors
-                raise RuntimeError("DeviceAdamW: the steps of one capture must see the same parameters and gradients")
+                raise RuntimeError(f"{self._name}: the steps of one capture must see the same parameters and gradients")
         else:
             key = self._address_key()
-            if self._table is None or self._table.capacity < len(key):
-                self._table, self._key = _Table(len(key), dev), None
+            if self._table is None or self._table.capacity < len(self._params()):
+                self._table, self._key = self._new_table(len(self._params()), dev), None
             table = self._table
             if key != self._key:
                 self._fill(table, defer=False)
                 self._key = key
         if table.n:
-            call("hwgat_optim_advance", ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), stream())
-            call("hwgat_optim_step", ptr(table.buf), table.n, ptr(table.derived), table.total, stream())
+            call(self._ADVANCE, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), stream())
+            call(self._STEP, ptr(table.buf), table.n, ptr(table.derived), table.total, stream())
         return loss
+
+    # ---- what a warm-up must not leave behind (train.GraphedTrainStep): every state tensor and private word
+    @torch.no_grad()
+    def snapshot_state(self):
+        """clones of every tensor of `state` and of every private per-tensor word, for `restore_state`"""
+        snap = {}
+        for p, st in self.state.items():
+            snap[p] = {k: v.clone() for k, v in st.items() if torch.is_tensor(v)}
+        for p, live in self._live.items():
+            snap.setdefault(p, {}).update((k, live[k].clone()) for k in self._PRIVATE_KEYS)
+        return snap
+
+    @torch.no_grad()
+    def restore_state(self, snap):
+        """put back what `snapshot_state` saw, in place; a tensor that did not exist then becomes a fresh one (zero; 1 for
+        NAdam's mu_product; "never stepped" for SGD's private word), so that state created since looks newly made"""
+        def put(p, k, t):
+            if p in snap and k in snap[p]:
+                t.copy_(snap[p][k])
+            else:
+                t.fill_(self._INITIAL.get(k, 0.0))
+        for p, st in self.state.items():
+            for k, v in st.items():
+                if torch.is_tensor(v):
+                    put(p, k, v)
+        for p, live in self._live.items():
+            for k in self._PRIVATE_KEYS:
+                put(p, k, live[k])
 
     # ---- (de)serialisation: the loaded values go INTO the live tensors, whose addresses device tables (a captured
     # graph's among them) hold
+    def _loaded(self, st):
+        """{key: value} of the live tensors, from one parameter's loaded state; None when that state holds nothing a
+        step would use"""
+        return {k: (torch.as_tensor(st.get(k, self._INITIAL.get(k, 0.0)), dtype=torch.float32).reshape(())
+                    if k in self._SCALAR_KEYS else st[k]) for k in self._STATE_KEYS}
+
     @torch.no_grad()
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         for group in self.param_groups:
             self._group_values(group)
-            group["capturable"] = True
+            if self._CAPTURABLE:
+                group["capturable"] = True
             for p in group["params"]:
                 st, live = self.state.get(p), self._live.get(p)
-                if not st:
+                new = self._loaded(st) if st else None
+                if new is None:
+                    if st is not None:
+                        del self.state[p]
                     if live is not None:         # the file has no state for it: fresh state in the same tensors
-                        for t in live:
-                            t.zero_()
-                        self.state[p].update(zip(_STATE_KEYS, live))
+                        self._reset(live)
+                        if self._REFILL_ON_LOAD:
+                            self.state[p].update((k, live[k]) for k in self._STATE_KEYS)
                     continue
-                new = (torch.as_tensor(st.get("step", 0.0), dtype=torch.float32).reshape(()),
-                       st["exp_avg"], st["exp_avg_sq"])
                 if live is None:
-                    live = tuple(t.detach().to(device=p.device, dtype=torch.float32).contiguous().clone() for t in new)
+                    live = {k: torch.as_tensor(t).detach().to(device=p.device, dtype=torch.float32).contiguous().clone()
+                            for k, t in new.items()}
+                    live.update((k, self._fresh(p, k)) for k in self._PRIVATE_KEYS if k not in new)
                     self._live[p] = live
                 else:
-                    for dst, src in zip(live, new):
-                        dst.copy_(src.to(device=dst.device, dtype=torch.float32).reshape(dst.shape))
-                st.update(zip(_STATE_KEYS, live))
+                    for k, src in new.items():
+                        dst = live[k]
+                        dst.copy_(torch.as_tensor(src).to(device=dst.device, dtype=torch.float32).reshape(dst.shape))
+                st.update((k, live[k]) for k in self._STATE_KEYS)
         self._key = None
+
+
+class DeviceAdamW(DeviceOptimizer):
+    """torch.optim.AdamW (decoupled_weight_decay=True) or Adam (False) with amsgrad = maximize = False on fp32
+    parameters, on hwgat_optim_set / hwgat_optim_advance / hwgat_optim_step (csrc/optim.hip).  See DeviceOptimizer for
+    `step()` and for capturing it in a HIP graph."""
+
+    _SET, _ADVANCE, _STEP = "hwgat_optim_set", "hwgat_optim_advance", "hwgat_optim_step"
+    _STATE_KEYS = ("step", "exp_avg", "exp_avg_sq")
+    _SCALAR_KEYS = ("step",)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled_weight_decay=True,
+                 amsgrad=False, maximize=False):
+        if amsgrad:
+            raise ValueError("DeviceAdamW: amsgrad=True is not supported")
+        if maximize:
+            raise ValueError("DeviceAdamW: maximize=True is not supported")
+        if not 0.0 <= float(lr):
+            raise ValueError(f"invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"invalid epsilon: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"invalid betas: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"invalid weight_decay: {weight_decay}")
+        # exactly the keys torch's own class writes into a state_dict, whatever the torch version
+        like = torch.optim.AdamW if decoupled_weight_decay else torch.optim.Adam
+        defaults = dict(like([torch.nn.Parameter(torch.zeros(1))]).defaults)
+        defaults.update(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        capturable=True, decoupled_weight_decay=bool(decoupled_weight_decay))
+        super().__init__(params, defaults)
+
+    @staticmethod
+    def _group_values(group):
+        if group.get("amsgrad", False):
+            raise ValueError("DeviceAdamW: amsgrad=True is not supported")
+        if group.get("maximize", False):
+            raise ValueError("DeviceAdamW: maximize=True is not supported")
+        b1, b2 = group["betas"]
+        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                bool(group.get("decoupled_weight_decay", True)))
+
+    def _set_args(self, vals):
+        return (*vals[:5], int(vals[5]))
+
+    def device_hyper(self):
+        """what the device block holds, read back: per group {lr, betas, eps, weight_decay, decoupled_weight_decay}"""
+        return [dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], decoupled_weight_decay=r[5] == 0.0)
+                for r in self._hyper_rows()]
+
+    def _record(self, p, g, live, gi):
+        """(p, g, m, v, step addresses, n, group)"""
+        return (p.data_ptr(), g.data_ptr(), live["exp_avg"].data_ptr(), live["exp_avg_sq"].data_ptr(),
+                live["step"].data_ptr(), p.numel(), gi)
+
+
+def _refuse_unsupported(name, group):
+    if group.get("maximize", False):
+        raise ValueError(f"{name}: maximize=True is not supported")
+    if group.get("differentiable", False):
+        raise ValueError(f"{name}: differentiable=True is not supported")
+
+
+class DeviceSGD(DeviceOptimizer):
+    """torch.optim.SGD with maximize = False on fp32 parameters, on hwgat_sgd_set / hwgat_sgd_advance / hwgat_sgd_step
+    (csrc/optim_family.hip).  `state[p]` is torch's: {"momentum_buffer"} in a group whose momentum is not 0, nothing
+    otherwise.  Torch's SGD keeps no step count; that a tensor's FIRST buffer is the gradient itself (torch clones it,
+    whatever the dampening) is decided on the device from a private per-tensor word, which is not part of `state_dict()`:
+    a buffer the caller seats before the first step is storage and counts as never stepped, one that arrives through
+    `load_state_dict` counts as stepped.  A group whose momentum moves between 0 and non-zero is given (or stops using)
+    its buffers at the next eager `step()`; after a capture that is refused, because the captured table cannot change."""
+
+    _SET, _ADVANCE, _STEP = "hwgat_sgd_set", "hwgat_sgd_advance", "hwgat_sgd_step"
+    _PACK = staticmethod(build_family_table)
+    _ENTRY_BYTES, _NDERIVED = FAMILY_ENTRY_BYTES, FAMILY_NDERIVED
+    _STATE_KEYS = ("momentum_buffer",)
+    _PRIVATE_KEYS = ("stepped",)
+    _CAPTURABLE = False
+    _REFILL_ON_LOAD = False              # no buffer in the file: torch would clone the next gradient, and so does this
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, maximize=False,
+                 differentiable=False):
+        defaults = dict(torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=1e-3).defaults)
+        defaults.update(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
+                        maximize=bool(maximize), differentiable=bool(differentiable))
+        self._group_values(defaults)
+        self._captured_momentum = None   # per group, whether the last captured table has buffers
+        super().__init__(params, defaults)
+
+    @staticmethod
+    def _group_values(group):
+        _refuse_unsupported("DeviceSGD", group)
+        lr, mom, damp, wd = (float(group[k]) for k in ("lr", "momentum", "dampening", "weight_decay"))
+        if not 0.0 <= lr:
+            raise ValueError(f"invalid learning rate: {lr}")
+        if not 0.0 <= mom:
+            raise ValueError(f"invalid momentum value: {mom}")
+        if not 0.0 <= wd:
+            raise ValueError(f"invalid weight_decay value: {wd}")
+        if group["nesterov"] and (mom <= 0.0 or damp != 0.0):
+            raise ValueError("nesterov momentum requires a momentum and zero dampening")
+        return (lr, mom, damp, wd, bool(group["nesterov"]))
+
+    def _set_args(self, vals):
+        return (*vals[:4], int(vals[4]))
+
+    def push_hyper(self):
+        if self._captured_momentum is not None:
+            now = [float(g["momentum"]) != 0.0 for g in self.param_groups]
+            if now != self._captured_momentum:
+                raise ValueError("DeviceSGD: a group's momentum moved between 0 and non-zero after a capture, and the "
+                                 "captured table has no momentum buffer for it (or one it must no longer use): capture again")
+        super().push_hyper()
+
+    def end_capture(self):
+        table = super().end_capture()
+        if table is not None and table.records is not None:
+            self._captured_momentum = [float(g["momentum"]) != 0.0 for g in self.param_groups]
+        return table
+
+    def device_hyper(self):
+        """what the device block holds, read back: per group {lr, momentum, dampening, weight_decay, nesterov}"""
+        return [dict(lr=r[0], momentum=r[1], dampening=r[2], weight_decay=r[3], nesterov=r[4] != 0.0)
+                for r in self._hyper_rows()]
+
+    def _wants_state(self, group):
+        return float(group["momentum"]) != 0.0
+
+    def _record(self, p, g, live, gi):
+        """(p, g, momentum buffer, 0, stepped word, 0 addresses, n, group); the buffer and the word 0 without momentum"""
+        if live is None:
+            return (p.data_ptr(), g.data_ptr(), 0, 0, 0, 0, p.numel(), gi)
+        return (p.data_ptr(), g.data_ptr(), live["momentum_buffer"].data_ptr(), 0, live["stepped"].data_ptr(), 0,
+                p.numel(), gi)
+
+    def _address_key(self):
+        return super()._address_key() + tuple(self._wants_state(g) for g in self.param_groups)
+
+    def _loaded(self, st):
+        if st.get("momentum_buffer") is None:
+            return None
+        return {"momentum_buffer": st["momentum_buffer"], "stepped": 1.0}
+
+
+class DeviceNAdam(DeviceOptimizer):
+    """torch.optim.NAdam (both values of decoupled_weight_decay) with maximize = False on fp32 parameters, on
+    hwgat_nadam_set / hwgat_nadam_advance / hwgat_nadam_step (csrc/optim_family.hip).  `state[p]` is that of a capturable
+    torch NAdam: {"step", "mu_product": 0-d fp32 device tensors, "exp_avg", "exp_avg_sq"}."""
+
+    _SET, _ADVANCE, _STEP = "hwgat_nadam_set", "hwgat_nadam_advance", "hwgat_nadam_step"
+    _PACK = staticmethod(build_family_table)
+    _ENTRY_BYTES, _NDERIVED = FAMILY_ENTRY_BYTES, FAMILY_NDERIVED
+    _STATE_KEYS = ("step", "mu_product", "exp_avg", "exp_avg_sq")
+    _SCALAR_KEYS = ("step", "mu_product")
+    _INITIAL = {"mu_product": 1.0}
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, momentum_decay=4e-3,
+                 decoupled_weight_decay=False, maximize=False, differentiable=False):
+        defaults = dict(torch.optim.NAdam([torch.nn.Parameter(torch.zeros(1))]).defaults)
+        defaults.update(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, momentum_decay=momentum_decay,
+                        decoupled_weight_decay=bool(decoupled_weight_decay), maximize=bool(maximize), capturable=True,
+                        differentiable=bool(differentiable))
+        self._group_values(defaults)
+        super().__init__(params, defaults)
+
+    @staticmethod
+    def _group_values(group):
+        _refuse_unsupported("DeviceNAdam", group)
+        lr, eps, wd, md = (float(group[k]) for k in ("lr", "eps", "weight_decay", "momentum_decay"))
+        b1, b2 = (float(b) for b in group["betas"])
+        if not 0.0 <= lr:
+            raise ValueError(f"invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"invalid epsilon: {eps}")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"invalid betas: {group['betas']}")
+        if not 0.0 <= wd:
+            raise ValueError(f"invalid weight_decay: {wd}")
+        if not 0.0 <= md:
+            raise ValueError(f"invalid momentum_decay: {md}")
+        return (lr, b1, b2, eps, wd, md, bool(group.get("decoupled_weight_decay", False)))
+
+    def _set_args(self, vals):
+        return (*vals[:6], int(vals[6]))
+
+    def device_hyper(self):
+        """what the device block holds, read back: per group {lr, betas, eps, weight_decay, momentum_decay,
+        decoupled_weight_decay}"""
+        return [dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], momentum_decay=r[6],
+                     decoupled_weight_decay=r[5] == 0.0) for r in self._hyper_rows()]
+
+    def _record(self, p, g, live, gi):
+        """(p, g, m, v, step, mu_product addresses, n, group)"""
+        return (p.data_ptr(), g.data_ptr(), live["exp_avg"].data_ptr(), live["exp_avg_sq"].data_ptr(),
+                live["step"].data_ptr(), live["mu_product"].data_ptr(), p.numel(), gi)

@@ -91,7 +91,8 @@ class TrainStep:
 
 
 class GraphedTrainStep:
-    """The train step -- seed advance, forward, loss, backward and, with an `optim.DeviceAdamW`, the optimizer step --
+    """The train step -- seed advance, forward, loss, backward and, with a device optimizer (`optim.DeviceAdamW`,
+    `optim.DeviceSGD`, `optim.DeviceNAdam`), the optimizer step --
     captured ONCE in a HIP graph and replayed per call: one graph launch instead of ~400 kernels issued one by one from Python
     (reference loop: hwgat/utils.py:93-116, which issues its ~40 ATen ops per block the same way).  Why it matters here: the bf16 steps
     of the sibling models are 10-17 ms, within 10 % of what one Python thread can issue, and a node runs 8 such ranks
@@ -104,12 +105,15 @@ class GraphedTrainStep:
     records it like torch's own kernels.  Capture follows the torch.cuda.graphs recipe (warm-up on a side stream, then
     `torch.cuda.graph`), in THIS process: nothing is re-launched or exec'ed.
 
-    The optimizer.  With `optim.DeviceAdamW` the step is two more nodes of the graph (hwgat_optim_advance,
+    The optimizer.  With an `optim.DeviceOptimizer` (AdamW / Adam, SGD, NAdam: every optimizer type of the reference) the
+    step is two more nodes of the graph (the class's `advance` and `step` entry points, e.g. hwgat_optim_advance and
     hwgat_optim_step): its hyper-parameters are fp64 device words that the kernels read when they run, so `__call__` only
-    pushes the param groups' values when they changed (hwgat_optim_set, one tiny launch, e.g. after `scheduler.step()`) and
-    replays; the optimizer's Python `step` is not entered, and a replay is the whole train step.  The kernels and their
-    inputs are the eager step's, so a replay and an eager TrainStep step agree bit for bit under `deterministic_train`,
-    with any scheduler (tests/test_gpu_optim.py).
+    pushes the param groups' values when they changed (its `set` entry point, one tiny launch, e.g. after
+    `scheduler.step()`) and replays; the optimizer's Python `step` is not entered, and a replay is the whole train step.
+    The kernels and their inputs are the eager step's, so a replay and an eager TrainStep step agree bit for bit under
+    `deterministic_train`, with any scheduler (tests/test_gpu_optim.py, tests/test_gpu_optim_family.py).  The warm-up's
+    traces in the optimizer are undone through its `snapshot_state` / `restore_state`, DeviceSGD's private
+    "stepped before" words included: the first replay of a fresh SGD with momentum sets its buffers to the gradient.
 
     With any other optimizer the step stays out of the graph and is issued right after the replay, so that it reads the
     param groups' hyper-parameters when it runs: a float lr captured in the graph would be frozen there (an lr scheduler
@@ -131,11 +135,11 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep needs device inputs")
         if not model.training:
             raise ValueError("GraphedTrainStep captures the train() step: call model.train() first")
+        self.in_graph = isinstance(optimizer, importlib.import_module(__package__ + ".optim").DeviceOptimizer)
         for grp in optimizer.param_groups:
-            if not grp.get("capturable", False):
+            if not self.in_graph and not grp.get("capturable", False):
                 raise ValueError("the optimizer must be built with capturable=True (its step count then lives on the device)")
         self.model, self.opt, self.reducer = model, optimizer, reducer
-        self.in_graph = isinstance(optimizer, importlib.import_module(__package__ + ".optim").DeviceAdamW)
         self.criterion = criterion or SmoothedCrossEntropyLoss()
         self.x, self.y = x.detach().clone(), y.detach().clone()
         start = int(model._drop_calls)
@@ -145,7 +149,10 @@ class GraphedTrainStep:
         # warm-up (allocator, weight-prep caches, optimizer state) on a side stream with the weights and the optimizer
         # state put back afterwards, so that capture changes nothing the caller can observe
         keep_p = [p.detach().clone() for p in model.parameters()]
-        keep_state = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in optimizer.state.items()}
+        if self.in_graph:                                # also the words the optimizer keeps to itself (DeviceSGD's)
+            keep_state = optimizer.snapshot_state()
+        else:
+            keep_state = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in optimizer.state.items()}
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 self._one()
@@ -153,13 +160,16 @@ class GraphedTrainStep:
         with torch.no_grad():
             for p, q in zip(model.parameters(), keep_p):
                 p.copy_(q)
-            for p, st in optimizer.state.items():        # moments / step counters: back to what they were (zero if new)
-                for k, v in st.items():
-                    if torch.is_tensor(v):
-                        if p in keep_state and k in keep_state[p]:
-                            v.copy_(keep_state[p][k])
-                        else:
-                            v.zero_()
+            if self.in_graph:                            # state back to what it was, fresh where it is new
+                optimizer.restore_state(keep_state)
+            else:
+                for p, st in optimizer.state.items():    # moments / step counters: back to what they were (zero if new)
+                    for k, v in st.items():
+                        if torch.is_tensor(v):
+                            if p in keep_state and k in keep_state[p]:
+                                v.copy_(keep_state[p][k])
+                            else:
+                                v.zero_()
         del keep_p, keep_state
         model.device_seed_counter = True                 # from here on the device counts the steps itself
         self.graph = torch.cuda.CUDAGraph()

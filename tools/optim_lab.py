@@ -1,22 +1,26 @@
 #!/usr/bin/env python3
-"""What the HIP AdamW (optim.DeviceAdamW, csrc/optim.hip) costs and buys, measured on the device.  Two parts, each a child
-process of its own under its own time limit (a part that fails ends the run; nothing is started after it):
+"""What the HIP optimizers (optim.DeviceAdamW / DeviceSGD / DeviceNAdam, csrc/optim.hip and csrc/optim_family.hip) cost and
+buy, measured on the device.  Two parts, each a child process of its own under its own time limit (a part that fails ends
+the run; nothing is started after it):
 
   step   one optimizer step on the trainable parameters of HWGATE at BASELINE config 2 and of HGATE (random gradients),
-         torch.optim.AdamW(fused=True, capturable=True) against DeviceAdamW, alternated, `--repeats` windows each:
+         once per class (or for the one `--optimizer adamw|sgd|nadam` names): torch's fastest variant of the class against
+         the device class, alternated, `--repeats` windows each.  Torch's variant: AdamW(fused=True, capturable=True); SGD(fused=True)
+         (with `--momentum`, default 0 as in the reference's call); NAdam(foreach=True, capturable=True) -- it has no
+         fused form.
            device   HIP events around replays of ONE graph that holds `--chain` steps back to back (no host between the
                     kernels), `--steps` steps per window: the device time of a step
            eager    HIP events around `--steps` steps issued from Python: the larger of issue time and device time
            issue    perf_counter around the same calls, no synchronise inside the window: the host time of one call
-         and for DeviceAdamW the bytes hwgat_optim_step moves, from shapes (p, g, m, v read; p, m, v written: 28 bytes per
-         element), over the device time of its step (which includes the one-block hwgat_optim_advance), as a share of
-         the 8 TB/s HBM peak.
+         and for the device class the bytes its step kernel moves, from shapes (AdamW and NAdam: p, g, m, v read; p, m, v
+         written: 28 bytes per element; SGD: 12 without momentum, 20 with), over the device time of its step (which
+         includes the one-block advance kernel), as a share of the 8 TB/s HBM peak.
   train  clips/s of train.GraphedTrainStep at fp32 config 2, bf16 config 3 and HGATE bf16, variant A (torch's fused AdamW
          issued after every replay: bench.py --graph) against variant B (DeviceAdamW inside the graph), two models in one
          process, windows alternated A B A B ..., `--repeats` each; host clock around a window that ends in a synchronise.
          The spread of a variant is (max - min) / median over its windows.
 
-  python tools/optim_lab.py [--steps 400] [--txt profiles/optim_lab.txt]
+  python tools/optim_lab.py [--only step] [--optimizer sgd [--momentum 0.9]] [--steps 400] [--txt profiles/optim_lab.txt]
 """
 import argparse
 import importlib
@@ -31,6 +35,7 @@ PARTS = (("step", 240), ("train", 540))                                         
 CFG = dict(B=64, T=128, J=67, nW=5, C=2, d0=128, nc=2002)                       # bench.py CFG (BASELINE configs[1])
 CFG_HGATE = dict(B=64, T=128, J=29, K=29, C=2, d0=128, nc=2002)                 # bench.py CFG_HGATE
 HBM_PEAK = 8.0e12
+CLASSES = ("adamw", "sgd", "nadam")
 
 
 def _gpu():
@@ -60,6 +65,18 @@ def _spread(v):
     return (max(v) - min(v)) / statistics.median(v)
 
 
+def _optimizer(torch, optim, args, name, ps):
+    """`name` "torch": torch's fastest variant of the chosen class; "device": this backend's class"""
+    if args.optimizer == "adamw":
+        return (torch.optim.AdamW(ps, lr=5e-4, fused=True, capturable=True) if name == "torch"
+                else optim.DeviceAdamW(ps, lr=5e-4))
+    if args.optimizer == "sgd":
+        return (torch.optim.SGD(ps, lr=5e-4, momentum=args.momentum, fused=True) if name == "torch"
+                else optim.DeviceSGD(ps, lr=5e-4, momentum=args.momentum))
+    return (torch.optim.NAdam(ps, lr=5e-4, foreach=True, capturable=True) if name == "torch"
+            else optim.DeviceNAdam(ps, lr=5e-4))
+
+
 def part_step(args):
     torch, hw, train, DEV = _gpu()
     optim = importlib.import_module("sl-hwgat_amd.optim")
@@ -75,8 +92,7 @@ def part_step(args):
             ps = [torch.nn.Parameter(torch.randn(s, device=DEV, generator=g) * 0.05) for s in shapes]
             for p in ps:
                 p.grad = torch.randn(p.shape, device=DEV, generator=g) * 1e-2
-            o = (torch.optim.AdamW(ps, lr=5e-4, fused=True, capturable=True) if name == "torch"
-                 else optim.DeviceAdamW(ps, lr=5e-4))
+            o = _optimizer(torch, optim, args, name, ps)
             for _ in range(20):                                  # warm-up: state, code objects, the table
                 o.step()
             torch.cuda.synchronize()
@@ -117,7 +133,8 @@ def part_step(args):
                 res[name, "issue"].append(host)
         n_t = len(shapes)
         blocks = sum(-(-torch.Size(s).numel() // optim.CHUNK) for s in shapes)
-        print(f"step: {kind}, {n_t} trainable tensors, {n_el} elements, {blocks} workgroups of {optim.CHUNK} elements; "
+        what = args.optimizer + (f" (momentum {args.momentum})" if args.optimizer == "sgd" else "")
+        print(f"step: {what}, {kind}, {n_t} trainable tensors, {n_el} elements, {blocks} workgroups of {optim.CHUNK} elements; "
               f"us per optimizer step, {args.steps} steps per window, {args.repeats} windows (median; spread = (max - min) / median)")
         for name in opts:
             line = f"  {name:6s}"
@@ -126,9 +143,10 @@ def part_step(args):
                 line += f"  {how} {statistics.median(v):8.1f} us (spread {100 * _spread(v):.1f} %)"
             print(line)
         dev_us = statistics.median(res["device", "device"])
-        nbytes = 28 * n_el
-        print(f"  hwgat_optim_step moves {nbytes / 1e6:.1f} MB per step (4 arrays read, 3 written): over the device time of "
-              f"DeviceAdamW's step {nbytes / dev_us / 1e6:.2f} TB/s, {100 * nbytes / (dev_us * 1e-6) / HBM_PEAK:.1f} % of the 8 TB/s HBM peak")
+        per_el = 28 if args.optimizer != "sgd" else (20 if args.momentum else 12)
+        nbytes = per_el * n_el
+        print(f"  the step kernel moves {nbytes / 1e6:.1f} MB per step ({per_el} bytes per element): over the device time of "
+              f"the device class's step {nbytes / dev_us / 1e6:.2f} TB/s, {100 * nbytes / (dev_us * 1e-6) / HBM_PEAK:.1f} % of the 8 TB/s HBM peak")
         del opts
     return 0
 
@@ -180,14 +198,20 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--txt", default=os.path.join(ROOT, "profiles", "optim_lab.txt"))
     ap.add_argument("--part", choices=[p for p, _ in PARTS])
+    ap.add_argument("--optimizer", choices=CLASSES, help="class of the step part (default: one step part per class)")
+    ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum of the step part (the reference's call: 0)")
+    ap.add_argument("--only", choices=[p for p, _ in PARTS], help="run this part alone (still as child processes)")
     args = ap.parse_args()
     if args.part:
         return {"step": part_step, "train": part_train}[args.part](args)
     text, ok = [], True
-    for part, limit in PARTS:                  # this process never opens the GPU: every part is a fresh child
+    # this process never opens the GPU: every part, and every class of the step part, is a fresh child
+    runs = [(part, limit, cls) for part, limit in PARTS if args.only in (None, part)
+            for cls in ((args.optimizer,) if args.optimizer else CLASSES if part == "step" else CLASSES[:1])]
+    for part, limit, cls in runs:
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--part", part,
                "--steps", str(args.steps), "--chain", str(args.chain), "--train-steps", str(args.train_steps),
-               "--repeats", str(args.repeats)]
+               "--repeats", str(args.repeats), "--optimizer", cls, "--momentum", str(args.momentum)]
         res = subprocess.run(cmd, capture_output=True, text=True)
         text += res.stdout.splitlines()
         print(res.stdout, end="", flush=True)
