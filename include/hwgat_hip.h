@@ -66,7 +66,9 @@ extern "C" {
  *         hwgat_ln_param_grads_from_g, the first block's norm1 / qkv parameter gradients without an input gradient;
  *         hwgat_optim_{set,advance,step}, Adam / AdamW over a device table with device-resident hyper-parameters;
  *         hwgat_sgd_{set,advance,step} and hwgat_nadam_{set,advance,step}, SGD and NAdam in the same form;
- *         hwgat_head_{fwd,bwd_dx,bwd_dw}, the classifier head */
+ *         hwgat_head_{fwd,bwd_dx,bwd_dw}, the classifier head;
+ *         hwgat_gguard_{set,partial,finish,scale}, the gradient guard (global-norm clipping and non-finite detection on the
+ *         device), and hwgat_gguard_{adamw,sgd,nadam}_{advance,step}, the three optimizers' launches under a guard */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -588,6 +590,64 @@ int hwgat_nadam_set(double* hyper, int group, double lr, double beta1, double be
                     double momentum_decay, int decoupled, void* stream);
 int hwgat_nadam_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream);
 int hwgat_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream);
+
+/* ---- gradient guard: clip all gradients of a model by their global norm (torch.nn.utils.clip_grad_norm_, norm_type 2 or
+ * inf) and turn a step whose gradients hold a NaN or an Inf into a no-op, with every result left in DEVICE memory: nothing
+ * is read back to the host, so the launches below can be captured in a HIP graph together with the optimizer step.
+ *
+ * table / entry_bytes: the optimizer's own table, `n` records of hwgat_optim_entry (entry_bytes = 56) or hwgat_opt_entry
+ *   (entry_bytes = 64) in DEVICE memory; only `g`, `n` and `first_block` of a record are used.  Workgroups are assigned as
+ *   for the step kernels: one workgroup of 256 threads per HWGAT_OPTIM_CHUNK elements of one tensor.
+ * state: HWGAT_GGUARD_NSTATE fp64 words in DEVICE memory, at the HWGAT_GGUARD_* slots below.  The three config words are
+ *   written by hwgat_gguard_set, the others by hwgat_gguard_finish; the caller zeroes the block once.
+ * workspace: 2 * total_blocks fp64 words in DEVICE memory: per workgroup { partial, flags (1 = saw a NaN, 2 = saw an Inf) }.
+ *
+ * hwgat_gguard_set:     one thread writes max_norm (>= 0, +Inf = measure only), norm_type (2 or +Inf) and the mode
+ *                       (skip != 0: a step with a non-finite gradient is skipped; 0: it propagates, as in torch) from the
+ *                       host values given as arguments; stream-ordered like hwgat_optim_set.
+ * hwgat_gguard_partial: per workgroup the sum of g^2 in fp64 (norm_type 2) or max |g| (norm_type Inf) over its chunk:
+ *                       per thread in a fixed element order, then in-wave, then across the four waves through LDS, in a
+ *                       fixed order; one 16-byte store per workgroup, no atomics.  A 16-byte-aligned tensor moves in
+ *                       16-byte vectors, any other element by element; both give every thread the same elements in the
+ *                       same order, hence the same bits.
+ * hwgat_gguard_finish:  one workgroup folds the partials in a fixed order and writes, in fp64:
+ *                         total_norm = sqrt(sum) | max (NaN when a NaN was seen);
+ *                         clip_coef  = c < 1 or c is NaN ? c : 1,   c = max_norm / (total_norm + 1e-6)   (torch's formula);
+ *                         nonfinite  = a NaN or an Inf was seen;   skip = nonfinite && mode == skip;
+ *                         steps += 1;  clipped += (clip_coef < 1 && !skip);  skipped += skip.
+ * hwgat_gguard_scale:   g = g * (float)clip_coef in place for every element of every entry (also when clip_coef == 1: the
+ *                       bits do not change); writes nothing when `skip` is set.  8 bytes per element.
+ * hwgat_gguard_{adamw,sgd,nadam}_{advance,step}: hwgat_optim_* / hwgat_sgd_* / hwgat_nadam_* advance and step with the
+ *                       guard's state block as one more argument: they return at once when `skip` is set, so no step count,
+ *                       "stepped" word, mu_product, parameter or state element is written. */
+#define HWGAT_GGUARD_NSTATE 16
+#define HWGAT_GGUARD_MAX_NORM 0
+#define HWGAT_GGUARD_NORM_TYPE 1
+#define HWGAT_GGUARD_MODE 2
+#define HWGAT_GGUARD_TOTAL_NORM 3
+#define HWGAT_GGUARD_CLIP_COEF 4
+#define HWGAT_GGUARD_NONFINITE 5
+#define HWGAT_GGUARD_SKIP 6
+#define HWGAT_GGUARD_STEPS 7
+#define HWGAT_GGUARD_CLIPPED 8
+#define HWGAT_GGUARD_SKIPPED 9
+int hwgat_gguard_set(double* state, double max_norm, double norm_type, int skip, void* stream);
+int hwgat_gguard_partial(const void* table, int n, int entry_bytes, const double* state, double* workspace,
+                         int total_blocks, void* stream);
+int hwgat_gguard_finish(const double* workspace, int total_blocks, double* state, void* stream);
+int hwgat_gguard_scale(const void* table, int n, int entry_bytes, const double* state, int total_blocks, void* stream);
+int hwgat_gguard_adamw_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived,
+                               const double* guard_state, void* stream);
+int hwgat_gguard_adamw_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks,
+                            const double* guard_state, void* stream);
+int hwgat_gguard_sgd_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived,
+                             const double* guard_state, void* stream);
+int hwgat_gguard_sgd_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks,
+                          const double* guard_state, void* stream);
+int hwgat_gguard_nadam_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived,
+                               const double* guard_state, void* stream);
+int hwgat_gguard_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks,
+                            const double* guard_state, void* stream);
 
 /* the dropout mask the fused kernels use: out[i] = keep(seed, i) ? 1/(1-p) : 0 */
 int hwgat_dropout_mask_f32(float* out, int64_t n, uint32_t seed, float p, const uint32_t* seed_base, void* stream);

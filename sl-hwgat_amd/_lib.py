@@ -136,6 +136,16 @@ _SIGS = {
     "hwgat_nadam_set": [_P, _I, _D, _D, _D, _D, _D, _D, _I, _P],
     "hwgat_nadam_advance": [_P, _I, _P, _P, _P],
     "hwgat_nadam_step": [_P, _I, _P, _I, _P],
+    "hwgat_gguard_set": [_P, _D, _D, _I, _P],
+    "hwgat_gguard_partial": [_P, _I, _I, _P, _P, _I, _P],
+    "hwgat_gguard_finish": [_P, _I, _P, _P],
+    "hwgat_gguard_scale": [_P, _I, _I, _P, _I, _P],
+    "hwgat_gguard_adamw_advance": [_P, _I, _P, _P, _P, _P],
+    "hwgat_gguard_adamw_step": [_P, _I, _P, _I, _P, _P],
+    "hwgat_gguard_sgd_advance": [_P, _I, _P, _P, _P, _P],
+    "hwgat_gguard_sgd_step": [_P, _I, _P, _I, _P, _P],
+    "hwgat_gguard_nadam_advance": [_P, _I, _P, _P, _P, _P],
+    "hwgat_gguard_nadam_step": [_P, _I, _P, _I, _P, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

@@ -44,22 +44,30 @@ def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused:
     return kinds[optimizer_type](params, lr=lr, **kw)
 
 
-def get_device_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw"):
+def get_device_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", max_grad_norm: Optional[float] = None,
+                         on_nonfinite: str = "propagate"):
     """utils.py:71-82 on the HIP optimizers (optim.DeviceAdamW / DeviceNAdam / DeviceSGD), which train.GraphedTrainStep
     captures inside its graph: ALL parameters in one group, as `get_optimizer` passes them, and the values the reference's
     `Class(model.parameters(), lr=cfg.lr)` leaves at torch's defaults -- AdamW weight decay 0.01, Adam and NAdam 0, SGD
-    without momentum."""
+    without momentum.  `max_grad_norm` (clip the gradients to that global 2-norm before every step) and `on_nonfinite`
+    ("skip": a step with a NaN or Inf gradient changes nothing) attach an `optim.GradGuard` as the optimizer's `guard`
+    when either differs from its default; the reference has neither."""
     from . import optim
     params = list(model.parameters())
     if optimizer_type == "adamw":
-        return optim.DeviceAdamW(params, lr=lr, weight_decay=1e-2, decoupled_weight_decay=True)
-    if optimizer_type == "adam":
-        return optim.DeviceAdamW(params, lr=lr, weight_decay=0.0, decoupled_weight_decay=False)
-    if optimizer_type == "nadam":
-        return optim.DeviceNAdam(params, lr=lr)
-    if optimizer_type == "sgd":
-        return optim.DeviceSGD(params, lr=lr)
-    raise ValueError(f"optimizer_type {optimizer_type!r}: one of ['adam', 'adamw', 'nadam', 'sgd']")
+        opt = optim.DeviceAdamW(params, lr=lr, weight_decay=1e-2, decoupled_weight_decay=True)
+    elif optimizer_type == "adam":
+        opt = optim.DeviceAdamW(params, lr=lr, weight_decay=0.0, decoupled_weight_decay=False)
+    elif optimizer_type == "nadam":
+        opt = optim.DeviceNAdam(params, lr=lr)
+    elif optimizer_type == "sgd":
+        opt = optim.DeviceSGD(params, lr=lr)
+    else:
+        raise ValueError(f"optimizer_type {optimizer_type!r}: one of ['adam', 'adamw', 'nadam', 'sgd']")
+    if max_grad_norm is not None or on_nonfinite != "propagate":
+        opt.guard = optim.GradGuard(max_norm=float("inf") if max_grad_norm is None else max_grad_norm,
+                                    on_nonfinite=on_nonfinite)
+    return opt
 
 
 def get_scheduler(optimizer, scheduler: Optional[str] = "CosineAnnealingLR"):

@@ -54,6 +54,25 @@ int hwgat_tn_det_reduce(const float* ws, float* out, int cap, int64_t stride, in
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// the guarded optimizer kernels (optim.hip, optim_family.hip) end at once when the gradient guard's finish kernel
+// (grad_guard.hip) has set the `skip` word of its state block; uniform, one scalar load
+__device__ __forceinline__ bool gguard_skips(const double* __restrict__ guard_state) {
+    return guard_state[HWGAT_GGUARD_SKIP] != 0.0;
+}
+
+// Table-driven launches (hwgat_optim_entry, hwgat_opt_entry: any record with a `first_block`): the entry of this workgroup
+// is the last one whose first_block <= blockIdx.x.  Uniform binary search (a model has ~200 entries; the loads are scalar).
+// optim_family.hip and grad_guard.hip use it; optim_step_k (optim.hip) keeps the loop it was written with
+template <class E>
+__device__ __forceinline__ int entry_of_block(const E* __restrict__ table, int n) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // row index of accumulator register r of v_mfma_f32_32x32x2_f32 for lane half h
 __device__ __forceinline__ constexpr int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 

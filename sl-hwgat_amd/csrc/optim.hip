@@ -14,6 +14,11 @@
 // thread per table entry, adds 1 to the entry's step count and derives the entry's fp32 scalars from the fp64 block (the
 // two pow() and the divisions are done once per tensor, not once per workgroup).  optim_step_k streams the four arrays.
 // No float atomics, no reductions: the result is a pure function of its inputs.
+//
+// With a gradient guard (grad_guard.hip) the advance and step kernels are instantiated a second time, GUARD = true, with
+// the guard's state block as one more argument: both return at once when its `skip` word is set, so a step whose
+// gradients hold a NaN or an Inf changes neither a step count nor a parameter nor a moment.  The GUARD = false
+// instantiations take no such argument and hold no trace of the guard: hwgat_optim_{advance,step} launch those.
 #include "common.h"
 
 namespace {
@@ -30,8 +35,12 @@ __global__ void optim_set_k(double* __restrict__ h, double lr, double beta1, dou
     h[0] = lr; h[1] = beta1; h[2] = beta2; h[3] = eps; h[4] = wd; h[5] = coupled; h[6] = 0.0; h[7] = 0.0;
 }
 
+// GUARD = true: `guard` is one `const double*`, the guard's state block; GUARD = false: an empty pack
+template <bool GUARD, class... G>
 __global__ __launch_bounds__(THREADS) void optim_advance_k(const hwgat_optim_entry* __restrict__ table, int n,
-                                                           const double* __restrict__ hyper, float* __restrict__ derived) {
+                                                           const double* __restrict__ hyper, float* __restrict__ derived,
+                                                           G... guard) {
+    if constexpr (GUARD) { if (gguard_skips(guard...)) return; }
     const int e = blockIdx.x * THREADS + threadIdx.x;
     if (e >= n) return;
     const hwgat_optim_entry en = table[e];
@@ -70,8 +79,10 @@ __device__ __forceinline__ void adam1(const Scalars& s, float& p, float g, float
     p = fmaf(-s.step, m / denom, p);
 }
 
+template <bool GUARD, class... G>
 __global__ __launch_bounds__(THREADS) void optim_step_k(const hwgat_optim_entry* __restrict__ table, int n,
-                                                        const float* __restrict__ derived) {
+                                                        const float* __restrict__ derived, G... guard) {
+    if constexpr (GUARD) { if (gguard_skips(guard...)) return; }
     // entry of this workgroup: the last one whose first_block <= blockIdx.x.  Uniform binary search (a model has ~200
     // entries; the loads are scalar)
     int lo = 0, hi = n - 1;
@@ -137,12 +148,26 @@ extern "C" int hwgat_optim_set(double* hyper, int group, double lr, double beta1
 
 extern "C" int hwgat_optim_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived, void* stream) {
     if (!table || !hyper || !derived || n <= 0) return HWGAT_EINVAL;
-    optim_advance_k<<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived);
+    optim_advance_k<false><<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived);
     HWGAT_LAUNCH_CHECK();
 }
 
 extern "C" int hwgat_optim_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks, void* stream) {
     if (!table || !derived || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;
-    optim_step_k<<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived);
+    optim_step_k<false><<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_gguard_adamw_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived,
+                                          const double* guard_state, void* stream) {
+    if (!table || !hyper || !derived || !guard_state || n <= 0) return HWGAT_EINVAL;
+    optim_advance_k<true><<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived, guard_state);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_gguard_adamw_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks,
+                                       const double* guard_state, void* stream) {
+    if (!table || !derived || !guard_state || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;
+    optim_step_k<true><<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived, guard_state);
     HWGAT_LAUNCH_CHECK();
 }

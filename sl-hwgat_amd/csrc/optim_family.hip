@@ -17,6 +17,11 @@
 // *_advance_k, one thread per table entry, updates the tensor's own scalar state (SGD: the "stepped before" word; NAdam:
 // step count and mu_product) and rounds the entry's fp32 scalars from fp64 once; *_step_k streams the arrays.  No float
 // atomics, no reductions, no LDS: the result is a pure function of its inputs.
+//
+// With a gradient guard (grad_guard.hip) the advance and step kernels are instantiated a second time, GUARD = true, with
+// the guard's state block as one more argument, and return at once when its `skip` word is set: SGD's "stepped" word,
+// NAdam's step count and mu_product, the parameters and the state arrays all stay as they are.  The GUARD = false
+// instantiations take no such argument and hold no trace of the guard: hwgat_{sgd,nadam}_{advance,step} launch those.
 #include "common.h"
 
 namespace {
@@ -40,8 +45,11 @@ __global__ void nadam_set_k(double* __restrict__ h, double lr, double beta1, dou
     h[0] = lr; h[1] = beta1; h[2] = beta2; h[3] = eps; h[4] = wd; h[5] = coupled; h[6] = momentum_decay; h[7] = 0.0;
 }
 
+template <bool GUARD, class... G>
 __global__ __launch_bounds__(THREADS) void sgd_advance_k(const hwgat_opt_entry* __restrict__ table, int n,
-                                                         const double* __restrict__ hyper, float* __restrict__ derived) {
+                                                         const double* __restrict__ hyper, float* __restrict__ derived,
+                                                         G... guard) {
+    if constexpr (GUARD) { if (gguard_skips(guard...)) return; }
     const int e = blockIdx.x * THREADS + threadIdx.x;
     if (e >= n) return;
     const hwgat_opt_entry en = table[e];
@@ -63,8 +71,11 @@ __global__ __launch_bounds__(THREADS) void sgd_advance_k(const hwgat_opt_entry* 
     d[S_HASBUF] = hasbuf ? 1.f : 0.f;
 }
 
+template <bool GUARD, class... G>
 __global__ __launch_bounds__(THREADS) void nadam_advance_k(const hwgat_opt_entry* __restrict__ table, int n,
-                                                           const double* __restrict__ hyper, float* __restrict__ derived) {
+                                                           const double* __restrict__ hyper, float* __restrict__ derived,
+                                                         G... guard) {
+    if constexpr (GUARD) { if (gguard_skips(guard...)) return; }
     const int e = blockIdx.x * THREADS + threadIdx.x;
     if (e >= n) return;
     const hwgat_opt_entry en = table[e];
@@ -123,16 +134,6 @@ __device__ __forceinline__ void nadam1(const NadamScalars& s, float& p, float g,
     p = fmaf(-s.cm, m / denom, p);
 }
 
-// entry of this workgroup: the last one whose first_block <= blockIdx.x.  Uniform binary search (scalar loads)
-__device__ __forceinline__ int find_entry(const hwgat_opt_entry* __restrict__ table, int n) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // one chunk of p, g and NS state arrays through f(p, g, a, b): 16-byte vectors when `aligned`, then (tails of aligned
 // tensors, whole chunks of misaligned ones) one element per lane.  g and the state arrays are touched once per step:
 // nontemporal.  p is read again by the next step's hwgat_weight_prep: plain
@@ -181,9 +182,11 @@ __device__ __forceinline__ void stream_chunk(gfloat* p, const gfloat* g, gfloat*
     }
 }
 
+template <bool GUARD, class... G>
 __global__ __launch_bounds__(THREADS) void sgd_step_k(const hwgat_opt_entry* __restrict__ table, int n,
-                                                      const float* __restrict__ derived) {
-    const int e = find_entry(table, n);
+                                                      const float* __restrict__ derived, G... guard) {
+    if constexpr (GUARD) { if (gguard_skips(guard...)) return; }
+    const int e = entry_of_block(table, n);
     const hwgat_opt_entry en = table[e];
     const float* d = derived + (int64_t)e * HWGAT_OPT_NDERIVED;
     const SgdScalars s = {d[S_LR], d[S_WD], d[S_MOM], d[S_OMD], d[S_NESTEROV] != 0.f, d[S_FIRST] != 0.f};
@@ -205,9 +208,11 @@ __global__ __launch_bounds__(THREADS) void sgd_step_k(const hwgat_opt_entry* __r
     }
 }
 
+template <bool GUARD, class... G>
 __global__ __launch_bounds__(THREADS) void nadam_step_k(const hwgat_opt_entry* __restrict__ table, int n,
-                                                        const float* __restrict__ derived) {
-    const int e = find_entry(table, n);
+                                                        const float* __restrict__ derived, G... guard) {
+    if constexpr (GUARD) { if (gguard_skips(guard...)) return; }
+    const int e = entry_of_block(table, n);
     const hwgat_opt_entry en = table[e];
     const float* d = derived + (int64_t)e * HWGAT_OPT_NDERIVED;
     const NadamScalars s = {d[N_LRWD], d[N_WD], d[N_OMB1], d[N_B2], d[N_OMB2], d[N_BC2], d[N_EPS], d[N_CG], d[N_CM]};
@@ -231,13 +236,13 @@ extern "C" int hwgat_sgd_set(double* hyper, int group, double lr, double momentu
 
 extern "C" int hwgat_sgd_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream) {
     if (!table || !hyper || !derived || n <= 0) return HWGAT_EINVAL;
-    sgd_advance_k<<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived);
+    sgd_advance_k<false><<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived);
     HWGAT_LAUNCH_CHECK();
 }
 
 extern "C" int hwgat_sgd_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream) {
     if (!table || !derived || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;
-    sgd_step_k<<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived);
+    sgd_step_k<false><<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived);
     HWGAT_LAUNCH_CHECK();
 }
 
@@ -251,12 +256,31 @@ extern "C" int hwgat_nadam_set(double* hyper, int group, double lr, double beta1
 
 extern "C" int hwgat_nadam_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream) {
     if (!table || !hyper || !derived || n <= 0) return HWGAT_EINVAL;
-    nadam_advance_k<<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived);
+    nadam_advance_k<false><<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived);
     HWGAT_LAUNCH_CHECK();
 }
 
 extern "C" int hwgat_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream) {
     if (!table || !derived || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;
-    nadam_step_k<<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived);
+    nadam_step_k<false><<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived);
     HWGAT_LAUNCH_CHECK();
 }
+
+// the same launches under a gradient guard (grad_guard.hip): `guard_state` is the guard's HWGAT_GGUARD_NSTATE fp64 words
+#define HWGAT_GUARDED_PAIR(kind)                                                                                          \
+    extern "C" int hwgat_gguard_##kind##_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, \
+                                                 const double* guard_state, void* stream) {                               \
+        if (!table || !hyper || !derived || !guard_state || n <= 0) return HWGAT_EINVAL;                                  \
+        kind##_advance_k<true><<<(n + THREADS - 1) / THREADS, THREADS, 0, (hipStream_t)stream>>>(table, n, hyper, derived, \
+                                                                                                  guard_state);           \
+        HWGAT_LAUNCH_CHECK();                                                                                             \
+    }                                                                                                                     \
+    extern "C" int hwgat_gguard_##kind##_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, \
+                                              const double* guard_state, void* stream) {                                  \
+        if (!table || !derived || !guard_state || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;                       \
+        kind##_step_k<true><<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, derived, guard_state);           \
+        HWGAT_LAUNCH_CHECK();                                                                                             \
+    }
+HWGAT_GUARDED_PAIR(sgd)
+HWGAT_GUARDED_PAIR(nadam)
+#undef HWGAT_GUARDED_PAIR

@@ -11,7 +11,13 @@ with momentum, nothing for SGD without), and those ARE the tensors the kernels r
 itself before the first step, e.g. as views of one flat arena), so `state_dict()` interchanges with the torch class (and
 the reference's) in both directions and `checkpoint.save_checkpoint` / `load_checkpoint` work unchanged.  There is no CPU
 fallback: the objects can be built, inspected and (de)serialised on CPU tensors, `step()` on them raises.
+
+`GradGuard` (csrc/grad_guard.hip) is what a step inside a graph has no other place for: clipping by the global gradient
+norm, as torch.nn.utils.clip_grad_norm_ does it, and a verdict on NaN / Inf gradients, both computed and kept on the
+device.  Attached to a device optimizer (`opt.guard = GradGuard(max_norm=1.0, on_nonfinite="skip")`) it runs between the
+backward and the update in every `step()` and in every replay; `clip_grad_norm_(parameters, guard)` runs it alone.
 """
+import math
 import struct
 
 import torch
@@ -28,6 +34,11 @@ FAMILY_NDERIVED = 16    # HWGAT_OPT_NDERIVED: fp32 words per table entry of hwga
 # hwgat_opt_entry: p, g, s0, s1, w0, w1 (pointers), n (int64), group, first_block (int32)
 FAMILY_ENTRY = struct.Struct("<6QqIi")
 FAMILY_ENTRY_BYTES = FAMILY_ENTRY.size
+
+
+GUARD_NSTATE = 16       # HWGAT_GGUARD_NSTATE: fp64 words of a guard's state block, at the HWGAT_GGUARD_* slots:
+G_MAX_NORM, G_NORM_TYPE, G_MODE, G_TOTAL_NORM, G_CLIP_COEF, G_NONFINITE, G_SKIP, G_STEPS, G_CLIPPED, G_SKIPPED = range(10)
+_COUNTERS = ("steps", "clipped", "skipped")
 
 
 def _pack_table(records, entry, chunk):
@@ -57,17 +68,193 @@ def build_family_table(records, chunk=CHUNK):
 
 
 class _Table:
-    """one device table + its derived block; `records` is what the device holds (or, while `pending`, will hold)"""
+    """one device table + its derived block; `records` is what the device holds (or, while `pending`, will hold).
+    `guard_ws`: a gradient guard's workspace for this table, two fp64 words per workgroup"""
 
     def __init__(self, capacity, device, entry_bytes=ENTRY_BYTES, nderived=NDERIVED):
         self.capacity = capacity
+        self.entry_bytes = entry_bytes
         self.buf = torch.zeros(max(1, capacity) * entry_bytes, dtype=torch.uint8, device=device)
         self.derived = torch.zeros(max(1, capacity) * nderived, dtype=torch.float32, device=device)
         self.records, self.n, self.total, self.pending = None, 0, 0, None
+        self.guard_ws = None
+
+    def reserve_guard_ws(self, blocks):
+        if self.guard_ws is None or self.guard_ws.numel() < 2 * blocks:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("a gradient guard's workspace would be allocated inside a capture: begin_capture() first")
+            self.guard_ws = torch.empty(2 * max(1, blocks), dtype=torch.float64, device=self.buf.device)
 
     def upload(self, blob):
         self.buf[:len(blob)].copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
         self.pending = None
+
+
+class GradGuard:
+    """Clip gradients by their global norm and detect non-finite ones, on the device (csrc/grad_guard.hip).
+
+    `max_norm`: torch.nn.utils.clip_grad_norm_'s; every gradient is multiplied in place by
+    min(1, max_norm / (total_norm + 1e-6)).  inf (the default) measures only: the coefficient is 1.
+    `norm_type`: 2 or inf.
+    `on_nonfinite`: "propagate" is torch's behaviour -- a NaN norm gives a NaN coefficient, NaN gradients and, after the
+    step, NaN weights; "skip" turns a step whose gradients hold a NaN or an Inf into a no-op: the gradients are left
+    unscaled (so they can be inspected) and a guarded optimizer writes no parameter, no state and no step count.
+    All three are plain attributes and may be changed at any time; the new values reach the device, and so a captured
+    graph, with the next `push()` (which `DeviceOptimizer.push_hyper()` and so every step and replay issues).
+
+    Results stay on the device, in one fp64 block that every run rewrites: `total_norm`, `clip_coef` and `nonfinite` are
+    0-d float64 views of it (reading one is the caller's host sync, at the time of its choosing), `counters()` reads
+    {steps, clipped, skipped} in one copy.  The sum of squares is accumulated in fp64 in a fixed order: the norm depends on
+    the gradients' values and sizes alone, not on their alignment, and repeats bit for bit."""
+
+    _MODES = ("propagate", "skip")
+
+    def __init__(self, max_norm=float("inf"), norm_type=2.0, on_nonfinite="propagate"):
+        self.max_norm, self.norm_type, self.on_nonfinite = max_norm, norm_type, on_nonfinite
+        self._config()
+        self._state = None           # device block, GUARD_NSTATE fp64
+        self._held = None            # the config the device holds
+        self._loaded = None          # counters of a load_state_dict() that came before the device block existed
+        self._clip = (None, None)    # clip_grad_norm_'s own table and the addresses it was built from
+
+    def _config(self):
+        """(max_norm, norm_type, skip) as the `set` entry point takes them; refuses what the kernels do not do"""
+        max_norm, norm_type = float(self.max_norm), float(self.norm_type)
+        if not max_norm >= 0.0:
+            raise ValueError(f"GradGuard: max_norm must be >= 0, got {self.max_norm}")
+        if norm_type != 2.0 and norm_type != math.inf:
+            raise ValueError(f"GradGuard: norm_type 2 or inf, got {self.norm_type}")
+        if self.on_nonfinite not in self._MODES:
+            raise ValueError(f"GradGuard: on_nonfinite {self.on_nonfinite!r}: one of {list(self._MODES)}")
+        return max_norm, norm_type, int(self.on_nonfinite == "skip")
+
+    # ---- device side
+    def bind(self, device):
+        """allocate the state block on `device` (once; a guard serves one device)"""
+        device = torch.device(device)
+        if self._state is None:
+            if device.type != "cuda":
+                raise RuntimeError("GradGuard needs an MI355X device; there is no CPU fallback")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("GradGuard: run it once (or bind() and push()) before capturing")
+            self._state = torch.zeros(GUARD_NSTATE, dtype=torch.float64, device=device)
+            if self._loaded is not None:
+                self._put_counters(self._loaded)
+                self._loaded = None
+        elif self._state.device != device:
+            raise ValueError(f"GradGuard lives on {self._state.device}, the gradients on {device}")
+        return self
+
+    def push(self, device=None):
+        """make the device hold the current config: one `set` launch when it changed"""
+        if device is not None:
+            self.bind(device)
+        cfg = self._config()
+        if cfg != self._held:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("GradGuard: the config changed inside a capture; push() before it")
+            call("hwgat_gguard_set", ptr(self._bound()), *cfg, stream())
+            self._held = cfg
+
+    def _bound(self):
+        if self._state is None:
+            raise RuntimeError("GradGuard has not run yet: its results live on the device of its first step (or bind())")
+        return self._state
+
+    def _measure_and_scale(self, table):
+        """partial, finish, scale over `table` (a filled _Table with its workspace reserved)"""
+        st, s = ptr(self._state), stream()
+        call("hwgat_gguard_partial", ptr(table.buf), table.n, table.entry_bytes, st, ptr(table.guard_ws), table.total, s)
+        call("hwgat_gguard_finish", ptr(table.guard_ws), table.total, st, s)
+        call("hwgat_gguard_scale", ptr(table.buf), table.n, table.entry_bytes, st, table.total, s)
+
+    # ---- readouts
+    @property
+    def total_norm(self):
+        return self._bound()[G_TOTAL_NORM]
+
+    @property
+    def clip_coef(self):
+        return self._bound()[G_CLIP_COEF]
+
+    @property
+    def nonfinite(self):
+        return self._bound()[G_NONFINITE]
+
+    def counters(self):
+        """{steps, clipped, skipped} so far: one host read"""
+        if self._state is None:
+            return dict(self._loaded or dict.fromkeys(_COUNTERS, 0))
+        return {k: int(v) for k, v in zip(_COUNTERS, self._state[G_STEPS:G_SKIPPED + 1].tolist())}
+
+    def _put_counters(self, values):
+        self._state[G_STEPS:G_SKIPPED + 1].copy_(torch.tensor([float(values[k]) for k in _COUNTERS], dtype=torch.float64))
+
+    # ---- what a warm-up must not leave behind: the results and the counters (the config is the caller's)
+    def snapshot(self):
+        return None if self._state is None else self._state[G_TOTAL_NORM:].clone()
+
+    def restore(self, snap):
+        if self._state is not None:
+            if snap is None:
+                self._state[G_TOTAL_NORM:].zero_()
+            else:
+                self._state[G_TOTAL_NORM:].copy_(snap)
+
+    # ---- for a checkpoint's own extra key (the reference's nine keys stay as they are)
+    def state_dict(self):
+        return dict(max_norm=float(self.max_norm), norm_type=float(self.norm_type), on_nonfinite=self.on_nonfinite,
+                    **self.counters())
+
+    def load_state_dict(self, sd):
+        keep = (self.max_norm, self.norm_type, self.on_nonfinite)
+        self.max_norm, self.norm_type, self.on_nonfinite = sd["max_norm"], sd["norm_type"], sd["on_nonfinite"]
+        try:
+            self._config()
+        except ValueError:
+            self.max_norm, self.norm_type, self.on_nonfinite = keep
+            raise
+        values = {k: int(sd.get(k, 0)) for k in _COUNTERS}
+        if self._state is None:
+            self._loaded = values
+        else:
+            self._put_counters(values)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, guard):
+    """torch.nn.utils.clip_grad_norm_(parameters, guard.max_norm, guard.norm_type) on the guard's three launches, for the
+    gradients of an optimizer that is not a DeviceOptimizer (a torch optimizer stepped after a GraphedTrainStep replay --
+    e.g. from its `register_step_pre_hook` --, an eager loop).  Returns `guard.total_norm`, a 0-d float64 device tensor:
+    nothing is read back.  The gradients must be contiguous float32 tensors on one device; in "skip" mode the caller
+    decides what a set `guard.nonfinite` means for its own optimizer."""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None and p.grad.numel() > 0]
+    if not grads:
+        raise ValueError("clip_grad_norm_: no gradients")
+    for g in grads:
+        if g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous():
+            raise ValueError("clip_grad_norm_ needs contiguous float32 gradients")
+        if not g.is_cuda:
+            raise RuntimeError("clip_grad_norm_ needs gradients on an MI355X device; there is no CPU fallback")
+        if g.device != grads[0].device:
+            raise ValueError("clip_grad_norm_ needs all gradients on one device")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("clip_grad_norm_ is an eager call; inside a capture attach the guard to a DeviceOptimizer")
+    guard.push(grads[0].device)
+    key = tuple((g.data_ptr(), g.numel()) for g in grads)
+    table, held = guard._clip
+    if key != held:
+        if table is None or table.capacity < len(grads):
+            table = _Table(len(grads), grads[0].device, nderived=0)
+        blob, _, table.total = build_table([(0, a, 0, 0, 0, n, 0) for a, n in key])
+        table.n = len(grads)
+        table.upload(blob)
+        table.reserve_guard_ws(table.total)
+        guard._clip = (table, key)
+    guard._measure_and_scale(table)
+    return guard.total_norm
 
 
 class DeviceOptimizer(torch.optim.Optimizer):
@@ -86,9 +273,15 @@ class DeviceOptimizer(torch.optim.Optimizer):
     inside ... `end_capture()` (after it; uploads the table -- capture executes nothing, so that is early enough -- and
     returns it: keep the returned object alive as long as the graph).  Hyper-parameters must be on the device before the
     capture (`push_hyper()`), and before each replay call `push_hyper()` again: it launches only when something changed.
-    `train.GraphedTrainStep` does all of this."""
+    `train.GraphedTrainStep` does all of this.
+
+    `guard`: a `GradGuard` or None (the default).  It is an attribute of the optimizer, not a param-group key and not part
+    of `state[p]`: `state_dict()` is the torch class's with or without one.  With a guard, `step()` issues the guard's
+    partial, finish and scale launches over the same table and then the guarded `advance` and `step` entry points, which
+    do nothing when the guard decided to skip; without one it issues exactly `advance` and `step`."""
 
     _SET = _ADVANCE = _STEP = None       # entry points
+    _GUARDED_ADVANCE = _GUARDED_STEP = None   # advance and step that take a GradGuard's state block
     _PACK = staticmethod(build_table)
     _ENTRY_BYTES, _NDERIVED = ENTRY_BYTES, NDERIVED
     _STATE_KEYS = ()                     # state[p], in torch's order
@@ -106,6 +299,7 @@ class DeviceOptimizer(torch.optim.Optimizer):
         self._capture = None
         self._hyper = None           # device block, NHYPER fp64 per group
         self._held = []              # host mirror of it, one tuple per group
+        self.guard = None            # a GradGuard, or None
         super().__init__(params, defaults)
 
     @property
@@ -140,7 +334,10 @@ class DeviceOptimizer(torch.optim.Optimizer):
         raise NotImplementedError
 
     def push_hyper(self):
-        """make the device block hold what `param_groups` say: one `set` launch per group that changed"""
+        """make the device block hold what `param_groups` say: one `set` launch per group that changed; and the guard's
+        config, when there is a guard and it changed"""
+        if self.guard is not None:
+            self.guard.push(self._device())
         n = len(self.param_groups)
         if self._hyper is None or self._hyper.numel() < n * NHYPER:
             if torch.cuda.is_current_stream_capturing():
@@ -238,6 +435,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("begin_capture() goes before the capture")
         self._capture = self._new_table(len(self._params()), self._device())
+        if self.guard is not None:           # as many partials as the table can have workgroups at the most
+            self._capture.reserve_guard_ws(sum(-(-p.numel() // CHUNK) for p in self._params()))
 
     def end_capture(self):
         """upload the table the captured launches read; returns it (the graph's owner keeps it alive)"""
@@ -272,9 +471,16 @@ class DeviceOptimizer(torch.optim.Optimizer):
             if key != self._key:
                 self._fill(table, defer=False)
                 self._key = key
-        if table.n:
+        if table.n and self.guard is None:
             call(self._ADVANCE, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), stream())
             call(self._STEP, ptr(table.buf), table.n, ptr(table.derived), table.total, stream())
+        elif table.n:
+            guard = self.guard
+            table.reserve_guard_ws(table.total)
+            guard._measure_and_scale(table)
+            gs = ptr(guard._state)
+            call(self._GUARDED_ADVANCE, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), gs, stream())
+            call(self._GUARDED_STEP, ptr(table.buf), table.n, ptr(table.derived), table.total, gs, stream())
         return loss
 
     # ---- what a warm-up must not leave behind (train.GraphedTrainStep): every state tensor and private word
@@ -286,6 +492,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
             snap[p] = {k: v.clone() for k, v in st.items() if torch.is_tensor(v)}
         for p, live in self._live.items():
             snap.setdefault(p, {}).update((k, live[k].clone()) for k in self._PRIVATE_KEYS)
+        if self.guard is not None:
+            snap[self.guard] = self.guard.snapshot()
         return snap
 
     @torch.no_grad()
@@ -304,6 +512,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
         for p, live in self._live.items():
             for k in self._PRIVATE_KEYS:
                 put(p, k, live[k])
+        if self.guard is not None:           # its results and counters; zero when it first ran after the snapshot
+            self.guard.restore(snap.get(self.guard))
 
     # ---- (de)serialisation: the loaded values go INTO the live tensors, whose addresses device tables (a captured
     # graph's among them) hold
@@ -350,6 +560,7 @@ class DeviceAdamW(DeviceOptimizer):
     `step()` and for capturing it in a HIP graph."""
 
     _SET, _ADVANCE, _STEP = "hwgat_optim_set", "hwgat_optim_advance", "hwgat_optim_step"
+    _GUARDED_ADVANCE, _GUARDED_STEP = "hwgat_gguard_adamw_advance", "hwgat_gguard_adamw_step"
     _STATE_KEYS = ("step", "exp_avg", "exp_avg_sq")
     _SCALAR_KEYS = ("step",)
 
@@ -415,6 +626,7 @@ class DeviceSGD(DeviceOptimizer):
     its buffers at the next eager `step()`; after a capture that is refused, because the captured table cannot change."""
 
     _SET, _ADVANCE, _STEP = "hwgat_sgd_set", "hwgat_sgd_advance", "hwgat_sgd_step"
+    _GUARDED_ADVANCE, _GUARDED_STEP = "hwgat_gguard_sgd_advance", "hwgat_gguard_sgd_step"
     _PACK = staticmethod(build_family_table)
     _ENTRY_BYTES, _NDERIVED = FAMILY_ENTRY_BYTES, FAMILY_NDERIVED
     _STATE_KEYS = ("momentum_buffer",)
@@ -492,6 +704,7 @@ class DeviceNAdam(DeviceOptimizer):
     torch NAdam: {"step", "mu_product": 0-d fp32 device tensors, "exp_avg", "exp_avg_sq"}."""
 
     _SET, _ADVANCE, _STEP = "hwgat_nadam_set", "hwgat_nadam_advance", "hwgat_nadam_step"
+    _GUARDED_ADVANCE, _GUARDED_STEP = "hwgat_gguard_nadam_advance", "hwgat_gguard_nadam_step"
     _PACK = staticmethod(build_family_table)
     _ENTRY_BYTES, _NDERIVED = FAMILY_ENTRY_BYTES, FAMILY_NDERIVED
     _STATE_KEYS = ("step", "mu_product", "exp_avg", "exp_avg_sq")

@@ -115,6 +115,14 @@ class GraphedTrainStep:
     traces in the optimizer are undone through its `snapshot_state` / `restore_state`, DeviceSGD's private
     "stepped before" words included: the first replay of a fresh SGD with momentum sets its buffers to the gradient.
 
+    Clipping and divergence.  A device optimizer that carries an `optim.GradGuard` (`optimizer.guard`) issues the guard's
+    three launches in front of its own two, so they are nodes of the graph as well: every replay clips the gradients by
+    their global norm and, in the guard's "skip" mode, leaves weights, state and step counts alone when a gradient holds
+    a NaN or an Inf.  The norm, the coefficient and the counters stay in device words (`guard.total_norm`,
+    `guard.clip_coef`, `guard.counters()`); a new `guard.max_norm` reaches the next replay like a new lr.  With a
+    `reducer` the guard runs after `reducer.finish()`: each rank sees the all-reduced gradients and so the same norm.
+    The warm-up leaves the guard's counters where they were (zero for a new guard).
+
     With any other optimizer the step stays out of the graph and is issued right after the replay, so that it reads the
     param groups' hyper-parameters when it runs: a float lr captured in the graph would be frozen there (an lr scheduler
     would change nothing), and a tensor lr is read by torch's fused AdamW as float32 -- the float lr rounded, updates that

@@ -1,0 +1,177 @@
+"""CPU: host logic of optim.GradGuard (csrc/grad_guard.hip) -- the new entry points in the header, the binding and the
+library, their argument checks, that a guard changes nothing of an optimizer's state_dict(), the guard's own argument
+errors and state_dict, checkpoint.get_device_optimizer."""
+import copy
+import ctypes
+import importlib
+import math
+import re
+
+import pytest
+import torch
+
+hw = importlib.import_module("sl-hwgat_amd")
+optim = importlib.import_module("sl-hwgat_amd.optim")
+ck = hw.checkpoint
+GUARD_SYMBOLS = ({f"hwgat_gguard_{what}" for what in ("set", "partial", "finish", "scale")}
+                 | {f"hwgat_gguard_{kind}_{what}" for kind in ("adamw", "sgd", "nadam") for what in ("advance", "step")})
+OPTIMIZERS = [(optim.DeviceAdamW, torch.optim.AdamW, dict(lr=2e-3, weight_decay=0.05)),
+              (optim.DeviceSGD, torch.optim.SGD, dict(lr=2e-3, momentum=0.9)),
+              (optim.DeviceNAdam, torch.optim.NAdam, dict(lr=2e-3))]
+
+
+def test_symbols_abi_and_constants_follow_the_header():
+    assert GUARD_SYMBOLS <= set(hw._lib.declared_symbols())
+    assert GUARD_SYMBOLS == {n for n in hw._lib._SIGS if n.startswith("hwgat_gguard_")}
+    assert not any(n.startswith(("hwgat_optim_", "hwgat_sgd_", "hwgat_nadam_")) for n in GUARD_SYMBOLS)
+    L = hw._lib.lib()
+    for name in GUARD_SYMBOLS:                               # exported by the library that was built
+        assert getattr(L, name) is not None
+    assert hw._lib.header_abi_version() == 4006 and L.hwgat_abi_version() == 4006
+    with open(hw._lib.HEADER) as fh:
+        src = fh.read()
+    slots = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+HWGAT_GGUARD_(\w+)\s+(\d+)", src)}
+    assert slots.pop("NSTATE") == optim.GUARD_NSTATE
+    mine = dict(MAX_NORM=optim.G_MAX_NORM, NORM_TYPE=optim.G_NORM_TYPE, MODE=optim.G_MODE, TOTAL_NORM=optim.G_TOTAL_NORM,
+                CLIP_COEF=optim.G_CLIP_COEF, NONFINITE=optim.G_NONFINITE, SKIP=optim.G_SKIP, STEPS=optim.G_STEPS,
+                CLIPPED=optim.G_CLIPPED, SKIPPED=optim.G_SKIPPED)
+    assert slots == mine and sorted(mine.values()) == list(range(10))
+    for cls in (optim.DeviceAdamW, optim.DeviceSGD, optim.DeviceNAdam):
+        assert {cls._GUARDED_ADVANCE, cls._GUARDED_STEP} <= GUARD_SYMBOLS
+
+
+def test_entry_points_refuse_bad_arguments_without_launching():
+    L = hw._lib.lib()
+    buf = ctypes.cast((ctypes.c_double * 64)(), ctypes.c_void_p)      # 16-byte aligned host memory: never dereferenced
+    odd = ctypes.c_void_p(buf.value + 8)
+    inf = math.inf
+    assert L.hwgat_gguard_set(None, 1.0, 2.0, 0, None) == -1
+    for max_norm, norm_type in ((-1.0, 2.0), (math.nan, 2.0), (1.0, 1.0), (1.0, 3.0), (1.0, -inf), (1.0, math.nan)):
+        assert L.hwgat_gguard_set(buf, max_norm, norm_type, 0, None) == -1, (max_norm, norm_type)
+    part, fin, scale = L.hwgat_gguard_partial, L.hwgat_gguard_finish, L.hwgat_gguard_scale
+    for eb in (56, 64):
+        assert part(None, 1, eb, buf, buf, 1, None) == -1
+        assert part(buf, 1, eb, None, buf, 1, None) == -1
+        assert part(buf, 1, eb, buf, None, 1, None) == -1
+        assert part(buf, 1, eb, buf, odd, 1, None) == -1             # the workspace takes 16-byte stores
+        assert part(buf, 0, eb, buf, buf, 1, None) == -1
+        assert part(buf, -1, eb, buf, buf, 1, None) == -1
+        assert part(buf, 1, eb, buf, buf, 0, None) == -1
+        assert scale(None, 1, eb, buf, 1, None) == -1
+        assert scale(buf, 1, eb, None, 1, None) == -1
+        assert scale(buf, 0, eb, buf, 1, None) == -1
+        assert scale(buf, 1, eb, buf, 0, None) == -1
+    for eb in (0, 48, 60, 128):                                      # neither record type
+        assert part(buf, 1, eb, buf, buf, 1, None) == -1
+        assert scale(buf, 1, eb, buf, 1, None) == -1
+    assert fin(None, 1, buf, None) == -1
+    assert fin(odd, 1, buf, None) == -1
+    assert fin(buf, 1, None, None) == -1
+    assert fin(buf, 0, buf, None) == -1
+    for kind in ("adamw", "sgd", "nadam"):
+        advance, step = getattr(L, f"hwgat_gguard_{kind}_advance"), getattr(L, f"hwgat_gguard_{kind}_step")
+        assert advance(buf, 0, buf, buf, buf, None) == -1
+        assert advance(buf, -1, buf, buf, buf, None) == -1
+        for i in range(4):                                           # each pointer in turn
+            args = [buf, buf, buf, buf]
+            args[i] = None
+            assert advance(args[0], 1, args[1], args[2], args[3], None) == -1, (kind, i)
+        assert step(buf, 1, buf, 0, buf, None) == -1
+        assert step(buf, 0, buf, 1, buf, None) == -1
+        assert step(None, 1, buf, 1, buf, None) == -1
+        assert step(buf, 1, None, 1, buf, None) == -1
+        assert step(buf, 1, buf, 1, None, None) == -1
+
+
+@pytest.mark.parametrize("cls, like, kw", OPTIMIZERS, ids=["adamw", "sgd", "nadam"])
+def test_a_guard_is_no_part_of_the_state_dict(cls, like, kw):
+    """the keys are the torch class's with a guard attached, and the dict goes through the torch class and back"""
+    torch.manual_seed(0)
+    theirs = [torch.nn.Parameter(torch.randn(s)) for s in ((3, 5), (7,))]
+    o_t = like(theirs, **kw)
+    for _ in range(2):
+        for p in theirs:
+            p.grad = torch.full_like(p, 0.25)
+        o_t.step()
+    mine = [torch.nn.Parameter(p.detach().clone()) for p in theirs]
+    plain, guarded = cls(mine, **kw), cls(mine, **kw)
+    assert plain.guard is None
+    guarded.guard = optim.GradGuard(max_norm=1.0, on_nonfinite="skip")
+    for o in (plain, guarded):
+        o.load_state_dict(copy.deepcopy(o_t.state_dict()))
+    a, b, t = plain.state_dict(), guarded.state_dict(), o_t.state_dict()
+    assert a.keys() == b.keys() == t.keys()
+    assert b["param_groups"][0].keys() == a["param_groups"][0].keys() == t["param_groups"][0].keys()
+    assert "guard" not in guarded.param_groups[0] and "guard" not in guarded.defaults
+    assert b["state"].keys() == t["state"].keys()
+    for k in t["state"]:
+        assert b["state"][k].keys() == a["state"][k].keys() == t["state"][k].keys()
+    back = like([torch.nn.Parameter(p.detach().clone()) for p in theirs], **kw)
+    back.load_state_dict(copy.deepcopy(b))
+    for k in t["state"]:
+        for name, v in t["state"][k].items():
+            assert torch.equal(torch.as_tensor(back.state_dict()["state"][k][name]).float(), torch.as_tensor(v).float()), name
+    # snapshot / restore with a guard that has not run: nothing to keep, nothing breaks
+    guarded.restore_state(guarded.snapshot_state())
+    assert guarded.guard.counters() == dict(steps=0, clipped=0, skipped=0)
+
+
+def test_guard_argument_errors_and_state_dict():
+    for bad in (dict(norm_type=1), dict(norm_type=1.0), dict(norm_type=0.0), dict(norm_type=-math.inf),
+                dict(max_norm=-1.0), dict(max_norm=math.nan), dict(on_nonfinite="raise"), dict(on_nonfinite=None)):
+        with pytest.raises(ValueError):
+            optim.GradGuard(**bad)
+    g = optim.GradGuard()
+    assert (g.max_norm, g.norm_type, g.on_nonfinite) == (math.inf, 2.0, "propagate")
+    optim.GradGuard(max_norm=0.0, norm_type=math.inf, on_nonfinite="skip")
+    optim.GradGuard(norm_type=2)
+    g.norm_type = 1                                          # a bad value set later is refused when it is next used
+    with pytest.raises(ValueError, match="norm_type"):
+        g.push()
+    with pytest.raises(RuntimeError, match="not run yet"):
+        g.total_norm
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        optim.GradGuard().bind("cpu")
+    # config and counters travel through state_dict(), before the guard has a device
+    g = optim.GradGuard(max_norm=0.5, norm_type=math.inf, on_nonfinite="skip")
+    assert g.state_dict() == dict(max_norm=0.5, norm_type=math.inf, on_nonfinite="skip", steps=0, clipped=0, skipped=0)
+    h = optim.GradGuard()
+    h.load_state_dict(dict(g.state_dict(), steps=7, clipped=3, skipped=1))
+    assert h.state_dict() == dict(max_norm=0.5, norm_type=math.inf, on_nonfinite="skip", steps=7, clipped=3, skipped=1)
+    assert h.counters() == dict(steps=7, clipped=3, skipped=1)
+    with pytest.raises(ValueError):
+        h.load_state_dict(dict(g.state_dict(), norm_type=1.0))
+    assert h.norm_type == math.inf                           # a refused load changes nothing
+
+
+@pytest.mark.parametrize("cls, like, kw", OPTIMIZERS, ids=["adamw", "sgd", "nadam"])
+def test_step_with_a_guard_on_cpu_parameters_raises(cls, like, kw):
+    p = torch.nn.Parameter(torch.zeros(4))
+    p.grad = torch.ones(4)
+    o = cls([p], **kw)
+    o.guard = optim.GradGuard(max_norm=1.0)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        o.step()
+    assert torch.equal(p.detach(), torch.zeros(4)) and torch.equal(p.grad, torch.ones(4))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        optim.clip_grad_norm_([p], optim.GradGuard(max_norm=1.0))
+    assert torch.equal(p.grad, torch.ones(4))
+
+
+def test_get_device_optimizer_attaches_a_guard():
+    hp = hw.HWGATEParams({"src_len": 16, "num_class": 5}, 2, torch.device("cpu"), num_kps=32)
+    model = hw.Model(*hp.get_model_params())
+    for kind in ("adamw", "adam", "nadam", "sgd"):
+        assert ck.get_device_optimizer(model, optimizer_type=kind).guard is None
+        o = ck.get_device_optimizer(model, optimizer_type=kind, max_grad_norm=1.5)
+        assert isinstance(o.guard, optim.GradGuard)
+        assert (o.guard.max_norm, o.guard.norm_type, o.guard.on_nonfinite) == (1.5, 2.0, "propagate")
+        plain = ck.get_device_optimizer(model, optimizer_type=kind)
+        assert o.state_dict().keys() == plain.state_dict().keys()
+        assert o.param_groups[0].keys() == plain.param_groups[0].keys()
+        o = ck.get_device_optimizer(model, optimizer_type=kind, on_nonfinite="skip")
+        assert (o.guard.max_norm, o.guard.on_nonfinite) == (math.inf, "skip")
+    with pytest.raises(ValueError, match="on_nonfinite"):
+        ck.get_device_optimizer(model, on_nonfinite="stop")
+    with pytest.raises(ValueError, match="max_norm"):
+        ck.get_device_optimizer(model, max_grad_norm=-1.0)
