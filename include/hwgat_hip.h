@@ -68,7 +68,8 @@ extern "C" {
  *         hwgat_sgd_{set,advance,step} and hwgat_nadam_{set,advance,step}, SGD and NAdam in the same form;
  *         hwgat_head_{fwd,bwd_dx,bwd_dw}, the classifier head;
  *         hwgat_gguard_{set,partial,finish,scale}, the gradient guard (global-norm clipping and non-finite detection on the
- *         device), and hwgat_gguard_{adamw,sgd,nadam}_{advance,step}, the three optimizers' launches under a guard */
+ *         device), and hwgat_gguard_{adamw,sgd,nadam}_{advance,step}, the three optimizers' launches under a guard;
+ *         hwgat_bsce_{fwd,bwd}, the smoothed cross-entropy of one slice of a zero-padded batch (additions only) */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -885,6 +886,26 @@ int64_t hwgat_eval_acc_bytes(int C, int k_max, int64_t cap);
 int hwgat_eval_accumulate(void* acc, const float* row_loss, const int32_t* rank, const int32_t* pred,
                           const int64_t* target, const float* loss, const int32_t* n_valid, int64_t B, int C, int k_max,
                           int64_t cap, void* stream);
+
+/* ---- the same loss for one SLICE of a zero-padded batch (train.BatchSlicedCrossEntropyLoss: micro-batches and short
+ * batches in one captured train step).  The batch holds *n_rows real rows (a DEVICE int32, read when the kernels run)
+ * followed by padding; the slice is its rows [offset, offset + B), `offset` a host integer in [0, 2^31).  The slice's
+ * first v = clamp(*n_rows - offset, 0, B) rows are live; logits (B, C), target (B) and the limits on B and C are
+ * hwgat_sce_fwd's.  A NULL pointer (n_rows included) or an offset out of range is HWGAT_EINVAL.
+ * hwgat_bsce_fwd (three launches: v, the rows, the sums):
+ *   live[0]     = v
+ *   lse, row_loss, rank, pred: hwgat_sce_fwd's, bit for bit, for the live rows; the other rows are neither read nor written
+ *   loss[0]     = sum of row_loss over the live rows, in a fixed order, divided by *n_rows: the slice's share of the
+ *                 BATCH mean, so the losses of a batch's slices add up to its mean loss.  v = 0 gives exactly 0, not the
+ *                 NaN of an empty mean
+ *   correct[0]  = number of live rows with rank 0
+ * hwgat_bsce_bwd: dlogits[b, j] = g[0] / *n_rows * (exp(z[b, j] - lse[b]) - (1 - eps) [j == t] - eps / C) for a live row,
+ *   exactly 0.0f for every other; a live row with a bad target is NaN throughout.  No float atomic anywhere. */
+int hwgat_bsce_fwd(const float* logits, const int64_t* target, const int32_t* n_rows, int64_t offset, float* lse,
+                   float* row_loss, int32_t* rank, int32_t* pred, float* loss, int64_t* correct, int32_t* live, int64_t B,
+                   int C, float eps, void* stream);
+int hwgat_bsce_bwd(const float* logits, const int64_t* target, const int32_t* n_rows, int64_t offset, const float* lse,
+                   const float* g, float* dlogits, int64_t B, int C, float eps, void* stream);
 
 /* ---- the classifier head (csrc/head.hip; reference: the `head` / `classifier` nn.Linear of every model,
  * hwgat/models/HWGATE.py:331,372).  Everything fp32 and row-major; W is (N, K) as nn.Linear stores it.

@@ -125,6 +125,8 @@ _SIGS = {
     "hwgat_dgcn_masked_sum": [_P, _P, _P, _P, _P, _L, _P],
     "hwgat_sce_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
     "hwgat_sce_bwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
+    "hwgat_bsce_fwd": [_P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
+    "hwgat_bsce_bwd": [_P, _P, _P, _L, _P, _P, _P, _L, _I, _F, _P],
     "hwgat_eval_acc_bytes": [_I, _I, _L],
     "hwgat_eval_accumulate": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _L, _P],
     "hwgat_optim_set": [_P, _I, _D, _D, _D, _D, _D, _I, _P],

@@ -208,32 +208,32 @@ class _FusedBlock(torch.autograd.Function):
         if doutm is not None and doutm.shape == dout.shape:
             # the consumer of this block's output already wrote dropmask3 * dout (hwgat_ln_bwd_masked): no hashing here
             doutm = doutm.contiguous()
-            dwq.run(lambda: HF.linear_tn(doutm, u, dw2, db2, deterministic=det))
+            dwq.run(lambda: HF.linear_tn(doutm, u, dw2, db2, deterministic=det, pad_stage=True))
             d_h1 = HF.linear_nt(doutm, wT("w2T", w2), None, epi=HF.EPI_MUL_AUX, aux=h1)
         else:
-            dwq.run(lambda: HF.linear_tn(dout, u, dw2, db2, pro_seed=seeds[2], pro_p=p, seed_base=sb, deterministic=det))
+            dwq.run(lambda: HF.linear_tn(dout, u, dw2, db2, pro_seed=seeds[2], pro_p=p, seed_base=sb, deterministic=det, pad_stage=True))
             d_h1 = HF.linear_nt(dout, wT("w2T", w2), None, pro=HF.PRO_DROP, pro_seed=seeds[2], pro_p=p,
                                 epi=HF.EPI_MUL_AUX, aux=h1, seed_base=sb)
         xn_path = HF.dw_wants_xn(x)               # LN(x) written by the LayerNorm backward for the dW launches (bf16, d % 256 == 0)
         if not xn_path:
-            dwq.run(lambda: HF.linear_tn(d_h1, y, dw1, db1, ln=(m2, r2, n2w, n2b), deterministic=det))
+            dwq.run(lambda: HF.linear_tn(d_h1, y, dw1, db1, ln=(m2, r2, n2w, n2b), deterministic=det, pad_stage=True))
         d_z = HF.linear_nt(d_h1, wT("w1T", w1), None, epi=HF.EPI_NONE)
         # ---- attention branch: y = x + drop1(o Wp^T + bp)
         if p > 0.0 and HF.MASK_ONCE >= 1 and d >= HF.MASK_ONCE_MIN_D:
             if xn_path:
                 d_y, d_ym, yn = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, mask=(seeds[0], p), beta=n2b, seed_base=sb, deterministic=det)
-                dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det))
+                dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det, pad_stage=True))
             else:
                 d_y, d_ym = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, mask=(seeds[0], p), seed_base=sb, deterministic=det)   # + shortcut; and dropmask1 * d_y
-            dwq.run(lambda: HF.linear_tn(d_ym, o, dwp, dbp, deterministic=det))
+            dwq.run(lambda: HF.linear_tn(d_ym, o, dwp, dbp, deterministic=det, pad_stage=True))
             d_o = HF.linear_nt(d_ym, wT("wpT", wp), None, epi=HF.EPI_NONE, out=d_z)
         else:
             if xn_path:
                 d_y, yn = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, beta=n2b, deterministic=det)
-                dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det))
+                dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det, pad_stage=True))
             else:
                 d_y = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, deterministic=det)          # + shortcut gradient
-            dwq.run(lambda: HF.linear_tn(d_y, o, dwp, dbp, pro_seed=seeds[0], pro_p=p, seed_base=sb, deterministic=det))
+            dwq.run(lambda: HF.linear_tn(d_y, o, dwp, dbp, pro_seed=seeds[0], pro_p=p, seed_base=sb, deterministic=det, pad_stage=True))
             d_o = HF.linear_nt(d_y, wT("wpT", wp), None, pro=HF.PRO_DROP, pro_seed=seeds[0], pro_p=p,
                                epi=HF.EPI_NONE, out=d_z, seed_base=sb)
         dqkv = torch.empty_like(qkv)
@@ -245,12 +245,12 @@ class _FusedBlock(torch.autograd.Function):
             # -- sums of 3d terms in index order (hwgat_ln_param_grads_from_g), the same bits every run.
             g_qkv = parts[12].view(3 * d, d)
             ones, zeros = HF.ln_identity(x.device, d)
-            dwq.run(lambda: HF.linear_tn(dqkv, x, g_qkv, dbqkv, ln=(m1, r1, ones, zeros), deterministic=det))
+            dwq.run(lambda: HF.linear_tn(dqkv, x, g_qkv, dbqkv, ln=(m1, r1, ones, zeros), deterministic=det, pad_stage=True))
             dwq.run(lambda: HF.ln_param_grads_from_g(g_qkv, dbqkv, wqkv, n1w, n1b, dwqkv, dn1w, dn1b))
             dwq.join()
             return (None, None, None, None, None, dn1w, dn1b, dwqkv, dbqkv, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2, None)
         if not xn_path:
-            dwq.run(lambda: HF.linear_tn(dqkv, x, dwqkv, dbqkv, ln=(m1, r1, n1w, n1b), deterministic=det))
+            dwq.run(lambda: HF.linear_tn(dqkv, x, dwqkv, dbqkv, ln=(m1, r1, n1w, n1b), deterministic=det, pad_stage=True))
         d_xn = HF.linear_nt(dqkv, wT("wqkvT", wqkv), None, epi=HF.EPI_NONE, out=d_o)
         dxm = None
         if ctx.send_up:           # the block that produced x gets dropmask3(its seed) * dx through the carrier's gradient
@@ -263,7 +263,7 @@ class _FusedBlock(torch.autograd.Function):
         else:
             dx = HF.ln_backward(d_xn, x, m1, r1, n1w, d_y, dn1w, dn1b, deterministic=det)
         if xn_path:
-            dwq.run(lambda: HF.linear_tn(dqkv, xn, dwqkv, dbqkv, deterministic=det))
+            dwq.run(lambda: HF.linear_tn(dqkv, xn, dwqkv, dbqkv, deterministic=det, pad_stage=True))
         if dxm is not None:
             book.register(dx, dxm)
         dwq.join()        # every temporary above stays referenced until here, so the allocator cannot recycle it early

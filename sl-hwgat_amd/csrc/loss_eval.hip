@@ -6,6 +6,11 @@
 //                          C % 4 == 0.  sce_mean_k (one workgroup) then takes the mean of the row losses in a fixed order.
 //   hwgat_sce_bwd          sce_bwd_k: one pass over the logits with the stored lse.
 //   hwgat_eval_accumulate  eval_acc_k: one workgroup folds a batch into the accumulator block (layout: hwgat_hip.h).
+//   hwgat_bsce_fwd         the loss of one SLICE of a padded batch (train.BatchSlicedCrossEntropyLoss): bsce_live_k turns
+//                          the batch's row count and the slice's offset into the slice's live-row count, sce_fwd_k runs
+//                          on those rows, bsce_sum_k (one workgroup) adds their losses in a fixed order, divides by the
+//                          BATCH's row count and counts the live rows whose target ranks first.
+//   hwgat_bsce_bwd         bsce_bwd_k: sce_bwd_k with the batch's row count as the divisor; exact zeros for the other rows.
 //
 // No float or double atomic anywhere: every floating-point sum is a per-thread strided sum followed by a fixed butterfly
 // and a fixed combination of the four waves, so every output is bit-reproducible.  The integer counters of the
@@ -194,6 +199,77 @@ __global__ __launch_bounds__(SCE_THREADS) void sce_bwd_k(const float* __restrict
     }
 }
 
+// ---- one slice of a padded batch.  The slice holds rows [offset, offset + B) of a batch whose first *n_rows rows are real:
+// v = clamp(*n_rows - offset, 0, B) of its rows are live, and every mean is over the batch's *n_rows, not the slice's v
+__device__ __forceinline__ int64_t live_rows(const int32_t* n_rows, int64_t offset, int64_t B) {
+    const int64_t v = (int64_t)*n_rows - offset;
+    return v < 0 ? 0 : (v > B ? B : v);
+}
+
+__global__ void bsce_live_k(const int32_t* __restrict__ n_rows, int32_t* __restrict__ live, int64_t offset, int64_t B) {
+    if (threadIdx.x == 0) live[0] = (int32_t)live_rows(n_rows, offset, B);
+}
+
+__global__ __launch_bounds__(SCE_THREADS) void bsce_sum_k(const float* __restrict__ row_loss,
+                                                         const int32_t* __restrict__ rank,
+                                                         const int32_t* __restrict__ n_rows, float* __restrict__ loss,
+                                                         int64_t* __restrict__ correct, int64_t offset, int64_t B) {
+    __shared__ float red_f[4];
+    __shared__ int red_i[4];
+    const int64_t v = live_rows(n_rows, offset, B);
+    float s = 0.f;
+    int hit = 0;
+    for (int64_t i = threadIdx.x; i < v; i += SCE_THREADS) {
+        s += row_loss[i];
+        hit += rank[i] == 0;
+    }
+    s = block_sum(s, red_f);
+    hit = block_sum(hit, red_i);
+    if (threadIdx.x == 0) {
+        loss[0] = v > 0 ? s / (float)*n_rows : 0.f;          // v > 0 implies *n_rows > offset >= 0; an empty slice adds nothing
+        correct[0] = hit;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(SCE_THREADS) void bsce_bwd_k(const float* __restrict__ z, const int64_t* __restrict__ target,
+                                                         const int32_t* __restrict__ n_rows, const float* __restrict__ lse,
+                                                         const float* __restrict__ g, float* __restrict__ dz,
+                                                         int64_t offset, int64_t B, int C, float eps) {
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* zr = z + b * C;
+    float* dr = dz + b * C;
+    const bool live = b < live_rows(n_rows, offset, B);
+    const int64_t t64 = live ? target[b] : 0;
+    const bool t_ok = t64 >= 0 && t64 < C;
+    const int t = t_ok ? (int)t64 : -1;          // -1 matches no column
+    const float fill = live ? NAN : 0.f;         // a live row gets here only with a bad target
+    if (!live || !t_ok) {
+        for (int j = tid; j < C; j += SCE_THREADS) dr[j] = fill;
+        return;
+    }
+    const float scale = g[0] / (float)*n_rows;   // a live row implies *n_rows >= 1
+    const float l = lse[b];
+    const float hit = 1.f - eps, flat = eps / (float)C;
+    if (VEC) {
+        const f32x4* zr4 = reinterpret_cast<const f32x4*>(zr);
+        f32x4* dr4 = reinterpret_cast<f32x4*>(dr);
+        for (int q = tid; q < C / 4; q += SCE_THREADS) {
+            const f32x4 v = zr4[q];
+            const int j = 4 * q;
+            f32x4 d;
+            d.x = scale * (expf(v.x - l) - (j == t ? hit : 0.f) - flat);
+            d.y = scale * (expf(v.y - l) - (j + 1 == t ? hit : 0.f) - flat);
+            d.z = scale * (expf(v.z - l) - (j + 2 == t ? hit : 0.f) - flat);
+            d.w = scale * (expf(v.w - l) - (j + 3 == t ? hit : 0.f) - flat);
+            dr4[q] = d;
+        }
+    } else {
+        for (int j = tid; j < C; j += SCE_THREADS) dr[j] = scale * (expf(zr[j] - l) - (j == t ? hit : 0.f) - flat);
+    }
+}
+
 // accumulator block, in 8-byte words (hwgat_hip.h documents the same offsets)
 constexpr int ACC_N_SAMPLES = 0, ACC_N_BATCHES = 1, ACC_N_INVALID = 2, ACC_LOSS_SAMPLES = 3, ACC_LOSS_BATCHES = 4,
               ACC_RANK_HIST = 5;
@@ -250,6 +326,19 @@ __global__ __launch_bounds__(SCE_THREADS) void eval_acc_k(int64_t* __restrict__ 
 inline bool bad_shape(int64_t B, int C) { return B < 1 || B > 0x7fffffff || C < 1 || C > SCE_MAX_C; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// sce_fwd_k on the first *n_valid rows (all B when NULL): staged in LDS when the row fits, 16-byte loads when it can
+inline void launch_sce_rows(const float* logits, const int64_t* target, const int32_t* n_valid, float* lse, float* row_loss,
+                            int32_t* rank, int32_t* pred, int64_t B, int C, float eps, hipStream_t st) {
+    const bool vec = C % 4 == 0 && aligned16(logits);
+    const bool staged = C <= SCE_LDS_FLOATS;
+#define SCE_FWD(S, V) sce_fwd_k<S, V><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_valid, lse, row_loss, rank, pred, B, C, eps)
+    if (staged) { if (vec) SCE_FWD(true, true); else SCE_FWD(true, false); }
+    else { if (vec) SCE_FWD(false, true); else SCE_FWD(false, false); }
+#undef SCE_FWD
+}
+
+inline bool bad_offset(int64_t offset) { return offset < 0 || offset > 0x7fffffff; }
+
 }  // namespace
 
 extern "C" int hwgat_sce_fwd(const float* logits, const int64_t* target, const int32_t* n_valid, float* lse, float* row_loss,
@@ -257,12 +346,7 @@ extern "C" int hwgat_sce_fwd(const float* logits, const int64_t* target, const i
     if (!logits || !target || !lse || !row_loss || !rank || !pred || !loss) return HWGAT_EINVAL;
     if (bad_shape(B, C)) return HWGAT_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = C % 4 == 0 && aligned16(logits);
-    const bool staged = C <= SCE_LDS_FLOATS;
-#define SCE_FWD(S, V) sce_fwd_k<S, V><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_valid, lse, row_loss, rank, pred, B, C, eps)
-    if (staged) { if (vec) SCE_FWD(true, true); else SCE_FWD(true, false); }
-    else { if (vec) SCE_FWD(false, true); else SCE_FWD(false, false); }
-#undef SCE_FWD
+    launch_sce_rows(logits, target, n_valid, lse, row_loss, rank, pred, B, C, eps, st);
     sce_mean_k<<<1, SCE_THREADS, 0, st>>>(row_loss, n_valid, loss, B);
     HWGAT_LAUNCH_CHECK();
 }
@@ -291,5 +375,30 @@ extern "C" int hwgat_eval_accumulate(void* acc, const float* row_loss, const int
     if (bad_shape(B, C)) return HWGAT_ESHAPE;
     eval_acc_k<<<1, SCE_THREADS, 0, (hipStream_t)stream>>>(static_cast<int64_t*>(acc), row_loss, rank, pred, target, loss,
                                                           n_valid, B, C, k_max, cap);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_bsce_fwd(const float* logits, const int64_t* target, const int32_t* n_rows, int64_t offset, float* lse,
+                              float* row_loss, int32_t* rank, int32_t* pred, float* loss, int64_t* correct, int32_t* live,
+                              int64_t B, int C, float eps, void* stream) {
+    if (!logits || !target || !n_rows || !lse || !row_loss || !rank || !pred || !loss || !correct || !live || bad_offset(offset))
+        return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    bsce_live_k<<<1, 64, 0, st>>>(n_rows, live, offset, B);
+    launch_sce_rows(logits, target, live, lse, row_loss, rank, pred, B, C, eps, st);
+    bsce_sum_k<<<1, SCE_THREADS, 0, st>>>(row_loss, rank, n_rows, loss, correct, offset, B);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_bsce_bwd(const float* logits, const int64_t* target, const int32_t* n_rows, int64_t offset,
+                              const float* lse, const float* g, float* dlogits, int64_t B, int C, float eps, void* stream) {
+    if (!logits || !target || !n_rows || !lse || !g || !dlogits || bad_offset(offset)) return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (C % 4 == 0 && aligned16(logits) && aligned16(dlogits))
+        bsce_bwd_k<true><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_rows, lse, g, dlogits, offset, B, C, eps);
+    else
+        bsce_bwd_k<false><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_rows, lse, g, dlogits, offset, B, C, eps);
     HWGAT_LAUNCH_CHECK();
 }

@@ -755,13 +755,29 @@ def linear_nt_ln(A, W, bias, ln, *, epi=EPI_BIAS, epi_seed=0, epi_p=0.0, out=Non
     return linear_nt(A, Wc, bias, pro=PRO_LN, ln=ln, epi=epi, epi_seed=epi_seed, epi_p=epi_p, out=out, seed_base=seed_base)
 
 
-def linear_tn(A, Bm, dW, db=None, *, pro_seed=0, pro_p=0.0, ln=None, seed_base=None, deterministic=False):
+def _zero_rows_to(t, M, rows):
+    """`t` (M rows) followed by zero rows up to `rows`"""
+    out = torch.zeros((rows,) + tuple(t.reshape(M, -1).shape[1:]), device=t.device, dtype=t.dtype)
+    out[:M] = t.reshape(M, -1)
+    return out
+
+
+def linear_tn(A, Bm, dW, db=None, *, pro_seed=0, pro_p=0.0, ln=None, seed_base=None, deterministic=False, pad_stage=False):
     """dW[N,K] += dropmask(A)[M,N]^T . ln(Bm)[M,K]; db[N] += colsum(dropmask(A)).
     ln = (mean, rstd, gamma, beta) normalises Bm on the fly.
     `deterministic`: the bit-reproducible form (hwgat_linear_tn_*_det: per-split partial images in a zero-filled
-    workspace, added in split order; no float atomics)."""
+    workspace, added in split order; no float atomics).  It takes whole 32-row stages only; `pad_stage` (the fused
+    block passes it: a micro-batch of 3 clips of 16 tokens is 48 rows) appends zero rows to A, Bm and the row statistics
+    up to the next stage instead of refusing: a zero row of A adds an exact zero to every entry of dW and db, and its
+    mask is the mask of a zero."""
     N, K = dW.shape
     M = A.numel() // N
+    if deterministic and pad_stage and M % 32:
+        rows = (M + 31) // 32 * 32
+        A, Bm = _zero_rows_to(A, M, rows), _zero_rows_to(Bm, M, rows)
+        if ln is not None:
+            ln = (_zero_rows_to(ln[0], M, rows), _zero_rows_to(ln[1], M, rows), ln[2], ln[3])
+        M = rows
     if N % 128 or K % 128:
         # 64x64 dW tiles (odd multiples of 64): split images added in a fixed order in every mode -- no float atomics
         need = _lib.lib().hwgat_linear_tn_det_bytes(M, N, K)
@@ -1357,6 +1373,66 @@ def smooth_ce(logits, target, eps, n_valid=None):
     """(loss, rank, pred): the batch-mean smoothed cross-entropy as an autograd node (forward two launches, backward one),
     with the detached rank of the target in a stable descending sort and the arg-max (both int32)"""
     return _SmoothCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_valid)
+
+
+# ---- the same loss for one slice of a zero-padded batch: `n_rows` is a device int32 (1,) holding the batch's real row count,
+# `offset` the slice's first row in the batch (a host integer); rows of the slice at or beyond n_rows - offset are dead
+def _bsce_check(logits, target, n_rows, offset):
+    _sce_check(logits, target)
+    if n_rows is None or n_rows.dtype != torch.int32 or n_rows.numel() != 1:
+        raise ValueError("n_rows must be a device int32 tensor of one element")
+    if not 0 <= int(offset) < 2 ** 31:
+        raise ValueError(f"the slice's offset must be in [0, 2^31), got {offset}")
+
+
+def bsce_forward(logits, target, eps, n_rows, offset, out=None):
+    """(loss (1,), row_loss (B,), lse (B,), rank (B,) int32, pred (B,) int32, correct (1,) int64, live (1,) int32) of one
+    slice: loss is the live rows' sum over the BATCH's row count (exactly 0 for a slice without live rows), correct the
+    number of live rows whose target ranks first; dead rows of the per-row outputs are not written.  `out` takes the same
+    seven tensors preallocated"""
+    _bsce_check(logits, target, n_rows, offset)
+    B, C = logits.shape
+    if out is None:
+        f = torch.empty(2 * B + 1, device=logits.device, dtype=torch.float32)
+        i = torch.empty(2 * B + 1, device=logits.device, dtype=torch.int32)
+        out = (f[2 * B:], f[:B], f[B:2 * B], i[:B], i[B:2 * B], torch.empty(1, device=logits.device, dtype=torch.int64),
+               i[2 * B:])
+    loss, row_loss, lse, rank, pred, correct, live = out
+    call("hwgat_bsce_fwd", ptr(logits), ptr(target), ptr(n_rows), int(offset), ptr(lse), ptr(row_loss), ptr(rank), ptr(pred),
+         ptr(loss), ptr(correct), ptr(live), B, C, float(eps), stream())
+    return out
+
+
+def bsce_backward(logits, target, lse, g, eps, n_rows, offset, out=None):
+    """d loss / d logits of bsce_forward times the device scalar `g`; exactly zero in the dead rows"""
+    _bsce_check(logits, target, n_rows, offset)
+    B, C = logits.shape
+    dz = torch.empty_like(logits) if out is None else out
+    call("hwgat_bsce_bwd", ptr(logits), ptr(target), ptr(n_rows), int(offset), ptr(lse), ptr(g), ptr(dz), B, C, float(eps),
+         stream())
+    return dz
+
+
+class _BatchSlicedCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, eps, n_rows, offset):
+        loss, _, lse, rank, pred, correct, _ = bsce_forward(logits, target, eps, n_rows, offset)
+        ctx.save_for_backward(logits, target, lse)
+        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
+        ctx.mark_non_differentiable(rank, pred, correct)
+        return loss.view(()), rank, pred, correct.view(())
+
+    @staticmethod
+    def backward(ctx, g, _rank, _pred, _correct):
+        logits, target, lse = ctx.saved_tensors
+        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
+        return bsce_backward(logits, target, lse, g, ctx.eps, ctx.n_rows, ctx.offset), None, None, None, None
+
+
+def batch_sliced_ce(logits, target, eps, n_rows, offset):
+    """(loss, rank, pred, correct): a slice's share of the batch-mean smoothed cross-entropy as an autograd node (forward
+    three launches, backward one), with the detached rank and arg-max of its live rows and their correct count (int64)"""
+    return _BatchSlicedCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_rows, int(offset))
 
 
 # ---------------------------------------------------------------- the classifier head (csrc/head.hip)

@@ -216,7 +216,7 @@ class Model(DeviceSeeds, nn.Module):
         self.block_tap = None              # a list: every unit's output (N, T, V, C) is appended to it (tests, debugging)
         self.drop_tap = None               # a list: every DropGraph draw's record is appended to it
         self.drop_seeds = None             # {(unit, site): seed tensor} used in place of the hash draw
-        self._init_device_seeds()
+        self._init_device_seeds(clips_independent_in_train=False)      # BatchNorm's batch statistics and DropGraph's normalisers
 
     @property
     def units(self):

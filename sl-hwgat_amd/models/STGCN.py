@@ -153,7 +153,7 @@ class Model(DeviceSeeds, nn.Module):
         self.head = Head(n_out_features, n_classes, dropout_ratio)
         self.activation_dtype = torch.float32
         self.block_tap = None              # a list: every block's output (N, T, V, C) is appended to it (tests, debugging)
-        self._init_device_seeds()
+        self._init_device_seeds(clips_independent_in_train=False)      # BatchNorm's batch statistics
 
     def set_activation_dtype(self, dtype):
         if dtype != torch.float32:

@@ -15,8 +15,11 @@ from . import functional as HF
 
 
 class DeviceSeeds:
-    def _init_device_seeds(self):
+    def _init_device_seeds(self, clips_independent_in_train=True):
         self._drop_calls = 0
+        # False: the train() forward couples the clips of a batch (batch statistics), so a batch must not be zero-padded
+        # (train.GraphedTrainStep(ragged=True), train.TrainStep(pad_to=...)); eval() never couples them
+        self.clips_independent_in_train = bool(clips_independent_in_train)
         # the dropout seed lives on the DEVICE: {step counter, base seed of the step, initial seed, rank salt}; every
         # seeded kernel adds word 1 to its (host, per-site) seed when it runs, see include/hwgat_hip.h "dropout seeds"
         self.register_buffer("_seed_state", torch.zeros(4, dtype=torch.int32), persistent=False)
