@@ -69,7 +69,8 @@ extern "C" {
  *         hwgat_head_{fwd,bwd_dx,bwd_dw}, the classifier head;
  *         hwgat_gguard_{set,partial,finish,scale}, the gradient guard (global-norm clipping and non-finite detection on the
  *         device), and hwgat_gguard_{adamw,sgd,nadam}_{advance,step}, the three optimizers' launches under a guard;
- *         hwgat_bsce_{fwd,bwd}, the smoothed cross-entropy of one slice of a zero-padded batch (additions only) */
+ *         hwgat_bsce_{fwd,bwd}, the smoothed cross-entropy of one slice of a zero-padded batch (additions only);
+ *         hwgat_wavg_{set,advance,update,swap}, EMA / equal-weight averages of the weights on the device (additions only) */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -649,6 +650,52 @@ int hwgat_gguard_nadam_advance(const hwgat_opt_entry* table, int n, const double
                                const double* guard_state, void* stream);
 int hwgat_gguard_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks,
                             const double* guard_state, void* stream);
+
+/* ---- weight averaging: an exponential moving average (EMA) or the equal-weight running mean (SWA) of the weights, as
+ * torch.optim.swa_utils.AveragedModel keeps it, with every number left in DEVICE memory, so the launches below can be
+ * captured in a HIP graph behind the optimizer step; and the in-place exchange of the averages with the live weights.
+ *
+ * table: `n` hwgat_wavg_entry records (HWGAT_WAVG_ENTRY_BYTES each) in DEVICE memory, sorted by first_block, workgroups
+ *   assigned as for hwgat_optim_step: one workgroup of 256 threads per HWGAT_OPTIM_CHUNK elements of one tensor.  avg and
+ *   src are fp32, 4-byte aligned and must not overlap.  A tensor whose avg and src are both 16-byte aligned moves in 16-byte
+ *   vectors, any other element by element; both give the same bits.
+ * state: HWGAT_WAVG_NSTATE fp64 words in DEVICE memory, at the HWGAT_WAVG_* slots below.  The five config words are written
+ *   by hwgat_wavg_set, the four result words by hwgat_wavg_advance; the caller zeroes the block once.
+ *
+ * hwgat_wavg_set:     one thread writes mode (0 = EMA, 1 = equal weight), decay (in [0, 1)), warmup (0 / 1), start (>= 0)
+ *                     and every (>= 1) from the host values given as arguments; stream-ordered like hwgat_optim_set.
+ * hwgat_wavg_advance: one thread.  guard_state (may be NULL) is a gradient guard's state block: when its `skip` word is
+ *                     set, active = 0, coef = 0 and no counter moves.  Otherwise steps_seen += 1; the update is due when
+ *                     steps_seen > start and (steps_seen - start) % every == 0.  Not due: active = 0.  Due: active = 1,
+ *                       coef = 1                                           when n_averaged == 0 (the first update copies),
+ *                       coef = 1 - d,  d = decay                           EMA
+ *                                      d = min(decay, (1 + n_averaged) / (10 + n_averaged))   EMA with warmup
+ *                       coef = 1 / (n_averaged + 1)                        equal weight
+ *                     in fp64, then n_averaged += 1.
+ * hwgat_wavg_update:  active == 0: writes nothing.  coef == 1: avg = src, the same bits.  Otherwise, per element in fp32,
+ *                     avg = fma((float)coef, src - avg, avg).  src is only read.  12 bytes per element.  No atomics, no
+ *                     reductions: bit-reproducible.
+ * hwgat_wavg_swap:    exchanges avg[i] and src[i] for every element of every entry.  16 bytes per element. */
+#define HWGAT_WAVG_NSTATE 16
+#define HWGAT_WAVG_ENTRY_BYTES 32
+#define HWGAT_WAVG_MODE 0
+#define HWGAT_WAVG_DECAY 1
+#define HWGAT_WAVG_WARMUP 2
+#define HWGAT_WAVG_START 3
+#define HWGAT_WAVG_EVERY 4
+#define HWGAT_WAVG_STEPS_SEEN 5
+#define HWGAT_WAVG_N_AVERAGED 6
+#define HWGAT_WAVG_COEF 7
+#define HWGAT_WAVG_ACTIVE 8
+typedef struct {
+    float* avg; float* src;
+    int64_t n;
+    int32_t first_block, pad;
+} hwgat_wavg_entry;
+int hwgat_wavg_set(double* state, int mode, double decay, int warmup, int64_t start, int64_t every, void* stream);
+int hwgat_wavg_advance(double* state, const double* guard_state, void* stream);
+int hwgat_wavg_update(const hwgat_wavg_entry* table, int n, const double* state, int total_blocks, void* stream);
+int hwgat_wavg_swap(const hwgat_wavg_entry* table, int n, int total_blocks, void* stream);
 
 /* the dropout mask the fused kernels use: out[i] = keep(seed, i) ? 1/(1-p) : 0 */
 int hwgat_dropout_mask_f32(float* out, int64_t n, uint32_t seed, float p, const uint32_t* seed_base, void* stream);

@@ -148,6 +148,10 @@ _SIGS = {
     "hwgat_gguard_sgd_step": [_P, _I, _P, _I, _P, _P],
     "hwgat_gguard_nadam_advance": [_P, _I, _P, _P, _P, _P],
     "hwgat_gguard_nadam_step": [_P, _I, _P, _I, _P, _P],
+    "hwgat_wavg_set": [_P, _I, _D, _I, _L, _L, _P],
+    "hwgat_wavg_advance": [_P, _P, _P],
+    "hwgat_wavg_update": [_P, _I, _P, _I, _P],
+    "hwgat_wavg_swap": [_P, _I, _I, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

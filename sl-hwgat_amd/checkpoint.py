@@ -45,13 +45,14 @@ def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused:
 
 
 def get_device_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", max_grad_norm: Optional[float] = None,
-                         on_nonfinite: str = "propagate"):
+                         on_nonfinite: str = "propagate", weight_average: Optional[dict] = None):
     """utils.py:71-82 on the HIP optimizers (optim.DeviceAdamW / DeviceNAdam / DeviceSGD), which train.GraphedTrainStep
     captures inside its graph: ALL parameters in one group, as `get_optimizer` passes them, and the values the reference's
     `Class(model.parameters(), lr=cfg.lr)` leaves at torch's defaults -- AdamW weight decay 0.01, Adam and NAdam 0, SGD
     without momentum.  `max_grad_norm` (clip the gradients to that global 2-norm before every step) and `on_nonfinite`
     ("skip": a step with a NaN or Inf gradient changes nothing) attach an `optim.GradGuard` as the optimizer's `guard`
-    when either differs from its default; the reference has neither."""
+    when either differs from its default; the reference has neither.  `weight_average`: a dict of `optim.WeightAverage`
+    keywords (`{}` for the defaults) attaches an EMA / SWA of the model's weights as the optimizer's `averager`."""
     from . import optim
     params = list(model.parameters())
     if optimizer_type == "adamw":
@@ -67,6 +68,8 @@ def get_device_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw",
     if max_grad_norm is not None or on_nonfinite != "propagate":
         opt.guard = optim.GradGuard(max_norm=float("inf") if max_grad_norm is None else max_grad_norm,
                                     on_nonfinite=on_nonfinite)
+    if weight_average is not None:
+        opt.averager = optim.WeightAverage(model, **weight_average)
     return opt
 
 

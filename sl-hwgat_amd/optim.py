@@ -16,7 +16,13 @@ fallback: the objects can be built, inspected and (de)serialised on CPU tensors,
 norm, as torch.nn.utils.clip_grad_norm_ does it, and a verdict on NaN / Inf gradients, both computed and kept on the
 device.  Attached to a device optimizer (`opt.guard = GradGuard(max_norm=1.0, on_nonfinite="skip")`) it runs between the
 backward and the update in every `step()` and in every replay; `clip_grad_norm_(parameters, guard)` runs it alone.
+
+`WeightAverage` (csrc/weight_avg.hip) keeps an EMA or the equal-weight mean (SWA) of a model's weights in shadow tensors
+on the device.  Attached to a device optimizer (`opt.averager = WeightAverage(model, decay=0.999)`) it is updated behind
+the optimizer's own launches in every `step()` and in every replay, a step the guard skipped not counted;
+`with avg.applied(): ...` exchanges averages and weights in place, so every captured graph stays valid.
 """
+import contextlib
 import math
 import struct
 
@@ -39,6 +45,13 @@ FAMILY_ENTRY_BYTES = FAMILY_ENTRY.size
 GUARD_NSTATE = 16       # HWGAT_GGUARD_NSTATE: fp64 words of a guard's state block, at the HWGAT_GGUARD_* slots:
 G_MAX_NORM, G_NORM_TYPE, G_MODE, G_TOTAL_NORM, G_CLIP_COEF, G_NONFINITE, G_SKIP, G_STEPS, G_CLIPPED, G_SKIPPED = range(10)
 _COUNTERS = ("steps", "clipped", "skipped")
+
+WAVG_NSTATE = 16        # HWGAT_WAVG_NSTATE: fp64 words of an averager's state block, at the HWGAT_WAVG_* slots:
+W_MODE, W_DECAY, W_WARMUP, W_START, W_EVERY, W_STEPS_SEEN, W_N_AVERAGED, W_COEF, W_ACTIVE = range(9)
+# hwgat_wavg_entry: avg, src (pointers), n (int64), first_block, pad (int32)
+WAVG_ENTRY = struct.Struct("<QQqii")
+WAVG_ENTRY_BYTES = WAVG_ENTRY.size
+_WAVG_COUNTERS = ("steps_seen", "n_averaged")
 
 
 def _pack_table(records, entry, chunk):
@@ -257,6 +270,279 @@ def clip_grad_norm_(parameters, guard):
     return guard.total_norm
 
 
+class WeightAverage:
+    """An exponential moving average (EMA) or the equal-weight running mean (SWA) of a model's weights, kept and updated
+    on the device (csrc/weight_avg.hip), as torch.optim.swa_utils.AveragedModel keeps it -- without a second model: the
+    averages live in fp32 shadow tensors beside the weights, and `swap()` / `applied()` exchange the two IN PLACE, so no
+    address changes and every captured graph (train.GraphedTrainStep, serve.GraphedEval, evaluate.Evaluator) stays valid and
+    simply sees the averaged weights while they are swapped in.
+
+    `mode`: "ema" -- avg += (1 - decay) (p - avg), torch's get_ema_multi_avg_fn(decay) -- or "swa" -- the equal-weight
+    mean, avg += (p - avg) / (n_averaged + 1), AveragedModel's default.  The first update copies the weights in both.
+    `warmup`: EMA with the decay min(decay, (1 + n_averaged) / (10 + n_averaged)), so that early averages are not
+    dominated by the initial weights.
+    `start`, `every`: the update is due at the steps s (counted from 1, skipped steps not counted) with s > start and
+    (s - start) % every == 0.
+    `buffers`: also average `running_mean` / `running_var` of every BatchNorm module.  No other buffer (adjacency, masks,
+    seeds, `num_batches_tracked`) is ever held.
+    All five config values are plain attributes and may be changed at any time; they reach the device, and so a captured
+    graph, with the next `push()` (which `DeviceOptimizer.push_hyper()` and so every step and replay issues).
+
+    Attached to a device optimizer (`opt.averager = WeightAverage(model)`) the average is updated by two launches behind
+    the optimizer's own in every `step()` and, as two more nodes of the graph, in every GraphedTrainStep replay; under a
+    `GradGuard` in "skip" mode a skipped step is not averaged in and not counted -- the verdict is a device word, the host
+    never learns it.  With any other optimizer call `update()` after its step.  `n_averaged`, `steps_seen` and `coef` are
+    0-d float64 device views (reading one is the caller's host sync).  One table serves eager steps and every capture: it
+    holds weight and shadow addresses only, no gradient's.
+
+    While the averages are swapped in (`is_applied`), `update()`, `DeviceOptimizer.step()` and a GraphedTrainStep call
+    raise: a step would train the averages.  Data-parallel runs need nothing extra: the ranks hold equal weights after
+    every step, so they hold equal averages.  There is no CPU fallback: the object can be built, inspected and
+    (de)serialised on a CPU model; everything that launches raises there."""
+
+    _MODES = ("ema", "swa")
+
+    def __init__(self, model, mode="ema", decay=0.999, warmup=False, start=0, every=1, buffers=True):
+        self.model = model
+        self.mode, self.decay, self.warmup, self.start, self.every = mode, decay, warmup, start, every
+        self.buffers = bool(buffers)
+        self._config()
+        # (state_dict key, owner, attribute): a model.to() replaces a buffer object, so the live tensor is looked up
+        self._slots = [(name, p, None) for name, p in model.named_parameters() if p.is_floating_point()]
+        if self.buffers:
+            for mname, m in model.named_modules():
+                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+                    for attr in ("running_mean", "running_var"):
+                        if getattr(m, attr, None) is not None:
+                            self._slots.append((f"{mname}.{attr}" if mname else attr, m, attr))
+        keys = set(model.state_dict().keys())
+        for key, t in zip(self.keys(), self._live()):
+            if key not in keys:
+                raise ValueError(f"WeightAverage: {key!r} is no key of the model's state_dict()")
+            if t.dtype != torch.float32:
+                raise ValueError(f"WeightAverage needs float32 weights, {key!r} is {t.dtype}")
+        if not self._slots:
+            raise ValueError("WeightAverage: the model has nothing to average")
+        self._shadow = [t.detach().clone(memory_format=torch.contiguous_format) for t in self._live()]
+        self._state = None           # device block, WAVG_NSTATE fp64
+        self._table = None           # device table, one WAVG_ENTRY per non-empty tensor
+        self._n = self._total = 0
+        self._key = None             # the addresses the table was built from
+        self._held = None            # the config the device holds
+        self._loaded = None          # counters of a load_state_dict() that came before the device block existed
+        self.is_applied = False
+
+    def keys(self):
+        """the state_dict keys of the averaged tensors, in table order"""
+        return [s[0] for s in self._slots]
+
+    def _live(self):
+        return [(o if attr is None else getattr(o, attr)).detach() for _, o, attr in self._slots]
+
+    def _config(self):
+        """(mode, decay, warmup, start, every) as the `set` entry point takes them; refuses what the kernels do not do"""
+        if self.mode not in self._MODES:
+            raise ValueError(f"WeightAverage: mode {self.mode!r}: one of {list(self._MODES)}")
+        decay = float(self.decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"WeightAverage: decay must be in [0, 1), got {self.decay}")
+        for name in ("start", "every"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or int(v) < (1 if name == "every" else 0):
+                raise ValueError(f"WeightAverage: {name} must be an integer >= {1 if name == 'every' else 0}, got {v!r}")
+        return self._MODES.index(self.mode), decay, int(bool(self.warmup)), int(self.start), int(self.every)
+
+    # ---- device side
+    def bind(self, device=None):
+        """allocate the state block and the table on the model's device and move the shadows there (once)"""
+        if self._state is not None:
+            if device is not None and torch.device(device) != self._state.device:
+                raise ValueError(f"WeightAverage lives on {self._state.device}, not on {device}")
+            return self
+        live = self._live()
+        if not all(t.is_cuda for t in live):
+            raise RuntimeError("WeightAverage needs the model on an MI355X device; there is no CPU fallback")
+        dev = live[0].device
+        if any(t.device != dev for t in live) or (device is not None and torch.device(device) != dev):
+            raise ValueError("WeightAverage needs all weights on one device, the optimizer's")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightAverage: bind() (or one eager update) before capturing")
+        self._shadow = [s if s.device == dev else s.to(dev) for s in self._shadow]
+        self._table = torch.zeros(len(self._slots) * WAVG_ENTRY_BYTES, dtype=torch.uint8, device=dev)
+        self._state = torch.zeros(WAVG_NSTATE, dtype=torch.float64, device=dev)
+        if self._loaded is not None:
+            self._put_counters(self._loaded)
+            self._loaded = None
+        self._check_table(live)
+        return self
+
+    def _bound(self):
+        if self._state is None:
+            raise RuntimeError("WeightAverage has not run yet: its results live on the device of its first update (or bind())")
+        return self._state
+
+    def _check_table(self, live=None):
+        """the table against the current addresses: a tuple compare, packed and uploaded (in place) only on change"""
+        live = self._live() if live is None else live
+        key = tuple(t.data_ptr() for t in live)
+        if key == self._key:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightAverage: a weight was reallocated before a capture; run one eager update() first")
+        blob, total, n = bytearray(), 0, 0
+        for t, s in zip(live, self._shadow):
+            if not t.is_contiguous() or t.shape != s.shape or t.device != s.device:
+                raise ValueError("WeightAverage needs contiguous weights that keep their shape and device")
+            if t.numel() == 0:
+                continue
+            blob += WAVG_ENTRY.pack(s.data_ptr(), t.data_ptr(), t.numel(), total, 0)
+            total += (t.numel() + CHUNK - 1) // CHUNK
+            n += 1
+        if total >= 2 ** 31:
+            raise ValueError("more workgroups than one launch holds")
+        if blob:
+            self._table[:len(blob)].copy_(torch.frombuffer(blob, dtype=torch.uint8))
+        self._n, self._total, self._key = n, total, key
+
+    def push(self, device=None):
+        """make the device hold the current config: one `set` launch when it changed"""
+        cfg = self._config()
+        self.bind(device)
+        if cfg != self._held:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("WeightAverage: the config changed inside a capture; push() before it")
+            call("hwgat_wavg_set", ptr(self._state), *cfg, stream())
+            self._held = cfg
+
+    def _refuse_applied(self, what):
+        if self.is_applied:
+            raise RuntimeError(f"{what} while the averaged weights are swapped in (WeightAverage.is_applied): swap() back first")
+
+    def _issue(self, guard=None):
+        """advance and update on the current stream; `guard`: the GradGuard whose skip verdict decides whether the step counts"""
+        self._check_table()
+        if self._n:
+            call("hwgat_wavg_advance", ptr(self._state), None if guard is None else ptr(guard._bound()), stream())
+            call("hwgat_wavg_update", ptr(self._table), self._n, ptr(self._state), self._total, stream())
+
+    @torch.no_grad()
+    def update(self, guard=None):
+        """take the current weights into the average: two launches on the current stream, capturable (bind() and push()
+        before the capture).  For an optimizer that is not a DeviceOptimizer, or a loop written by hand"""
+        self._refuse_applied("WeightAverage.update()")
+        self.push()
+        self._issue(guard)
+
+    @torch.no_grad()
+    def swap(self):
+        """exchange the averaged and the live weights in place: one launch.  Every forward re-derives its weight images
+        from the weights, so the next one, eager or replayed, runs on what is swapped in"""
+        self.bind()
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightAverage.swap() is an eager call: the host has to know which weights are live")
+        self._check_table()
+        if self._n:
+            call("hwgat_wavg_swap", ptr(self._table), self._n, self._total, stream())
+        self.is_applied = not self.is_applied
+
+    @contextlib.contextmanager
+    def applied(self):
+        """`with avg.applied(): ...`: the body runs on the averaged weights; they are swapped back out on any exit"""
+        self._refuse_applied("WeightAverage.applied()")
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    # ---- readouts
+    @property
+    def n_averaged(self):
+        return self._bound()[W_N_AVERAGED]
+
+    @property
+    def steps_seen(self):
+        return self._bound()[W_STEPS_SEEN]
+
+    @property
+    def coef(self):
+        return self._bound()[W_COEF]
+
+    def counters(self):
+        """{steps_seen, n_averaged} so far: one host read"""
+        if self._state is None:
+            return dict(self._loaded or dict.fromkeys(_WAVG_COUNTERS, 0))
+        return {k: int(v) for k, v in zip(_WAVG_COUNTERS, self._state[W_STEPS_SEEN:W_N_AVERAGED + 1].tolist())}
+
+    def _put_counters(self, values):
+        self._state[W_STEPS_SEEN:W_N_AVERAGED + 1].copy_(
+            torch.tensor([float(values[k]) for k in _WAVG_COUNTERS], dtype=torch.float64))
+
+    # ---- what a warm-up must not leave behind: the shadows and the result words (the config is the caller's)
+    @torch.no_grad()
+    def snapshot(self):
+        return ([s.clone() for s in self._shadow], None if self._state is None else self._state[W_STEPS_SEEN:].clone())
+
+    @torch.no_grad()
+    def restore(self, snap):
+        """None: an averager that was attached after the snapshot becomes a fresh one, its shadows the current weights"""
+        shadows, words = (self._live(), None) if snap is None else snap
+        for s, q in zip(self._shadow, shadows):
+            s.copy_(q)
+        if self._state is not None:
+            if words is None:
+                self._state[W_STEPS_SEEN:].zero_()
+            else:
+                self._state[W_STEPS_SEEN:].copy_(words)
+
+    # ---- (de)serialisation
+    @torch.no_grad()
+    def model_state_dict(self):
+        """the model's state_dict() -- its keys, its order -- with clones of the averaged values in place of the live
+        ones: `torch.save({"model_state_dict": avg.model_state_dict()}, path)` is a weights file of the averaged model"""
+        sd = self.model.state_dict()
+        for key, s, t in zip(self.keys(), self._shadow, self._live()):
+            sd[key] = (t if self.is_applied else s).detach().clone()
+        return sd
+
+    @torch.no_grad()
+    def state_dict(self):
+        """config, counters and the shadows by state_dict key; for a checkpoint's own extra key"""
+        self._refuse_applied("WeightAverage.state_dict()")
+        return dict(mode=self.mode, decay=float(self.decay), warmup=bool(self.warmup), start=int(self.start),
+                    every=int(self.every), buffers=self.buffers, **self.counters(),
+                    shadows={k: s.detach().clone() for k, s in zip(self.keys(), self._shadow)})
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """the loaded values go INTO the live shadow tensors and device words: no address changes"""
+        self._refuse_applied("WeightAverage.load_state_dict()")
+        names = ("mode", "decay", "warmup", "start", "every")
+        shadows = sd["shadows"]
+        if list(shadows.keys()) != self.keys():
+            raise ValueError("WeightAverage.load_state_dict: the file averages other tensors than this object "
+                             f"({len(shadows)} against {len(self._slots)}; `buffers` must match)")
+        for (k, q), s in zip(shadows.items(), self._shadow):
+            if tuple(q.shape) != tuple(s.shape):
+                raise ValueError(f"WeightAverage.load_state_dict: {k!r} has shape {tuple(q.shape)}, expected {tuple(s.shape)}")
+        keep = tuple(getattr(self, k) for k in names)
+        for k in names:
+            setattr(self, k, sd[k])
+        try:
+            self._config()
+        except ValueError:
+            for k, v in zip(names, keep):
+                setattr(self, k, v)
+            raise
+        for q, s in zip(shadows.values(), self._shadow):
+            s.copy_(q.to(dtype=torch.float32))
+        values = {k: int(sd.get(k, 0)) for k in _WAVG_COUNTERS}
+        if self._state is None:
+            self._loaded = values
+        else:
+            self._put_counters(values)
+
+
 class DeviceOptimizer(torch.optim.Optimizer):
     """What the device optimizers share: the fp32 / one-device checks, the fp64 hyper-parameter block with its host
     mirror (`push_hyper`), the device table keyed by the (parameter, gradient) addresses, `begin_capture` / `end_capture`,
@@ -278,7 +564,13 @@ class DeviceOptimizer(torch.optim.Optimizer):
     `guard`: a `GradGuard` or None (the default).  It is an attribute of the optimizer, not a param-group key and not part
     of `state[p]`: `state_dict()` is the torch class's with or without one.  With a guard, `step()` issues the guard's
     partial, finish and scale launches over the same table and then the guarded `advance` and `step` entry points, which
-    do nothing when the guard decided to skip; without one it issues exactly `advance` and `step`."""
+    do nothing when the guard decided to skip; without one it issues exactly `advance` and `step`.
+
+    `averager`: a `WeightAverage` or None (the default), an attribute like `guard` and as little a part of `state_dict()`.
+    With one, `step()` issues the averager's `advance` and `update` launches after its own (handing them the guard's state
+    block when there is a guard, so a skipped step is not averaged in), `push_hyper()` pushes its config, and
+    `snapshot_state` / `restore_state` cover its shadows and result words; `step()` raises while the averaged weights are
+    swapped in.  Without one the launches are exactly those above."""
 
     _SET = _ADVANCE = _STEP = None       # entry points
     _GUARDED_ADVANCE = _GUARDED_STEP = None   # advance and step that take a GradGuard's state block
@@ -300,6 +592,7 @@ class DeviceOptimizer(torch.optim.Optimizer):
         self._hyper = None           # device block, NHYPER fp64 per group
         self._held = []              # host mirror of it, one tuple per group
         self.guard = None            # a GradGuard, or None
+        self.averager = None         # a WeightAverage, or None
         super().__init__(params, defaults)
 
     @property
@@ -335,9 +628,11 @@ class DeviceOptimizer(torch.optim.Optimizer):
 
     def push_hyper(self):
         """make the device block hold what `param_groups` say: one `set` launch per group that changed; and the guard's
-        config, when there is a guard and it changed"""
+        and the averager's config, when there is one and it changed"""
         if self.guard is not None:
             self.guard.push(self._device())
+        if self.averager is not None:
+            self.averager.push(self._device())
         n = len(self.param_groups)
         if self._hyper is None or self._hyper.numel() < n * NHYPER:
             if torch.cuda.is_current_stream_capturing():
@@ -454,6 +749,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         dev = self._device()
+        if self.averager is not None:
+            self.averager._refuse_applied(f"{self._name}.step()")
         self.push_hyper()
         if torch.cuda.is_current_stream_capturing():
             table = self._capture
@@ -481,6 +778,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
             gs = ptr(guard._state)
             call(self._GUARDED_ADVANCE, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), gs, stream())
             call(self._GUARDED_STEP, ptr(table.buf), table.n, ptr(table.derived), table.total, gs, stream())
+        if table.n and self.averager is not None:            # after the update, and only of a step the guard let happen
+            self.averager._issue(self.guard)
         return loss
 
     # ---- what a warm-up must not leave behind (train.GraphedTrainStep): every state tensor and private word
@@ -494,6 +793,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
             snap.setdefault(p, {}).update((k, live[k].clone()) for k in self._PRIVATE_KEYS)
         if self.guard is not None:
             snap[self.guard] = self.guard.snapshot()
+        if self.averager is not None:
+            snap[self.averager] = self.averager.snapshot()
         return snap
 
     @torch.no_grad()
@@ -514,6 +815,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
                 put(p, k, live[k])
         if self.guard is not None:           # its results and counters; zero when it first ran after the snapshot
             self.guard.restore(snap.get(self.guard))
+        if self.averager is not None:        # its shadows and result words; a fresh one when it came after the snapshot
+            self.averager.restore(snap.get(self.averager))
 
     # ---- (de)serialisation: the loaded values go INTO the live tensors, whose addresses device tables (a captured
     # graph's among them) hold

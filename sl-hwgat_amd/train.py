@@ -239,6 +239,11 @@ class GraphedTrainStep:
     `reducer` the guard runs after `reducer.finish()`: each rank sees the all-reduced gradients and so the same norm.
     The warm-up leaves the guard's counters where they were (zero for a new guard).
 
+    Weight averaging.  A device optimizer that carries an `optim.WeightAverage` (`optimizer.averager`) issues the
+    averager's two launches behind its own, so every replay also updates the EMA / SWA of the weights, once per replay
+    whatever `micro_batch` is, and not at all when the guard skipped the step.  The warm-up leaves the averages and their
+    counters as they were.  While the averaged weights are swapped in (`averager.is_applied`) a call raises.
+
     With any other optimizer the step stays out of the graph and is issued right after the replay, so that it reads the
     param groups' hyper-parameters when it runs: a float lr captured in the graph would be frozen there (an lr scheduler
     would change nothing), and a tensor lr is read by torch's fused AdamW as float32 -- the float lr rounded, updates that
@@ -387,6 +392,9 @@ class GraphedTrainStep:
             raise ValueError(f"captured for {tuple(self.x.shape)} / {tuple(self.y.shape)}, got {tuple(x.shape)} / {tuple(y.shape)}")
         if self._addresses() != self._addr:
             raise RuntimeError("a parameter or buffer of the model was reallocated after the capture: capture again")
+        averager = getattr(self.opt, "averager", None)
+        if averager is not None:                         # a replay bypasses the optimizer's step() and its check
+            averager._refuse_applied("a GraphedTrainStep replay")
         if self.ragged:
             self._pad.load(x, y)                         # the rows, zeros behind them, the row count when it changed
         else:
