@@ -39,15 +39,17 @@ constexpr int SLD = 132;                                        // epilogue stag
 
 constexpr int SG_MFMA = 0x008, SG_VALU = 0x002, SG_VMEM_RD = 0x020, SG_DS_RD = 0x100, SG_DS_WR = 0x200;
 
-// pin one 64-MFMA chunk: G groups of { 64/G MFMAs, NV vector instructions, N1 x M1, N2 x M2 }
+// pin one 64-MFMA chunk: G groups of { NV vector instructions, N1 x M1, N2 x M2, 64/G MFMAs }.  The memory instructions
+// of a group stand IN FRONT of its MFMAs: the chunk's last LDS read is then 64/G MFMAs old when the next chunk (or the
+// barrier) waits for it, instead of having been issued one instruction earlier.
 template <int G, int M1, int N1, int M2 = 0, int N2 = 0, int NV = 0>
 __device__ __forceinline__ void pin() {
 #pragma unroll
     for (int q = 0; q < G; ++q) {
-        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 64 / G, 0);
         if constexpr (NV > 0) __builtin_amdgcn_sched_group_barrier(SG_VALU, NV, 0);
         if constexpr (N1 > 0) __builtin_amdgcn_sched_group_barrier(M1, N1, 0);
         if constexpr (N2 > 0) __builtin_amdgcn_sched_group_barrier(M2, N2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 64 / G, 0);
     }
 }
 
@@ -163,16 +165,23 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_k(NtArgs p) {
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[i][e], f.b[j][e], acc[i][j], 0, 0, 0);
     };
-    // one slab: 4 chunks of 64 MFMAs.  The 16 global loads of the NEXT slab ride in chunk 0, its LDS commit (with the
-    // prologue arithmetic) in chunk 2.  ONE body for every slab: the next slab of a tile's last slab is the next
-    // tile's first (the loaders are retargeted before that body runs; when there is no next tile they harmlessly
-    // re-read this one), so there is no specialised tile-boundary body for the register allocator to spill in
-    // (the round's first version had one, with 50 scratch accesses and an s_waitcnt vmcnt(0) behind every load).
+    // one slab: 4 chunks of 64 MFMAs, entered with f0 = the slab's first fragments already in registers.  The 16 global
+    // loads of the NEXT slab ride in chunk 0, its LDS commit (with the prologue arithmetic) in chunk 2, the slab's ONE
+    // barrier stands between chunk 2 and chunk 3, and chunk 3 reads the next slab's first fragments: the matrix pipe
+    // never starts a slab on operands that are still on their way from LDS.
+    // Why two buffers and one barrier suffice: buffer b is written in chunk 2 of the slab BEFORE its use, ahead of that
+    // slab's barrier; it is read from chunk 3 of that slab (behind the barrier) through chunk 2 of the next, and every
+    // one of those reads is issued ahead of the next slab's barrier; b is written again in chunk 2 of the slab after
+    // that, which a wave reaches only through that barrier.
+    // ONE body for every slab: the next slab of a tile's last slab is the next tile's first (the loaders are
+    // retargeted before that body runs; when there is no next tile they harmlessly re-read this one), so there is no
+    // specialised tile-boundary body for the register allocator to spill in (the round's first version had one, with
+    // 50 scratch accesses and an s_waitcnt vmcnt(0) behind every load).
     auto slab_body = [&](int buf, int64_t m_next, int s_next) {
         fetch(f1, buf, 1);
         issue(s_next);
         mfma64(f0);
-        pin<16, SG_DS_RD, 1, SG_VMEM_RD, 1>();
+        pin<8, SG_DS_RD, 1, SG_VMEM_RD, 2>();
         __builtin_amdgcn_sched_barrier(0);
         fetch(f0, buf, 2);
         mfma64(f1);
@@ -183,9 +192,11 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_k(NtArgs p) {
         mfma64(f0);
         pin<8, SG_DS_WR, 2, SG_DS_RD, 1, PRO_VALU>();
         __builtin_amdgcn_sched_barrier(0);
-        mfma64(f1);
-        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
+        fetch(f0, buf ^ 1, 0);
+        mfma64(f1);
+        pin<8, SG_DS_RD, 1>();
+        __builtin_amdgcn_sched_barrier(0);
     };
 
     int t = blockIdx.x;
@@ -198,8 +209,11 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_k(NtArgs p) {
     commit(0, m0, 0);
     __syncthreads();
     int buf = 0;
+    fetch(f0, buf, 0);
 
     while (true) {
+        // (the reset stays at the head of the tile: moved into the epilogue, behind the stores that park each piece, it
+        //  has to be opaque to the compiler, and every such form spilled -- LABLOG 10.13)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -209,17 +223,18 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_k(NtArgs p) {
 
         const int tn = t + gridDim.x;
         int64_t mn = m0; int nn = n0;
+#pragma nounroll    // no peeled last iteration: that was a second slab body, whose register assignment cost ~200 accumulator moves per tile
         for (int s = 0; s < n_slab; ++s) {
             const bool last = s + 1 == n_slab;
             if (last) {                                         // the slab streamed in next belongs to the next tile
                 if (tn < n_tiles) tile_origin(tn, mn, nn);
                 set_tile(mn, nn);
             }
-            fetch(f0, buf, 0);
             slab_body(buf, last ? mn : m0, last ? 0 : s + 1);
             buf ^= 1;
         }
-        // buf = the next tile's slab 0 (if any); buf^1 is idle now
+        // buf = the next tile's slab 0 (if any), whose first fragments f0 holds across the epilogue; buf^1 is idle now:
+        // every wave issued its last reads of it ahead of the last slab's barrier
 
         // ---- epilogue.  acc[i][j]: lane (n = lq, hh), reg r -> C[m = 32 i + crow(r,hh)][n = 32 j + lq] of the wave tile
         {
@@ -322,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256_k(NtArgs p) {
                 atomicAdd(p.stat_sq + mr, rowstat[2 * tid + 1] + rowstat[2 * (BT + tid) + 1]);
             }
         }
-        __syncthreads();            // staging lives in buf^1, which the next tile's second slab overwrites
+        __syncthreads();            // staging lives in buf^1, which the next tile's first slab overwrites in its chunk 2
         t = tn;
         if (t >= n_tiles) break;
         m0 = mn; n0 = nn;
