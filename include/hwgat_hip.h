@@ -70,7 +70,9 @@ extern "C" {
  *         hwgat_gguard_{set,partial,finish,scale}, the gradient guard (global-norm clipping and non-finite detection on the
  *         device), and hwgat_gguard_{adamw,sgd,nadam}_{advance,step}, the three optimizers' launches under a guard;
  *         hwgat_bsce_{fwd,bwd}, the smoothed cross-entropy of one slice of a zero-padded batch (additions only);
- *         hwgat_wavg_{set,advance,update,swap}, EMA / equal-weight averages of the weights on the device (additions only) */
+ *         hwgat_wavg_{set,advance,update,swap}, EMA / equal-weight averages of the weights on the device (additions only);
+ *         hwgat_meter_{bytes,fold,close}, the train meters: per-epoch sums, a step log and closed epochs kept on the
+ *         device (additions only) */
 #define HWGAT_ABI_VERSION 4006
 int hwgat_abi_version(void);
 
@@ -696,6 +698,63 @@ int hwgat_wavg_set(double* state, int mode, double decay, int warmup, int64_t st
 int hwgat_wavg_advance(double* state, const double* guard_state, void* stream);
 int hwgat_wavg_update(const hwgat_wavg_entry* table, int n, const double* state, int total_blocks, void* stream);
 int hwgat_wavg_swap(const hwgat_wavg_entry* table, int n, int total_blocks, void* stream);
+
+/* ---- train meters: what the reference's train() reads back after every batch (utils.py:109-114: `loss.item()`, the
+ * correct predictions) summed on the device instead, so a train step captured in a HIP graph needs no host read per batch;
+ * one more launch behind the optimizer's (and the averager's), one read per epoch or later.
+ *
+ * block: hwgat_meter_bytes(log_capacity, history_capacity) bytes of DEVICE memory, 8-byte aligned, zeroed once by the
+ *   caller, in 8-byte words:
+ *     [0, HWGAT_METER_RUN)                 header, int64: HWGAT_METER_LOG_TOTAL (records ever appended to the log),
+ *                                          HWGAT_METER_CLOSED (epochs closed), HWGAT_METER_OVERFLOW (closes that found the
+ *                                          history full), one spare
+ *     [HWGAT_METER_RUN, HWGAT_METER_LOG)   the running words of the open epoch: HWGAT_METER_NRUN words at the HWGAT_METER_R_*
+ *                                          slots.  int64: steps, rows, correct, finite_steps, nonfinite_loss, skipped;
+ *                                          fp64: loss_sum, max_grad_norm; fp32 in the word's low four bytes (the high four
+ *                                          are zero): last_loss, max_loss
+ *     [HWGAT_METER_LOG, + 2 log_capacity)  the step log, a ring of 16-byte records { float loss; int32 correct; int32 rows;
+ *                                          float grad_norm }: record number r (from 0) sits in slot r % log_capacity, so
+ *                                          the ring holds the latest min(LOG_TOTAL, log_capacity) of them
+ *     [.., + NRUN history_capacity)        the closed epochs, HWGAT_METER_NRUN words each, a copy of the running words
+ *
+ * hwgat_meter_fold:  one thread folds one step.  loss: the step's fp32 device word; correct: its int64 device word; n_rows:
+ *                    its int32 device word with the real row count, or NULL: the constant batch_rows (>= 0) counts;
+ *                    guard_state: a gradient guard's block (HWGAT_GGUARD_*), or NULL.
+ *                      steps += 1; rows += n; correct += correct;
+ *                      loss finite:  finite_steps += 1; loss_sum = loss_sum + (double)loss -- one IEEE addition per step in
+ *                                    fold order, nothing fused: what Python's `total += loss.item()` gives, bit for bit;
+ *                                    max_loss = the first finite loss of the epoch, then the larger;
+ *                      otherwise:    nonfinite_loss += 1, loss_sum and max_loss untouched;
+ *                      last_loss = loss (whatever it is);
+ *                      guard: skipped += (skip word != 0); max_grad_norm = total_norm where total_norm > max_grad_norm (a
+ *                             NaN norm never is, an Inf norm is);
+ *                      log (log_capacity > 0): record { loss, (int32)correct, (int32)n, (float)total_norm or 0 },
+ *                      LOG_TOTAL += 1.
+ *                    No atomics, no reduction: every sum has one order.
+ * hwgat_meter_close: copies the running words to history slot min(CLOSED, history_capacity - 1) (none when
+ *                    history_capacity is 0), OVERFLOW += (CLOSED >= history_capacity), CLOSED += 1, zeroes the running
+ *                    words; the step log and LOG_TOTAL stay. */
+#define HWGAT_METER_LOG_TOTAL 0
+#define HWGAT_METER_CLOSED 1
+#define HWGAT_METER_OVERFLOW 2
+#define HWGAT_METER_RUN 4
+#define HWGAT_METER_NRUN 12
+#define HWGAT_METER_LOG (HWGAT_METER_RUN + HWGAT_METER_NRUN)
+#define HWGAT_METER_R_STEPS 0
+#define HWGAT_METER_R_ROWS 1
+#define HWGAT_METER_R_CORRECT 2
+#define HWGAT_METER_R_LOSS_SUM 3
+#define HWGAT_METER_R_FINITE_STEPS 4
+#define HWGAT_METER_R_NONFINITE_LOSS 5
+#define HWGAT_METER_R_SKIPPED 6
+#define HWGAT_METER_R_LAST_LOSS 7
+#define HWGAT_METER_R_MAX_LOSS 8
+#define HWGAT_METER_R_MAX_GRAD_NORM 9
+#define HWGAT_METER_MAX_CAPACITY (1 << 24)
+int64_t hwgat_meter_bytes(int log_capacity, int history_capacity);
+int hwgat_meter_fold(int64_t* block, const float* loss, const int64_t* correct, const int32_t* n_rows, int batch_rows,
+                     const double* guard_state, int log_capacity, void* stream);
+int hwgat_meter_close(int64_t* block, int log_capacity, int history_capacity, void* stream);
 
 /* the dropout mask the fused kernels use: out[i] = keep(seed, i) ? 1/(1-p) : 0 */
 int hwgat_dropout_mask_f32(float* out, int64_t n, uint32_t seed, float p, const uint32_t* seed_base, void* stream);

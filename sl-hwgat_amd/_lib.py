@@ -152,6 +152,9 @@ _SIGS = {
     "hwgat_wavg_advance": [_P, _P, _P],
     "hwgat_wavg_update": [_P, _I, _P, _I, _P],
     "hwgat_wavg_swap": [_P, _I, _I, _P],
+    "hwgat_meter_bytes": [_I, _I],
+    "hwgat_meter_fold": [_P, _P, _P, _P, _I, _P, _I, _P],
+    "hwgat_meter_close": [_P, _I, _I, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

@@ -12,12 +12,14 @@ checkpoint written by either side loads on the other:
   load_checkpoint               utils.py:216-237   weights as above + optimizer / scheduler state, start epoch, 4 lists
   get_optimizer / get_scheduler utils.py:71-88     AdamW(lr) by default; CosineAnnealingLR(T_max=20, last_epoch=-1)
   get_device_optimizer          utils.py:71-82     the same four optimizer types on this backend's HIP kernels
+  read_extra                    --                 what save_checkpoint(extra=...) put next to the nine keys (train.EpochLoop)
 """
 from typing import Optional
 
 import torch
 
 _LISTS = ("train_loss_list", "val_loss_list", "train_acc_list", "val_acc_list")
+EXTRA_KEY = "extra"     # this backend's own key next to the reference's nine (save_checkpoint(extra=...), read_extra)
 
 
 def get_optimizer(model, lr: float = 5e-4, optimizer_type: str = "adamw", fused: Optional[bool] = None,
@@ -93,13 +95,16 @@ def _plain(v):
 
 
 def save_checkpoint(path, model, optimizer, scheduler, train_acc_list, train_loss_list, val_acc_list, val_loss_list,
-                    epoch, lr):
+                    epoch, lr, extra=None):
     """same argument order and the same dict layout as utils.py:164-176.  Learning rates are written as floats even when
-    the optimizer holds them as tensors: the reference's AdamW(foreach=True) refuses a tensor lr."""
+    the optimizer holds them as tensors: the reference's AdamW(foreach=True) refuses a tensor lr.  `extra` (a dict of
+    plain Python values and tensors: numbers, strings, lists, dicts -- what `weights_only=True` loads) goes under one more key,
+    'extra', which the reference's loader never looks at; None (the default) writes exactly the reference's nine keys.
+    `read_extra` returns it."""
     opt_state = optimizer.state_dict()
     opt_state["param_groups"] = [{k: (v if k == "params" else _plain(v)) for k, v in g.items()}
                                  for g in opt_state["param_groups"]]
-    torch.save({
+    ckpt = {
         "model_state_dict": model.state_dict(),
         "optimizer_state_dict": opt_state,
         "train_loss_list": train_loss_list,
@@ -109,13 +114,23 @@ def save_checkpoint(path, model, optimizer, scheduler, train_acc_list, train_los
         "epoch": epoch,
         "learning_rate": lr,
         "scheduler": _plain(scheduler.state_dict()),
-    }, path)
+    }
+    if extra is not None:
+        if not isinstance(extra, dict):
+            raise TypeError(f"extra must be a dict of plain values or None, got {type(extra).__name__}")
+        ckpt[EXTRA_KEY] = extra
+    torch.save(ckpt, path)
 
 
 def _read(path, device):
     # a checkpoint is tensors + python scalars / lists: the safe loader suffices (and is required for files that
     # were not written by this process)
     return torch.load(path, map_location=device, weights_only=True)
+
+
+def read_extra(path, device="cpu"):
+    """the dict `save_checkpoint(extra=...)` wrote, {} for a file without one (the reference's own files)"""
+    return _read(path, device).get(EXTRA_KEY, {})
 
 
 def load_weights_from_pretrained(model, pretrained_model_path, device="cpu", report=None):

@@ -1435,6 +1435,46 @@ def batch_sliced_ce(logits, target, eps, n_rows, offset):
     return _BatchSlicedCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_rows, int(offset))
 
 
+# ---------------------------------------------------------------- train meters (csrc/train_meter.hip, train.TrainMeter)
+# The block is int64 words (layout: include/hwgat_hip.h, "train meters"; the slot constants are mirrored in train.py).
+def meter_words(log_capacity, history_capacity):
+    """size of a meter block in 8-byte words"""
+    n = _lib.lib().hwgat_meter_bytes(int(log_capacity), int(history_capacity))
+    if n < 0:
+        raise ValueError(f"no meter block for log capacity {log_capacity}, history capacity {history_capacity}")
+    return n // 8
+
+
+def _meter_check(block, log_capacity, history_capacity):
+    if block.dtype != torch.int64 or block.numel() < meter_words(log_capacity, history_capacity):
+        raise ValueError("the meter block must be int64 and meter_words(log_capacity, history_capacity) long")
+
+
+def meter_fold(block, loss, correct, n_rows, batch_rows, guard_state, log_capacity, history_capacity):
+    """fold one step into `block`: loss a one-element fp32 device tensor, correct a one-element int64 one, n_rows a
+    one-element int32 one or None (then the host integer `batch_rows` counts), guard_state a GradGuard's fp64 block or
+    None.  One launch; nothing is read back"""
+    _meter_check(block, log_capacity, history_capacity)
+    if loss.dtype != torch.float32 or loss.numel() != 1:
+        raise ValueError(f"the step loss must be one fp32 element, got {loss.dtype} {tuple(loss.shape)}")
+    if correct.dtype != torch.int64 or correct.numel() != 1:
+        raise ValueError(f"the correct count must be one int64 element, got {correct.dtype} {tuple(correct.shape)}")
+    if n_rows is not None and (n_rows.dtype != torch.int32 or n_rows.numel() != 1):
+        raise ValueError("n_rows must be a device int32 tensor of one element")
+    if n_rows is None and not 0 <= int(batch_rows) < 2 ** 31:
+        raise ValueError(f"batch_rows must be in [0, 2^31) when there is no n_rows word, got {batch_rows}")
+    if guard_state is not None and (guard_state.dtype != torch.float64 or guard_state.numel() < 16):
+        raise ValueError("guard_state must be a gradient guard's fp64 block")
+    call("hwgat_meter_fold", ptr(block), ptr(loss), ptr(correct), ptr(n_rows), 0 if n_rows is not None else int(batch_rows),
+         ptr(guard_state), int(log_capacity), stream())
+
+
+def meter_close(block, log_capacity, history_capacity):
+    """close the epoch: the running words go to the next history slot and are zeroed.  One launch"""
+    _meter_check(block, log_capacity, history_capacity)
+    call("hwgat_meter_close", ptr(block), int(log_capacity), int(history_capacity), stream())
+
+
 # ---------------------------------------------------------------- the classifier head (csrc/head.hip)
 # logits = feat W^T + bias on the project's own kernels: exact fp32, fixed summation order, so a clip's logits have the same
 # bits at any batch size.  Opt-in per model (`model.hip_head = True`, seeding.DeviceSeeds._classify).

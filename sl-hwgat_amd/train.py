@@ -1,7 +1,9 @@
 """Loss and the fwd+bwd step harness of the hot path (reference hwgat/utils.py:93-116
 and hwgat/losses/SmoothCrossEntropy.py), without the per-step host syncs."""
+import contextlib
 import numbers
 
+import numpy as np
 import torch
 import torch.nn.functional as tF
 
@@ -144,6 +146,14 @@ def _correct(criterion, out, y):
     return (out.detach().argmax(-1) == y).sum()
 
 
+def _guard_of(optimizer):
+    """the GradGuard of a device optimizer that carries one, else None"""
+    import importlib
+    if isinstance(optimizer, importlib.import_module(__package__ + ".optim").DeviceOptimizer):
+        return optimizer.guard
+    return None
+
+
 class TrainStep:
     """zero_grad -> forward -> loss -> backward (-> bucketed all-reduce) -> optimizer.
 
@@ -161,10 +171,14 @@ class TrainStep:
     gradient are those of the real rows (a padding row has finite activations and an exactly zero upstream gradient:
     DESIGN.md section 6o).  This is what `GraphedTrainStep(ragged=True)` captures, run eagerly: the two agree bit for bit
     under `deterministic_train`.  Models whose train forward couples clips (ST-GCN, DecoupledGCN) are refused.  `None`
-    (the default): the batch runs as it comes."""
+    (the default): the batch runs as it comes.
 
-    def __init__(self, model, optimizer=None, reducer=None, criterion=None, micro_batch=None, pad_to=None):
-        self.model, self.opt, self.reducer = model, optimizer, reducer
+    `meter`: a `TrainMeter`; every call ends with its fold launch (after the optimizer's and the averager's), which adds
+    the step's loss, correct count and row count -- and the verdict and norm of the device optimizer's guard -- to the
+    meter's device words.  `None` (the default): the launch sequence is what it has always been."""
+
+    def __init__(self, model, optimizer=None, reducer=None, criterion=None, micro_batch=None, pad_to=None, meter=None):
+        self.model, self.opt, self.reducer, self.meter = model, optimizer, reducer, meter
         self.pad_to, self._pad = pad_to, None
         if pad_to is not None:
             if isinstance(pad_to, bool) or not isinstance(pad_to, numbers.Integral) or pad_to < 1:
@@ -203,6 +217,8 @@ class TrainStep:
         if self.opt is not None:
             self.opt.step()
         self.loss, self.correct = total, correct
+        if self.meter is not None:
+            self.meter.fold(total, correct, n_rows=self.n_rows, batch_rows=n, guard=_guard_of(self.opt))
         return self.loss
 
 
@@ -270,6 +286,14 @@ class GraphedTrainStep:
     (`clips_independent_in_train` False: ST-GCN, DecoupledGCN) are refused.  `TrainStep(pad_to=B)` is the same computation
     issued eagerly.
 
+    Meters.  `meter=TrainMeter(...)` makes the meter's fold the last launch of the step and so the last node of the graph,
+    behind the optimizer's and the averager's, once per replay whatever `micro_batch` is: it adds the summed `loss` and
+    `correct`, the ragged step's `n_rows` word (else the static batch size) and the guard's verdict and norm to the
+    meter's device words, so a training loop reads its epoch's numbers once (`meter.close_epoch()`, `meter.history()`)
+    instead of `loss` / `correct` after every replay.  With an optimizer that stays out of the graph the fold is still
+    captured, after the backward.  The warm-up leaves the meter as it found it.  `None` (the default): the captured node
+    sequence is what it has always been.
+
     Inputs are copied into static buffers; `loss` / `correct` are static device tensors rewritten by every replay.
     Shapes are fixed at capture.  Parameters must not be reallocated afterwards (same rule as serve.GraphedEval).
     The warm-up's traces in the model's buffers (BatchNorm running statistics) are undone like those in the weights.
@@ -277,7 +301,8 @@ class GraphedTrainStep:
     draws in its k-th step from the same `c` (tests/test_gpu_graph.py).  Each forward hands its kernels a per-call copy of
     the base seed (seeding.DeviceSeeds._next_step_seed); in the graph that copy is a node after the seed advance."""
 
-    def __init__(self, model, optimizer, x, y, criterion=None, warmup=2, reducer=None, micro_batch=None, ragged=False):
+    def __init__(self, model, optimizer, x, y, criterion=None, warmup=2, reducer=None, micro_batch=None, ragged=False,
+                 meter=None):
         import importlib
         HF = importlib.import_module(__package__ + ".functional")
         micro_batch = _check_micro_batch(micro_batch)
@@ -296,7 +321,7 @@ class GraphedTrainStep:
         for grp in optimizer.param_groups:
             if not self.in_graph and not grp.get("capturable", False):
                 raise ValueError("the optimizer must be built with capturable=True (its step count then lives on the device)")
-        self.model, self.opt, self.reducer = model, optimizer, reducer
+        self.model, self.opt, self.reducer, self.meter = model, optimizer, reducer, meter
         self.criterion = criterion or SmoothedCrossEntropyLoss()
         self.ragged, self._pad = bool(ragged), None
         if self.ragged:
@@ -320,6 +345,7 @@ class GraphedTrainStep:
             keep_state = optimizer.snapshot_state()
         else:
             keep_state = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in optimizer.state.items()}
+        keep_meter = None if meter is None else meter.bind(dev).snapshot()   # the block exists before the capture
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 self._one()
@@ -339,7 +365,9 @@ class GraphedTrainStep:
                                 v.copy_(keep_state[p][k])
                             else:
                                 v.zero_()
-        del keep_p, keep_b, keep_state
+            if meter is not None:                        # the warm-up's folds never happened
+                meter.restore(keep_meter)
+        del keep_p, keep_b, keep_state, keep_meter
         model.device_seed_counter = True                 # from here on the device counts the steps itself
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
@@ -375,11 +403,18 @@ class GraphedTrainStep:
                 self.reducer.finish()
             if step:
                 self.opt.step()
-            return loss.detach(), _correct(self.criterion, out, self.y)
+            return self._fold(loss.detach(), _correct(self.criterion, out, self.y))
         loss, correct = _run_slices(self.model, self.criterion, self.x, self.y, self.micro_batch, weighted=not self.ragged,
                                     n_rows=self.n_rows)
         if step:                                         # once, after the last slice (no reducer here: refused above)
             self.opt.step()
+        return self._fold(loss, correct)
+
+    def _fold(self, loss, correct):
+        """the meter's launch, the last of the step: once per step, on the sums the step returns"""
+        if self.meter is not None:
+            self.meter.fold(loss, correct, n_rows=self.n_rows, batch_rows=self.x.shape[0],
+                            guard=_guard_of(self.opt) if self.in_graph else None)
         return loss, correct
 
     def _addresses(self):
@@ -414,3 +449,464 @@ class GraphedTrainStep:
         else:
             self.opt.step()                              # on the gradients the replay wrote, with the current lr
         return self.loss
+
+
+# ---------------------------------------------------------------------------------------------------- train meters
+# The meter block of csrc/train_meter.hip in 8-byte words; the constants mirror HWGAT_METER_* of include/hwgat_hip.h
+METER_LOG_TOTAL, METER_CLOSED, METER_OVERFLOW = 0, 1, 2
+METER_RUN, METER_NRUN = 4, 12
+METER_LOG = METER_RUN + METER_NRUN
+(METER_R_STEPS, METER_R_ROWS, METER_R_CORRECT, METER_R_LOSS_SUM, METER_R_FINITE_STEPS, METER_R_NONFINITE_LOSS,
+ METER_R_SKIPPED, METER_R_LAST_LOSS, METER_R_MAX_LOSS, METER_R_MAX_GRAD_NORM) = range(10)
+METER_MAX_CAPACITY = 1 << 24
+_METER_INTS = (("steps", METER_R_STEPS), ("rows", METER_R_ROWS), ("correct", METER_R_CORRECT),
+               ("finite_steps", METER_R_FINITE_STEPS), ("nonfinite_loss", METER_R_NONFINITE_LOSS),
+               ("skipped", METER_R_SKIPPED))
+
+
+def _meter_entry(words):
+    """METER_NRUN int64 words (the running words, or a closed epoch) as a dict: the raw words under their own names, and
+    `loss` = loss_sum / finite_steps (utils.py:116's total_loss / num_batches when every loss is finite), `acc` = correct /
+    rows (its sum(train_acc) / len(train_acc))"""
+    w = np.ascontiguousarray(words, dtype=np.int64)
+    f64, f32 = w.view(np.float64), w.view(np.float32)         # an fp32 word sits in the low four bytes: index 2 i
+    d = {name: int(w[i]) for name, i in _METER_INTS}
+    d.update(loss_sum=float(f64[METER_R_LOSS_SUM]), last_loss=float(f32[2 * METER_R_LAST_LOSS]),
+             max_loss=float(f32[2 * METER_R_MAX_LOSS]), max_grad_norm=float(f64[METER_R_MAX_GRAD_NORM]))
+    d["loss"] = d["loss_sum"] / max(d["finite_steps"], 1)
+    d["acc"] = d["correct"] / max(d["rows"], 1)
+    return d
+
+
+class TrainMeter:
+    """What a training loop reports per epoch, summed on the device (csrc/train_meter.hip): the reference's train()
+    reads `loss.item()` and the correct predictions back after every batch (utils.py:109-114); a meter handed to
+    `GraphedTrainStep` / `TrainStep` (`meter=`) folds them in with one launch at the end of every step -- a node of the
+    graph -- and the host reads when it wants to.
+
+        meter = train.TrainMeter(log_capacity=256)
+        step = train.GraphedTrainStep(model, opt, x, y, ragged=True, meter=meter)
+        for x, y in loader: step(x, y)          # nothing is read back
+        meter.close_epoch()                      # the running words become the next entry of history()
+        meter.history()[-1]["loss"], meter.history()[-1]["acc"]
+
+    The running words of the open epoch: steps, rows (real rows), correct, loss_sum (fp64, one addition per step in step
+    order: bit for bit Python's `total += loss.item()`), finite_steps, nonfinite_loss (steps with a NaN or Inf loss: counted,
+    not added), skipped (steps the optimizer's GradGuard turned into a no-op), last_loss, max_loss (over the finite
+    losses), max_grad_norm (the largest norm the guard reported; a NaN norm never counts, an Inf one does).
+    `log_capacity` > 0 also keeps the latest that many steps' (loss, correct, rows, grad_norm) in a ring: the loss curve
+    per step without a sync.  `history_capacity` closed epochs are kept; a close past it overwrites the last entry and is
+    counted (`overflow`).
+
+    The block is allocated by `bind(device)` or the first `fold`, never inside a capture."""
+
+    def __init__(self, log_capacity=0, history_capacity=1024):
+        for name, v in (("log_capacity", log_capacity), ("history_capacity", history_capacity)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v <= METER_MAX_CAPACITY:
+                raise ValueError(f"TrainMeter: {name} must be an integer in [0, {METER_MAX_CAPACITY}], got {v!r}")
+        self.log_capacity, self.history_capacity = int(log_capacity), int(history_capacity)
+        self._block = None           # device block, int64 words
+        self._loaded = None          # the words of a load_state_dict() that came before the device block existed
+
+    @property
+    def words(self):
+        """length of the block in 8-byte words"""
+        return METER_LOG + 2 * self.log_capacity + METER_NRUN * self.history_capacity
+
+    # ---- device side
+    def bind(self, device):
+        """allocate the block on `device` (once; a meter serves one device)"""
+        device = torch.device(device)
+        if self._block is None:
+            if device.type != "cuda":
+                raise RuntimeError("TrainMeter needs an MI355X device; there is no CPU fallback")
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("TrainMeter: fold once (or bind()) before capturing")
+            HF = _functional()
+            if HF.meter_words(self.log_capacity, self.history_capacity) != self.words:
+                raise RuntimeError("TrainMeter: the library lays the block out differently from train.py's constants")
+            self._block = torch.zeros(self.words, dtype=torch.int64, device=device)
+            if self._loaded is not None:
+                self._block.copy_(torch.from_numpy(self._loaded))
+                self._loaded = None
+        elif self._block.device != device and not (device.index is None and self._block.device.type == device.type):
+            raise ValueError(f"TrainMeter lives on {self._block.device}, the step on {device}")
+        return self
+
+    def fold(self, loss, correct, n_rows=None, batch_rows=None, guard=None):
+        """one launch: add a step.  `loss` its fp32 device word, `correct` its int64 one; the row count is the device
+        int32 word `n_rows` or, without one, the host integer `batch_rows`; `guard` an `optim.GradGuard` (or its fp64
+        block) whose skip verdict and norm of this step are recorded, or None"""
+        if n_rows is None and batch_rows is None:
+            raise ValueError("TrainMeter.fold: give the row count, as the device word n_rows or the integer batch_rows")
+        self.bind(loss.device)
+        state = guard
+        if guard is not None and not torch.is_tensor(guard):
+            state = guard.bind(loss.device)._bound()
+        _functional().meter_fold(self._block, loss, correct, n_rows, 0 if batch_rows is None else batch_rows, state,
+                                 self.log_capacity, self.history_capacity)
+
+    def close_epoch(self):
+        """one launch: the running words become the next closed epoch and start again from zero; the step log goes on"""
+        if self._block is None:
+            raise RuntimeError("TrainMeter has folded nothing yet: its block lives on the device of its first step (or bind())")
+        _functional().meter_close(self._block, self.log_capacity, self.history_capacity)
+
+    def reset(self):
+        """everything back to zero: running words, step log, closed epochs"""
+        self._loaded = None
+        if self._block is not None:
+            self._block.zero_()
+
+    # ---- what a warm-up must not leave behind
+    def snapshot(self):
+        return None if self._block is None else self._block.clone()
+
+    def restore(self, snap):
+        if self._block is not None:
+            if snap is None:
+                self._block.zero_()
+            else:
+                self._block.copy_(snap)
+
+    # ---- readouts: each is ONE host read
+    def _host(self):
+        if self._block is not None:
+            return self._block.cpu().numpy()
+        return np.zeros(self.words, dtype=np.int64) if self._loaded is None else self._loaded.copy()
+
+    def result(self):
+        """the open epoch so far, as a dict (see the class docstring; `loss` and `acc` as the reference computes them)"""
+        return self._result(self._host())
+
+    @staticmethod
+    def _result(h):
+        d = _meter_entry(h[METER_RUN:METER_LOG])
+        d.update(log_total=int(h[METER_LOG_TOTAL]), epochs_closed=int(h[METER_CLOSED]), overflow=int(h[METER_OVERFLOW]))
+        return d
+
+    def _history(self, h):
+        kept = min(int(h[METER_CLOSED]), self.history_capacity)
+        base = METER_LOG + 2 * self.log_capacity
+        return [_meter_entry(h[base + i * METER_NRUN:base + (i + 1) * METER_NRUN]) for i in range(kept)]
+
+    def history(self):
+        """the closed epochs, oldest first, one dict each; after an overflow the last one is the latest close"""
+        return self._history(self._host())
+
+    def step_log(self):
+        """the logged steps in step order: dicts of step (its number since the last reset, from 0), loss, correct, rows,
+        grad_norm; the latest `log_capacity` of them"""
+        h = self._host()
+        total, cap = int(h[METER_LOG_TOTAL]), self.log_capacity
+        ring = h[METER_LOG:METER_LOG + 2 * cap]
+        f32, i32 = ring.view(np.float32), ring.view(np.int32)
+        out = []
+        for r in range(max(0, total - cap), total):
+            s = 4 * (r % cap)
+            out.append(dict(step=r, loss=float(f32[s]), correct=int(i32[s + 1]), rows=int(i32[s + 2]),
+                            grad_norm=float(f32[s + 3])))
+        return out
+
+    # ---- for a checkpoint's own extra key: plain Python values, the words as integers (exact for the fp64 sums too)
+    def state_dict(self):
+        h = self._host()
+        kept = min(int(h[METER_CLOSED]), self.history_capacity)
+        base = METER_LOG + 2 * self.log_capacity
+        return dict(log_capacity=self.log_capacity, history_capacity=self.history_capacity,
+                    head=[int(v) for v in h[:METER_LOG]], log=[int(v) for v in h[METER_LOG:base]],
+                    history=[int(v) for v in h[base:base + kept * METER_NRUN]])
+
+    def load_state_dict(self, sd):
+        if (int(sd["log_capacity"]), int(sd["history_capacity"])) != (self.log_capacity, self.history_capacity):
+            raise ValueError(f"TrainMeter.load_state_dict: the file's meter has capacities ({sd['log_capacity']}, "
+                             f"{sd['history_capacity']}), this one ({self.log_capacity}, {self.history_capacity})")
+        head, log, hist = list(sd["head"]), list(sd["log"]), list(sd["history"])
+        base = METER_LOG + 2 * self.log_capacity
+        if len(head) != METER_LOG or len(log) != 2 * self.log_capacity or len(hist) % METER_NRUN or base + len(hist) > self.words:
+            raise ValueError("TrainMeter.load_state_dict: the word lists do not fit this meter's block")
+        h = np.zeros(self.words, dtype=np.int64)
+        h[:base] = head + log
+        h[base:base + len(hist)] = hist
+        if self._block is None:
+            self._loaded = h
+        else:
+            self._block.copy_(torch.from_numpy(h))
+
+
+def _functional():
+    import importlib
+    return importlib.import_module(__package__ + ".functional")
+
+
+# ---------------------------------------------------------------------------------------------------- the epoch loop
+class EarlyStopper:
+    """Stop when the validation accuracy has stopped rising (the rule of the reference's utils.EarlyStopper).  The best
+    accuracy starts at 0.  `early_stop(acc)`: an accuracy above the best becomes the best and clears the count; any
+    other accuracy below best + `min_delta` adds one to the count, and the call that brings the count to `patience`
+    answers True.  (With `min_delta` 0 an accuracy equal to the best does neither.)"""
+
+    def __init__(self, patience=1, min_delta=0):
+        self.patience, self.min_delta = patience, min_delta
+        self.counter, self.max_validation_acc = 0, 0.0
+
+    def early_stop(self, validation_acc):
+        if validation_acc > self.max_validation_acc:
+            self.max_validation_acc, self.counter = validation_acc, 0
+            return False
+        if validation_acc < self.max_validation_acc + self.min_delta:
+            self.counter += 1
+            return self.counter >= self.patience
+        return False
+
+
+class EpochBook:
+    """The bookkeeping of run_epochs (utils.py:242-290) without a model or a GPU: the four per-epoch lists, the best
+    validation loss and accuracy, which checkpoint files an epoch writes and whether the run stops.
+
+    `record(epoch, train_loss, train_acc, val_loss, val_acc)` appends to the lists and returns `(suffixes, stop)`:
+    "best_loss" on a validation loss strictly below the best so far (9999 at the start), "best_acc" on a validation
+    accuracy strictly above the best so far (0.0 at the start), and str(epoch) when `epoch > 0 and epoch % save_interval
+    == 0`, in that order; `stop` is the early stopper's answer to the validation accuracy (False without one).
+    `EpochBook.resumed(lists, ...)` is the book of a run that goes on from a checkpoint's lists: the best values are the
+    lists' min / max, or 99999 / 0.0 when they are empty (utils.py:246-250)."""
+
+    def __init__(self, save_interval=100, early_stopper=None):
+        if isinstance(save_interval, bool) or not isinstance(save_interval, numbers.Integral) or save_interval < 1:
+            raise ValueError(f"save_interval must be a positive integer, got {save_interval!r}")
+        self.save_interval, self.early_stopper = int(save_interval), early_stopper
+        self.train_loss_list, self.val_loss_list, self.train_acc_list, self.val_acc_list = [], [], [], []
+        self.best_val_loss, self.best_val_acc = 9999, 0.0
+
+    @classmethod
+    def resumed(cls, lists, save_interval=100, early_stopper=None):
+        """`lists`: [train_loss, val_loss, train_acc, val_acc], the order checkpoint.load_checkpoint returns"""
+        book = cls(save_interval, early_stopper)
+        book.train_loss_list, book.val_loss_list, book.train_acc_list, book.val_acc_list = (list(v) for v in lists)
+        book.best_val_acc = 0.0 if len(book.val_acc_list) < 1 else max(book.val_acc_list)
+        book.best_val_loss = 99999 if len(book.val_acc_list) < 1 else min(book.val_loss_list)
+        return book
+
+    @property
+    def lists(self):
+        return [self.train_loss_list, self.val_loss_list, self.train_acc_list, self.val_acc_list]
+
+    def record(self, epoch, train_loss, train_acc, val_loss, val_acc):
+        self.train_loss_list.append(train_loss)
+        self.train_acc_list.append(train_acc)
+        self.val_loss_list.append(val_loss)
+        self.val_acc_list.append(val_acc)
+        suffixes = []
+        if val_loss < self.best_val_loss:
+            self.best_val_loss = val_loss
+            suffixes.append("best_loss")
+        if val_acc > self.best_val_acc:
+            self.best_val_acc = val_acc
+            suffixes.append("best_acc")
+        if epoch > 0 and epoch % self.save_interval == 0:
+            suffixes.append(str(epoch))
+        stop = bool(self.early_stopper is not None and self.early_stopper.early_stop(val_acc))
+        return suffixes, stop
+
+
+class _NoSchedule:
+    """stands in for `scheduler=None`: nothing to step, nothing to save"""
+
+    def step(self):
+        pass
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, sd):
+        pass
+
+
+class EpochLoop:
+    """The reference's run_epochs (utils.py:240-290) on this package's pieces: per epoch one pass over the train batches
+    through a train step with a `TrainMeter` (nothing is read back per batch), `scheduler.step()`, one pass over the
+    validation batches through an `evaluate.Evaluator`, the four lists, the checkpoints and the early stop.
+
+        loop = train.EpochLoop(model, opt, sched, batch_size=64, example=(x0, y0), num_classes=C, out_prefix="out/run1")
+        loop.run(train_batches, val_batches, epochs=100)
+
+    `example`: one (x, y) batch of `batch_size` rows; it fixes the shapes the step and the evaluator are built for.
+    `graph=True`: the train step is a `GraphedTrainStep(ragged=True, meter=...)`, the evaluator replays a graph as well;
+    `graph=False`: `TrainStep(pad_to=batch_size, meter=...)` and an eager evaluator.  Both are built at the first batch.
+    Models whose train forward couples the clips of a batch (`clips_independent_in_train` False: ST-GCN, DecoupledGCN)
+    cannot be padded: for them the loop builds the unpadded step and raises a ValueError at the first train batch that has
+    not `batch_size` rows (drop the last batch: `drop_last=True`); nothing falls back to another path.
+    `k`: the validation accuracy is top-k.  `out_prefix`: the reference's cfg.save_model_path -- files
+    `{out_prefix}_best_loss.pt`, `_best_acc.pt`, `_{epoch}.pt` through checkpoint.save_checkpoint; None writes nothing.
+    `lr`: the value recorded under 'learning_rate' (the reference's cfg.lr); default: the first param group's lr now.
+    `eval_averaged=True` evaluates on the optimizer's averaged weights (`optimizer.averager.applied()`).
+    `meter`: a `TrainMeter` of the caller's (say, one with a step log); `evaluator`: anything with reset() / update(x, y) /
+    result() -> {"loss", "acc": {k: ...}} in the Evaluator's place.
+
+    `run(train_batches, val_batches, epochs, start_epoch=None)`: two re-iterable sources of (x, y) batches, on the CPU
+    (copied with non_blocking=True; pinning is the loader's business, see collate.PinnedBatcher) or on the device.
+    `epochs` has the reference's meaning: the loop runs `range(start_epoch, epochs + 1)`, so a fresh run with epochs=2
+    trains three epochs.  `start_epoch=None` goes on where `resume()` (or nothing: 0) left it.
+
+    Train numbers are the meter's: loss = sum of the step losses / steps with a finite loss, acc = correct / real rows.
+    Validation loss is the sum of batch means / batches, as utils.py:131,142.
+
+    `resume(path)` loads a checkpoint of this loop (checkpoint.load_checkpoint): weights, optimizer, scheduler, the four
+    lists, `start_epoch = epoch + 1`, best values from the lists; and from the file's 'extra' key the guard's, the
+    averager's and the meter's state and the model's dropout counter, so dropout masks go on where they stopped.  Torch's
+    device generator state is NOT carried: it draws HWGATE's train-mode window thresholds (HWGATE.py:96), so a resumed
+    HWGATE run draws other thresholds than the uninterrupted one would have."""
+
+    def __init__(self, model, optimizer, scheduler, batch_size, example, num_classes, smooth_factor=0.01, k=1, graph=True,
+                 micro_batch=None, out_prefix=None, save_interval=100, early_stopper=None, lr=None, eval_averaged=False,
+                 meter=None, evaluator=None):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, numbers.Integral) or batch_size < 1:
+            raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+        x, y = example
+        if x.shape[0] != batch_size or y.shape != (batch_size,):
+            raise ValueError(f"the example batch must have batch_size = {batch_size} rows, got {tuple(x.shape)} with "
+                             f"targets {tuple(y.shape)}")
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 1:
+            raise ValueError(f"k must be a positive integer, got {k!r}")
+        if eval_averaged and getattr(optimizer, "averager", None) is None:
+            raise ValueError("eval_averaged needs an optimizer that carries an optim.WeightAverage (optimizer.averager)")
+        meter = TrainMeter() if meter is None else meter
+        if meter.history_capacity < 1:
+            raise ValueError("the loop reads each epoch from the meter's history: history_capacity must be at least 1")
+        self.model, self.opt, self.scheduler = model, optimizer, scheduler if scheduler is not None else _NoSchedule()
+        self.batch_size, self.example, self.num_classes = int(batch_size), (x, y), int(num_classes)
+        self.smooth_factor, self.k, self.graph = float(smooth_factor), int(k), bool(graph)
+        self.micro_batch = _check_micro_batch(micro_batch)
+        self.out_prefix, self.eval_averaged = out_prefix, bool(eval_averaged)
+        self.lr = _plain_lr(optimizer.param_groups[0]["lr"]) if lr is None else lr
+        self.meter, self.evaluator, self.step = meter, evaluator, None
+        self.book = EpochBook(save_interval, early_stopper)
+        self.start_epoch = 0
+        self.padded = bool(getattr(model, "clips_independent_in_train", False))
+        self.written = []            # the files of the latest run(), in the order they were written
+
+    # ---- the pieces, built at the first batch (on the device the model lives on)
+    def _device(self):
+        return next(self.model.parameters()).device
+
+    def _on_device(self, x, y):
+        dev = self._device()
+        if x.device != dev:
+            x = x.to(dev, non_blocking=True)
+        if y.device != dev:
+            y = y.to(dev, non_blocking=True)
+        return x, y
+
+    def _build_step(self):
+        x, y = self._on_device(*self.example)
+        self.model.train()
+        if self.padded:
+            crit = BatchSlicedCrossEntropyLoss(self.smooth_factor)
+        else:
+            crit = FusedSmoothedCrossEntropyLoss(self.smooth_factor)
+        if self.graph:
+            self.step = GraphedTrainStep(self.model, self.opt, x, y, criterion=crit, micro_batch=self.micro_batch,
+                                         ragged=self.padded, meter=self.meter)
+        else:
+            self.step = TrainStep(self.model, self.opt, criterion=crit, micro_batch=self.micro_batch,
+                                  pad_to=self.batch_size if self.padded else None, meter=self.meter)
+
+    def _build_evaluator(self):
+        import importlib
+        evaluate = importlib.import_module(__package__ + ".evaluate")
+        x, _ = self._on_device(*self.example)
+        self.model.eval()
+        self.evaluator = evaluate.Evaluator(self.model, self.num_classes, x, k_max=self.k, smooth_factor=self.smooth_factor,
+                                            graph=self.graph)
+
+    # ---- one epoch's two halves
+    def train_epoch(self, train_batches):
+        """one pass over the train batches and the meter's close; reads nothing back"""
+        self.model.train()
+        for x, y in train_batches:
+            if not self.padded and x.shape[0] != self.batch_size:
+                raise ValueError(f"{type(self.model).__name__} couples the clips of a train batch, so a batch cannot be "
+                                 f"padded: every train batch must have batch_size = {self.batch_size} rows, got "
+                                 f"{x.shape[0]} -- build the loader with drop_last=True")
+            if self.step is None:
+                self._build_step()
+            self.step(*self._on_device(x, y))
+        if self.step is None:
+            raise ValueError("the train source gave no batch")
+        self.meter.close_epoch()
+
+    def validate(self, val_batches):
+        """(val_loss, val_acc): one pass through the evaluator, one host read"""
+        if self.evaluator is None:
+            self._build_evaluator()
+        self.model.eval()
+        self.evaluator.reset()
+        averaged = self.opt.averager.applied() if self.eval_averaged else contextlib.nullcontext()
+        with averaged:
+            for x, y in val_batches:
+                self.evaluator.update(*self._on_device(x, y))
+            r = self.evaluator.result()
+        return r["loss"], r["acc"][self.k]
+
+    # ---- checkpoints
+    def _extra(self):
+        guard, averager = _guard_of(self.opt), getattr(self.opt, "averager", None)
+        return dict(guard=None if guard is None else guard.state_dict(),
+                    averager=None if averager is None else averager.state_dict(),
+                    meter=self.meter.state_dict(), drop_calls=int(getattr(self.model, "_drop_calls", 0)))
+
+    def _save(self, suffix, epoch):
+        import importlib
+        checkpoint = importlib.import_module(__package__ + ".checkpoint")
+        path = f"{self.out_prefix}_{suffix}.pt"
+        b = self.book
+        checkpoint.save_checkpoint(path, self.model, self.opt, self.scheduler, b.train_acc_list, b.train_loss_list,
+                                   b.val_acc_list, b.val_loss_list, epoch, self.lr, extra=self._extra())
+        self.written.append(path)
+
+    def resume(self, path):
+        """go on from a checkpoint this loop wrote; returns the epoch the next run() starts at"""
+        import importlib
+        checkpoint = importlib.import_module(__package__ + ".checkpoint")
+        dev = self._device()
+        _, _, _, lists, start = checkpoint.load_checkpoint(path, self.model, self.opt, self.scheduler, device=dev)
+        extra = checkpoint.read_extra(path, device=dev)
+        guard, averager = _guard_of(self.opt), getattr(self.opt, "averager", None)
+        if guard is not None and extra.get("guard") is not None:
+            guard.load_state_dict(extra["guard"])
+        if averager is not None and extra.get("averager") is not None:
+            averager.load_state_dict(extra["averager"])
+        if extra.get("meter") is not None:
+            self.meter.load_state_dict(extra["meter"])
+        if "drop_calls" in extra and hasattr(self.model, "_drop_calls"):
+            self.model._drop_calls = int(extra["drop_calls"])
+            if self.model._seed_state.is_cuda:           # the device counter a captured step advances by itself
+                _functional().seed_set(self.model._seed_state, self.model._drop_calls, torch.initial_seed(),
+                                       getattr(self.model, "rank_salt", 0))
+        self.book = EpochBook.resumed(lists, self.book.save_interval, self.book.early_stopper)
+        self.start_epoch = int(start)
+        return self.start_epoch
+
+    # ---- the loop
+    def run(self, train_batches, val_batches, epochs, start_epoch=None):
+        """epochs `start_epoch` .. `epochs`, both included (the reference's range(start_epoch, epochs + 1)); returns the
+        book.  Ends early when the early stopper says so"""
+        start = self.start_epoch if start_epoch is None else int(start_epoch)
+        self.written = []
+        for epoch in range(start, int(epochs) + 1):
+            self.train_epoch(train_batches)
+            self.scheduler.step()
+            val_loss, val_acc = self.validate(val_batches)
+            tr = self.meter.history()[-1]
+            suffixes, stop = self.book.record(epoch, tr["loss"], tr["acc"], val_loss, val_acc)
+            if self.out_prefix is not None:
+                for suffix in suffixes:
+                    self._save(suffix, epoch)
+            self.start_epoch = epoch + 1
+            if stop:
+                break
+        return self.book
+
+
+def _plain_lr(v):
+    return float(v.item()) if torch.is_tensor(v) else v
