@@ -72,8 +72,12 @@ extern "C" {
  *         hwgat_bsce_{fwd,bwd}, the smoothed cross-entropy of one slice of a zero-padded batch (additions only);
  *         hwgat_wavg_{set,advance,update,swap}, EMA / equal-weight averages of the weights on the device (additions only);
  *         hwgat_meter_{bytes,fold,close}, the train meters: per-epoch sums, a step log and closed epochs kept on the
- *         device (additions only) */
-#define HWGAT_ABI_VERSION 4006
+ *         device (additions only)
+ *   4007  one record and one entry-point triple for the device optimizers: hwgat_opt_{set,advance,step} with a `kind` and
+ *         a nullable `guard_state` replace hwgat_{optim,sgd,nadam}_{set,advance,step} and
+ *         hwgat_gguard_{adamw,sgd,nadam}_{advance,step}; hwgat_opt_entry (64 bytes) is the only table record, and
+ *         hwgat_gguard_{partial,scale} lose their record-size argument */
+#define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
 /* ---- dropout seeds (round 4).  Every `*_seed` argument below is a SITE seed, a host integer that identifies one dropout
@@ -499,116 +503,96 @@ typedef struct {
 } hwgat_prep_entry;
 int hwgat_weight_prep(const hwgat_prep_entry* table, int n, int total_blocks, int dtype, void* stream);
 
-/* ---- Adam / AdamW for all parameter tensors of a model in one launch (reference: torch.optim.AdamW / Adam as
- * hwgat/utils.py:71-82 builds them and utils.py:93-116 steps them; amsgrad = maximize = False).  Parameters, gradients
- * and both moments are fp32.  Every value that changes between steps lives in DEVICE memory and is read when the kernels
- * run, so the three launches below can be captured in a HIP graph and replayed under a learning-rate schedule.
+/* ---- the optimizers: AdamW / Adam, SGD and NAdam for all parameter tensors of a model in one launch each (reference:
+ * cfg.optimizer_type 'adamw' / 'adam' / 'sgd' / 'nadam' as hwgat/utils.py:71-84 builds them and utils.py:93-116 steps them;
+ * torch.optim.AdamW / Adam with amsgrad = maximize = False, torch.optim.SGD and torch.optim.NAdam with maximize = False).
+ * Parameters, gradients and state are fp32.  Every value that changes between steps lives in DEVICE memory and is read
+ * when the kernels run, so the advance and step launches below can be captured in a HIP graph and replayed under a
+ * learning-rate schedule.  `kind` is one of HWGAT_OPT_ADAMW / HWGAT_OPT_SGD / HWGAT_OPT_NADAM; any other value is refused.
  *
- * table: `n` entries in DEVICE memory, sorted by first_block; entry i owns workgroups [first_block, next entry's
- *   first_block) of hwgat_optim_step, ceil(n_i / HWGAT_OPTIM_CHUNK) of them, workgroup b covering elements
- *   [b * CHUNK, min(n_i, (b + 1) * CHUNK)).  `step` points at the tensor's own step count, one fp32 device word (torch's
- *   state["step"] of a capturable optimizer); `group` selects the hyper-parameter block.  A tensor whose p, g, m and v are
- *   all 16-byte aligned moves in 16-byte vectors, any other (e.g. a gradient that is a view into a flat bucket) element
- *   by element; both give the same bits.
- * hyper: HWGAT_OPTIM_NHYPER fp64 words per group: { lr, beta1, beta2, eps, weight_decay, coupled (0 = AdamW, decoupled
- *   decay; 1 = Adam, decay added to the gradient), 0, 0 }.
- * derived: HWGAT_OPTIM_NDERIVED fp32 words per table entry, scratch that hwgat_optim_advance writes and hwgat_optim_step
- *   reads: the per-tensor scalars of the update rounded from fp64 once (lr wd, wd, 1 - beta1, beta2, 1 - beta2,
- *   lr / (1 - beta1^t), sqrt(1 - beta2^t), eps).
- *
- * hwgat_optim_set:     one thread writes group `group` of `hyper` from the host doubles given as arguments (no copy, no
- *                      host buffer: stream-ordered like hwgat_seed_set).  decoupled != 0: AdamW.
- * hwgat_optim_advance: one thread per entry: *step += 1 (t), then the entry's derived block from its group's hyper block
- *                      and t, in fp64.  A launch of its own: the workgroups of one entry must all see the same t.
- * hwgat_optim_step:    for each element, in fp32 (fused multiply-adds as written, nothing else contracted):
- *                        p = p - (lr wd) p                       AdamW   |   g = g + wd p    Adam
- *                        m = m + (1 - beta1) (g - m)
- *                        v = ((1 - beta2) g) g + beta2 v
- *                        p = p - (lr / (1 - beta1^t)) (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
- *                      total_blocks = the sum of the entries' workgroups.  No atomics, no reductions: bit-reproducible. */
-#define HWGAT_OPTIM_CHUNK 4096
-#define HWGAT_OPTIM_NHYPER 8
-#define HWGAT_OPTIM_NDERIVED 8
-typedef struct {
-    float* p; const float* g; float* m; float* v; float* step;
-    int64_t n;
-    int32_t group, first_block;
-} hwgat_optim_entry;
-int hwgat_optim_set(double* hyper, int group, double lr, double beta1, double beta2, double eps, double weight_decay,
-                    int decoupled, void* stream);
-int hwgat_optim_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived, void* stream);
-int hwgat_optim_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks, void* stream);
-
-/* ---- SGD and NAdam in the same form (reference: cfg.optimizer_type 'sgd' / 'nadam', hwgat/utils.py:73-84; torch.optim.SGD
- * and torch.optim.NAdam with maximize = False).  With hwgat_optim_* above, every optimizer type of the reference has a
- * set / advance / step triple whose launches can be captured in a HIP graph.  Parameters, gradients and state are fp32.
- *
- * table: `n` hwgat_opt_entry records in DEVICE memory, sorted by first_block, workgroups assigned as for hwgat_optim_step
- *   (HWGAT_OPTIM_CHUNK elements each).  s0 / s1 are the tensor's state arrays, w0 / w1 its own scalar device words:
+ * table: `n` hwgat_opt_entry records in DEVICE memory, sorted by first_block; entry i owns workgroups [first_block, next
+ *   entry's first_block) of hwgat_opt_step, ceil(n_i / HWGAT_OPTIM_CHUNK) of them, workgroup b covering elements
+ *   [b * CHUNK, min(n_i, (b + 1) * CHUNK)); `group` selects the hyper-parameter block.  s0 / s1 are the tensor's state
+ *   arrays, w0 / w1 its own scalar device words:
+ *     AdamW  s0 = exp_avg (m), s1 = exp_avg_sq (v), w0 = step count, one fp32 device word (torch's state["step"] of a
+ *            capturable optimizer); w1 = NULL.
  *     SGD    s0 = momentum buffer, w0 = "stepped before" word (0.0f = never, anything else = yes); s1 = w1 = NULL.
  *            s0 = w0 = NULL for a tensor of a group without momentum: nothing but p and g is touched then.
  *     NAdam  s0 = exp_avg, s1 = exp_avg_sq, w0 = step count, w1 = mu_product (torch's state["step"] and
  *            state["mu_product"] of a capturable NAdam); all four required.
- *   A tensor whose p, g and state arrays are all 16-byte aligned moves in 16-byte vectors, any other element by element;
- *   both give the same bits.
+ *   A tensor whose p, g and state arrays are all 16-byte aligned moves in 16-byte vectors, any other (e.g. a gradient that
+ *   is a view into a flat bucket) element by element; both give the same bits.
  * hyper: HWGAT_OPTIM_NHYPER fp64 words per group:
+ *     AdamW  { lr, beta1, beta2, eps, weight_decay, coupled (0 = AdamW, decoupled decay; 1 = Adam, decay added to the
+ *              gradient), 0, 0 }
  *     SGD    { lr, momentum, dampening, weight_decay, nesterov (0 / 1), 0, 0, 0 }
  *     NAdam  { lr, beta1, beta2, eps, weight_decay, coupled (0 = decoupled decay, 1 = decay added to the gradient),
  *              momentum_decay, 0 }
- * derived: HWGAT_OPT_NDERIVED fp32 words per table entry, written by *_advance and read by *_step.
+ * derived: HWGAT_OPT_NDERIVED fp32 words per table entry, scratch that hwgat_opt_advance writes and hwgat_opt_step reads:
+ *   the per-tensor scalars of the update rounded from fp64 once.
+ * guard_state: NULL, or the state block of a gradient guard (below).  With one, advance and step return at once when its
+ *   `skip` word is set, so no step count, "stepped" word, mu_product, parameter or state element is written.  It is the
+ *   only pointer of these entry points that may be NULL; the kernels launched without one take no such argument.
  *
- * hwgat_sgd_set / hwgat_nadam_set: one thread writes group `group` of `hyper` from the host doubles given as arguments.
- * hwgat_sgd_advance:   one thread per entry: when the group's momentum != 0 and the entry has a buffer, first = (*w0 == 0),
- *                      then *w0 = 1; the entry's fp32 scalars (lr, weight_decay, momentum, 1 - dampening, flags) rounded
- *                      from fp64 once.
- * hwgat_sgd_step:      for each element, in fp32 (fused multiply-adds as written, nothing else contracted):
- *                        g' = g + wd p
- *                        with a buffer:   buf = first ? g' : (1 - dampening) g' + momentum buf   (a select: the old
- *                                         contents of a never-stepped buffer are not used, as torch clones the gradient)
- *                                         d = nesterov ? g' + momentum buf : buf
- *                        without:         d = g'
- *                        p = p - lr d
- *                      12 bytes per element without a buffer, 20 with one.
- * hwgat_nadam_advance: one thread per entry, in fp64: t = *w0 + 1, *w0 = t; mu = beta1 (1 - 0.5 * 0.96^(t momentum_decay)),
- *                      mu' the same at t + 1; *w1 = (float)(*w1 * mu); then the entry's fp32 scalars, among them
- *                      1 - beta2^t, cg = lr (1 - mu) / (1 - *w1) and cm = lr mu' / (1 - *w1 mu').
- * hwgat_nadam_step:    for each element, in fp32:
- *                        p = p - (lr wd) p                       decoupled   |   g = g + wd p    coupled
- *                        m = m + (1 - beta1) (g - m)
- *                        v = ((1 - beta2) g) g + beta2 v
- *                        denom = sqrt(v / (1 - beta2^t)) + eps
- *                        p = p - cg (g / denom);   p = p - cm (m / denom)
- *                      28 bytes per element.
- * total_blocks = the sum of the entries' workgroups.  No atomics, no reductions: bit-reproducible. */
+ * hwgat_opt_set:     one thread writes group `group` of `hyper` from the HWGAT_OPTIM_NHYPER HOST doubles at `values`, in the
+ *                    layout of `kind` above.  They travel as a kernel argument (no copy, no copy node; stream-ordered like
+ *                    hwgat_seed_set): `values` is not read after the call returns.
+ * hwgat_opt_advance: one thread per entry, in fp64, the entry's derived block from its group's hyper block.  A launch of
+ *                    its own: the workgroups of one entry must all see the same t.
+ *                      AdamW  *w0 += 1 (t); lr wd, wd, 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^t), sqrt(1 - beta2^t), eps.
+ *                      SGD    when the group's momentum != 0 and the entry has a buffer, first = (*w0 == 0), then *w0 = 1;
+ *                             lr, weight_decay, momentum, 1 - dampening, flags.
+ *                      NAdam  t = *w0 + 1, *w0 = t; mu = beta1 (1 - 0.5 * 0.96^(t momentum_decay)), mu' the same at t + 1;
+ *                             *w1 = (float)(*w1 * mu); then the entry's fp32 scalars, among them 1 - beta2^t,
+ *                             cg = lr (1 - mu) / (1 - *w1) and cm = lr mu' / (1 - *w1 mu').
+ * hwgat_opt_step:    for each element, in fp32 (fused multiply-adds as written, nothing else contracted):
+ *                      AdamW  p = p - (lr wd) p                       AdamW   |   g = g + wd p    Adam
+ *                             m = m + (1 - beta1) (g - m)
+ *                             v = ((1 - beta2) g) g + beta2 v
+ *                             p = p - (lr / (1 - beta1^t)) (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+ *                      SGD    g' = g + wd p
+ *                             with a buffer:   buf = first ? g' : (1 - dampening) g' + momentum buf   (a select: the old
+ *                                              contents of a never-stepped buffer are not used, as torch clones the gradient)
+ *                                              d = nesterov ? g' + momentum buf : buf
+ *                             without:         d = g'
+ *                             p = p - lr d
+ *                             12 bytes per element without a buffer, 20 with one.
+ *                      NAdam  p = p - (lr wd) p                       decoupled   |   g = g + wd p    coupled
+ *                             m = m + (1 - beta1) (g - m)
+ *                             v = ((1 - beta2) g) g + beta2 v
+ *                             denom = sqrt(v / (1 - beta2^t)) + eps
+ *                             p = p - cg (g / denom);   p = p - cm (m / denom)
+ *                             28 bytes per element, as for AdamW.
+ *                    total_blocks = the sum of the entries' workgroups.  No atomics, no reductions: bit-reproducible. */
+#define HWGAT_OPTIM_CHUNK 4096
+#define HWGAT_OPTIM_NHYPER 8
 #define HWGAT_OPT_NDERIVED 16
+enum { HWGAT_OPT_ADAMW = 0, HWGAT_OPT_SGD = 1, HWGAT_OPT_NADAM = 2 };
 typedef struct {
     float* p; const float* g; float* s0; float* s1; float* w0; float* w1;
     int64_t n;
     int32_t group, first_block;
 } hwgat_opt_entry;
-int hwgat_sgd_set(double* hyper, int group, double lr, double momentum, double dampening, double weight_decay,
-                  int nesterov, void* stream);
-int hwgat_sgd_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream);
-int hwgat_sgd_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream);
-int hwgat_nadam_set(double* hyper, int group, double lr, double beta1, double beta2, double eps, double weight_decay,
-                    double momentum_decay, int decoupled, void* stream);
-int hwgat_nadam_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived, void* stream);
-int hwgat_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks, void* stream);
+int hwgat_opt_set(double* hyper, int group, int kind, const double* values, void* stream);
+int hwgat_opt_advance(int kind, const hwgat_opt_entry* table, int n, const double* hyper, float* derived,
+                      const double* guard_state, void* stream);
+int hwgat_opt_step(int kind, const hwgat_opt_entry* table, int n, const float* derived, int total_blocks,
+                   const double* guard_state, void* stream);
 
 /* ---- gradient guard: clip all gradients of a model by their global norm (torch.nn.utils.clip_grad_norm_, norm_type 2 or
  * inf) and turn a step whose gradients hold a NaN or an Inf into a no-op, with every result left in DEVICE memory: nothing
  * is read back to the host, so the launches below can be captured in a HIP graph together with the optimizer step.
  *
- * table / entry_bytes: the optimizer's own table, `n` records of hwgat_optim_entry (entry_bytes = 56) or hwgat_opt_entry
- *   (entry_bytes = 64) in DEVICE memory; only `g`, `n` and `first_block` of a record are used.  Workgroups are assigned as
- *   for the step kernels: one workgroup of 256 threads per HWGAT_OPTIM_CHUNK elements of one tensor.
+ * table: the optimizer's own table, `n` hwgat_opt_entry records in DEVICE memory; only `g`, `n` and `first_block` of a
+ *   record are used.  Workgroups are assigned as for hwgat_opt_step: one workgroup of 256 threads per HWGAT_OPTIM_CHUNK
+ *   elements of one tensor.
  * state: HWGAT_GGUARD_NSTATE fp64 words in DEVICE memory, at the HWGAT_GGUARD_* slots below.  The three config words are
  *   written by hwgat_gguard_set, the others by hwgat_gguard_finish; the caller zeroes the block once.
  * workspace: 2 * total_blocks fp64 words in DEVICE memory: per workgroup { partial, flags (1 = saw a NaN, 2 = saw an Inf) }.
  *
  * hwgat_gguard_set:     one thread writes max_norm (>= 0, +Inf = measure only), norm_type (2 or +Inf) and the mode
  *                       (skip != 0: a step with a non-finite gradient is skipped; 0: it propagates, as in torch) from the
- *                       host values given as arguments; stream-ordered like hwgat_optim_set.
+ *                       host values given as arguments; stream-ordered like hwgat_opt_set.
  * hwgat_gguard_partial: per workgroup the sum of g^2 in fp64 (norm_type 2) or max |g| (norm_type Inf) over its chunk:
  *                       per thread in a fixed element order, then in-wave, then across the four waves through LDS, in a
  *                       fixed order; one 16-byte store per workgroup, no atomics.  A 16-byte-aligned tensor moves in
@@ -621,9 +605,7 @@ int hwgat_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, 
  *                         steps += 1;  clipped += (clip_coef < 1 && !skip);  skipped += skip.
  * hwgat_gguard_scale:   g = g * (float)clip_coef in place for every element of every entry (also when clip_coef == 1: the
  *                       bits do not change); writes nothing when `skip` is set.  8 bytes per element.
- * hwgat_gguard_{adamw,sgd,nadam}_{advance,step}: hwgat_optim_* / hwgat_sgd_* / hwgat_nadam_* advance and step with the
- *                       guard's state block as one more argument: they return at once when `skip` is set, so no step count,
- *                       "stepped" word, mu_product, parameter or state element is written. */
+ * hwgat_opt_advance / hwgat_opt_step take the state block as `guard_state` and do nothing when `skip` is set. */
 #define HWGAT_GGUARD_NSTATE 16
 #define HWGAT_GGUARD_MAX_NORM 0
 #define HWGAT_GGUARD_NORM_TYPE 1
@@ -636,36 +618,24 @@ int hwgat_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, 
 #define HWGAT_GGUARD_CLIPPED 8
 #define HWGAT_GGUARD_SKIPPED 9
 int hwgat_gguard_set(double* state, double max_norm, double norm_type, int skip, void* stream);
-int hwgat_gguard_partial(const void* table, int n, int entry_bytes, const double* state, double* workspace,
-                         int total_blocks, void* stream);
+int hwgat_gguard_partial(const hwgat_opt_entry* table, int n, const double* state, double* workspace, int total_blocks,
+                         void* stream);
 int hwgat_gguard_finish(const double* workspace, int total_blocks, double* state, void* stream);
-int hwgat_gguard_scale(const void* table, int n, int entry_bytes, const double* state, int total_blocks, void* stream);
-int hwgat_gguard_adamw_advance(const hwgat_optim_entry* table, int n, const double* hyper, float* derived,
-                               const double* guard_state, void* stream);
-int hwgat_gguard_adamw_step(const hwgat_optim_entry* table, int n, const float* derived, int total_blocks,
-                            const double* guard_state, void* stream);
-int hwgat_gguard_sgd_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived,
-                             const double* guard_state, void* stream);
-int hwgat_gguard_sgd_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks,
-                          const double* guard_state, void* stream);
-int hwgat_gguard_nadam_advance(const hwgat_opt_entry* table, int n, const double* hyper, float* derived,
-                               const double* guard_state, void* stream);
-int hwgat_gguard_nadam_step(const hwgat_opt_entry* table, int n, const float* derived, int total_blocks,
-                            const double* guard_state, void* stream);
+int hwgat_gguard_scale(const hwgat_opt_entry* table, int n, const double* state, int total_blocks, void* stream);
 
 /* ---- weight averaging: an exponential moving average (EMA) or the equal-weight running mean (SWA) of the weights, as
  * torch.optim.swa_utils.AveragedModel keeps it, with every number left in DEVICE memory, so the launches below can be
  * captured in a HIP graph behind the optimizer step; and the in-place exchange of the averages with the live weights.
  *
  * table: `n` hwgat_wavg_entry records (HWGAT_WAVG_ENTRY_BYTES each) in DEVICE memory, sorted by first_block, workgroups
- *   assigned as for hwgat_optim_step: one workgroup of 256 threads per HWGAT_OPTIM_CHUNK elements of one tensor.  avg and
+ *   assigned as for hwgat_opt_step: one workgroup of 256 threads per HWGAT_OPTIM_CHUNK elements of one tensor.  avg and
  *   src are fp32, 4-byte aligned and must not overlap.  A tensor whose avg and src are both 16-byte aligned moves in 16-byte
  *   vectors, any other element by element; both give the same bits.
  * state: HWGAT_WAVG_NSTATE fp64 words in DEVICE memory, at the HWGAT_WAVG_* slots below.  The five config words are written
  *   by hwgat_wavg_set, the four result words by hwgat_wavg_advance; the caller zeroes the block once.
  *
  * hwgat_wavg_set:     one thread writes mode (0 = EMA, 1 = equal weight), decay (in [0, 1)), warmup (0 / 1), start (>= 0)
- *                     and every (>= 1) from the host values given as arguments; stream-ordered like hwgat_optim_set.
+ *                     and every (>= 1) from the host values given as arguments; stream-ordered like hwgat_opt_set.
  * hwgat_wavg_advance: one thread.  guard_state (may be NULL) is a gradient guard's state block: when its `skip` word is
  *                     set, active = 0, coef = 0 and no counter moves.  Otherwise steps_seen += 1; the update is due when
  *                     steps_seen > start and (steps_seen - start) % every == 0.  Not due: active = 0.  Due: active = 1,

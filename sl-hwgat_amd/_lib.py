@@ -129,25 +129,13 @@ _SIGS = {
     "hwgat_bsce_bwd": [_P, _P, _P, _L, _P, _P, _P, _L, _I, _F, _P],
     "hwgat_eval_acc_bytes": [_I, _I, _L],
     "hwgat_eval_accumulate": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _L, _P],
-    "hwgat_optim_set": [_P, _I, _D, _D, _D, _D, _D, _I, _P],
-    "hwgat_optim_advance": [_P, _I, _P, _P, _P],
-    "hwgat_optim_step": [_P, _I, _P, _I, _P],
-    "hwgat_sgd_set": [_P, _I, _D, _D, _D, _D, _I, _P],
-    "hwgat_sgd_advance": [_P, _I, _P, _P, _P],
-    "hwgat_sgd_step": [_P, _I, _P, _I, _P],
-    "hwgat_nadam_set": [_P, _I, _D, _D, _D, _D, _D, _D, _I, _P],
-    "hwgat_nadam_advance": [_P, _I, _P, _P, _P],
-    "hwgat_nadam_step": [_P, _I, _P, _I, _P],
+    "hwgat_opt_set": [_P, _I, _I, _P, _P],
+    "hwgat_opt_advance": [_I, _P, _I, _P, _P, _P, _P],
+    "hwgat_opt_step": [_I, _P, _I, _P, _I, _P, _P],
     "hwgat_gguard_set": [_P, _D, _D, _I, _P],
-    "hwgat_gguard_partial": [_P, _I, _I, _P, _P, _I, _P],
+    "hwgat_gguard_partial": [_P, _I, _P, _P, _I, _P],
     "hwgat_gguard_finish": [_P, _I, _P, _P],
-    "hwgat_gguard_scale": [_P, _I, _I, _P, _I, _P],
-    "hwgat_gguard_adamw_advance": [_P, _I, _P, _P, _P, _P],
-    "hwgat_gguard_adamw_step": [_P, _I, _P, _I, _P, _P],
-    "hwgat_gguard_sgd_advance": [_P, _I, _P, _P, _P, _P],
-    "hwgat_gguard_sgd_step": [_P, _I, _P, _I, _P, _P],
-    "hwgat_gguard_nadam_advance": [_P, _I, _P, _P, _P, _P],
-    "hwgat_gguard_nadam_step": [_P, _I, _P, _I, _P, _P],
+    "hwgat_gguard_scale": [_P, _I, _P, _I, _P],
     "hwgat_wavg_set": [_P, _I, _D, _I, _L, _L, _P],
     "hwgat_wavg_advance": [_P, _P, _P],
     "hwgat_wavg_update": [_P, _I, _P, _I, _P],

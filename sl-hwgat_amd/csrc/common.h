@@ -54,15 +54,15 @@ int hwgat_tn_det_reduce(const float* ws, float* out, int cap, int64_t stride, in
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-// the guarded optimizer kernels (optim.hip, optim_family.hip) end at once when the gradient guard's finish kernel
+// the guarded optimizer kernels (optim.hip) end at once when the gradient guard's finish kernel
 // (grad_guard.hip) has set the `skip` word of its state block; uniform, one scalar load
 __device__ __forceinline__ bool gguard_skips(const double* __restrict__ guard_state) {
     return guard_state[HWGAT_GGUARD_SKIP] != 0.0;
 }
 
-// Table-driven launches (hwgat_optim_entry, hwgat_opt_entry: any record with a `first_block`): the entry of this workgroup
+// Table-driven launches (hwgat_opt_entry, hwgat_wavg_entry: any record with a `first_block`): the entry of this workgroup
 // is the last one whose first_block <= blockIdx.x.  Uniform binary search (a model has ~200 entries; the loads are scalar).
-// optim_family.hip and grad_guard.hip use it; optim_step_k (optim.hip) keeps the loop it was written with
+// optim.hip, grad_guard.hip and weight_avg.hip use it
 template <class E>
 __device__ __forceinline__ int entry_of_block(const E* __restrict__ table, int n) {
     int lo = 0, hi = n - 1;

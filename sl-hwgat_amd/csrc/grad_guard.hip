@@ -1,8 +1,8 @@
 // Gradient guard for gfx950 (wave64): the global norm of ALL gradients of a model, torch's clip coefficient from it, a
 // "saw a NaN or an Inf" verdict and three counters, computed and kept on the device, and the in-place scaling of the
 // gradients by that coefficient.  Table-driven like optim.hip: the launches read the optimizer's own table (only `g`, `n`
-// and `first_block` of a record; the kernels are templates on the record type) and map workgroups to tensors as its step
-// kernel does, so a train step captured in a HIP graph can hold them between its backward and its optimizer launches.
+// and `first_block` of a record) and map workgroups to tensors as its step kernel does, so a train step captured in a HIP
+// graph can hold them between its backward and its optimizer launches.
 //
 // Reference: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type = 2 | inf):
 //     total_norm = || (||g_1||, ..., ||g_k||) ||        coef = clamp(max_norm / (total_norm + 1e-6), max = 1)
@@ -72,12 +72,11 @@ __device__ __forceinline__ void fold_block(bool maxn, double& acc, int& flags) {
     }
 }
 
-template <class E>
-__global__ __launch_bounds__(THREADS) void gguard_partial_k(const E* __restrict__ table, int n,
+__global__ __launch_bounds__(THREADS) void gguard_partial_k(const hwgat_opt_entry* __restrict__ table, int n,
                                                             const double* __restrict__ state,
                                                             double* __restrict__ workspace) {
     const bool maxn = state[HWGAT_GGUARD_NORM_TYPE] != 2.0;
-    const E en = table[entry_of_block(table, n)];
+    const hwgat_opt_entry en = table[entry_of_block(table, n)];
     const int64_t c0 = (int64_t)((int)blockIdx.x - en.first_block) * HWGAT_OPTIM_CHUNK;
     // c0 < n with a well-formed table; an empty chunk still writes its (neutral) partial, which the finish kernel reads
     const int count = c0 >= en.n ? 0 : (int)((en.n - c0 < HWGAT_OPTIM_CHUNK) ? en.n - c0 : HWGAT_OPTIM_CHUNK);
@@ -129,12 +128,11 @@ __global__ __launch_bounds__(THREADS) void gguard_finish_k(const double* __restr
     if (skip) state[HWGAT_GGUARD_SKIPPED] += 1.0;
 }
 
-template <class E>
-__global__ __launch_bounds__(THREADS) void gguard_scale_k(const E* __restrict__ table, int n,
+__global__ __launch_bounds__(THREADS) void gguard_scale_k(const hwgat_opt_entry* __restrict__ table, int n,
                                                           const double* __restrict__ state) {
     if (gguard_skips(state)) return;                          // the offending gradients stay as they are
     const float coef = (float)state[HWGAT_GGUARD_CLIP_COEF];
-    const E en = table[entry_of_block(table, n)];
+    const hwgat_opt_entry en = table[entry_of_block(table, n)];
     const int64_t c0 = (int64_t)((int)blockIdx.x - en.first_block) * HWGAT_OPTIM_CHUNK;
     if (c0 >= en.n) return;                                   // cannot happen with a well-formed table
     const int count = (int)((en.n - c0 < HWGAT_OPTIM_CHUNK) ? en.n - c0 : HWGAT_OPTIM_CHUNK);
@@ -153,14 +151,6 @@ __global__ __launch_bounds__(THREADS) void gguard_scale_k(const E* __restrict__ 
     for (int i = done + threadIdx.x; i < count; i += THREADS) g[i] = g[i] * coef;
 }
 
-// the two record types the tables come in
-template <class F56, class F64>
-int by_entry(int entry_bytes, const F56& f56, const F64& f64) {
-    if (entry_bytes == (int)sizeof(hwgat_optim_entry)) return f56();
-    if (entry_bytes == (int)sizeof(hwgat_opt_entry)) return f64();
-    return HWGAT_EINVAL;
-}
-
 }  // namespace
 
 extern "C" int hwgat_gguard_set(double* state, double max_norm, double norm_type, int skip, void* stream) {
@@ -169,20 +159,11 @@ extern "C" int hwgat_gguard_set(double* state, double max_norm, double norm_type
     HWGAT_LAUNCH_CHECK();
 }
 
-extern "C" int hwgat_gguard_partial(const void* table, int n, int entry_bytes, const double* state, double* workspace,
+extern "C" int hwgat_gguard_partial(const hwgat_opt_entry* table, int n, const double* state, double* workspace,
                                     int total_blocks, void* stream) {
     if (!table || !state || !workspace || (((uintptr_t)workspace) & 15) || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;
-    const hipStream_t st = (hipStream_t)stream;
-    return by_entry(
-        entry_bytes,
-        [&]() -> int {
-            gguard_partial_k<<<total_blocks, THREADS, 0, st>>>((const hwgat_optim_entry*)table, n, state, workspace);
-            HWGAT_LAUNCH_CHECK();
-        },
-        [&]() -> int {
-            gguard_partial_k<<<total_blocks, THREADS, 0, st>>>((const hwgat_opt_entry*)table, n, state, workspace);
-            HWGAT_LAUNCH_CHECK();
-        });
+    gguard_partial_k<<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, state, workspace);
+    HWGAT_LAUNCH_CHECK();
 }
 
 extern "C" int hwgat_gguard_finish(const double* workspace, int total_blocks, double* state, void* stream) {
@@ -191,18 +172,8 @@ extern "C" int hwgat_gguard_finish(const double* workspace, int total_blocks, do
     HWGAT_LAUNCH_CHECK();
 }
 
-extern "C" int hwgat_gguard_scale(const void* table, int n, int entry_bytes, const double* state, int total_blocks,
-                                  void* stream) {
+extern "C" int hwgat_gguard_scale(const hwgat_opt_entry* table, int n, const double* state, int total_blocks, void* stream) {
     if (!table || !state || n <= 0 || total_blocks <= 0) return HWGAT_EINVAL;
-    const hipStream_t st = (hipStream_t)stream;
-    return by_entry(
-        entry_bytes,
-        [&]() -> int {
-            gguard_scale_k<<<total_blocks, THREADS, 0, st>>>((const hwgat_optim_entry*)table, n, state);
-            HWGAT_LAUNCH_CHECK();
-        },
-        [&]() -> int {
-            gguard_scale_k<<<total_blocks, THREADS, 0, st>>>((const hwgat_opt_entry*)table, n, state);
-            HWGAT_LAUNCH_CHECK();
-        });
+    gguard_scale_k<<<total_blocks, THREADS, 0, (hipStream_t)stream>>>(table, n, state);
+    HWGAT_LAUNCH_CHECK();
 }

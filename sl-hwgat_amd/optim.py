@@ -1,7 +1,7 @@
 """The reference's optimizer types on HIP kernels (reference: hwgat/utils.py:73-84 builds `Class(model.parameters(),
 lr=cfg.lr)` for cfg.optimizer_type 'adamw' / 'adam' / 'nadam' / 'sgd', utils.py:93-116 steps it): DeviceAdamW (AdamW and
-Adam, csrc/optim.hip), DeviceSGD and DeviceNAdam (csrc/optim_family.hip).  One launch updates every parameter tensor of
-the model from a table in device memory, and every hyper-parameter is a device word the kernels read when they run, so
+Adam), DeviceSGD and DeviceNAdam, all on csrc/optim.hip.  One launch updates every parameter tensor of the model from a
+table of one record type in device memory, and every hyper-parameter is a device word the kernels read when they run, so
 `train.GraphedTrainStep` captures any of these optimizers' step inside its graph: a replay is the whole train step, under
 any torch LR scheduler.
 
@@ -23,6 +23,7 @@ the optimizer's own launches in every `step()` and in every replay, a step the g
 `with avg.applied(): ...` exchanges averages and weights in place, so every captured graph stays valid.
 """
 import contextlib
+import ctypes
 import math
 import struct
 
@@ -32,14 +33,11 @@ from ._lib import call, ptr, stream
 
 CHUNK = 4096            # HWGAT_OPTIM_CHUNK: elements per workgroup of a step kernel
 NHYPER = 8              # HWGAT_OPTIM_NHYPER: fp64 words per group
-NDERIVED = 8            # HWGAT_OPTIM_NDERIVED: fp32 words per table entry of hwgat_optim_*
-# hwgat_optim_entry: p, g, m, v, step (pointers), n (int64), group, first_block (int32)
-ENTRY = struct.Struct("<5QqIi")
-ENTRY_BYTES = ENTRY.size
-FAMILY_NDERIVED = 16    # HWGAT_OPT_NDERIVED: fp32 words per table entry of hwgat_sgd_* / hwgat_nadam_*
+NDERIVED = 16           # HWGAT_OPT_NDERIVED: fp32 words per table entry
 # hwgat_opt_entry: p, g, s0, s1, w0, w1 (pointers), n (int64), group, first_block (int32)
-FAMILY_ENTRY = struct.Struct("<6QqIi")
-FAMILY_ENTRY_BYTES = FAMILY_ENTRY.size
+ENTRY = struct.Struct("<6QqIi")
+ENTRY_BYTES = ENTRY.size
+KIND_ADAMW, KIND_SGD, KIND_NADAM = range(3)     # HWGAT_OPT_ADAMW / _SGD / _NADAM
 
 
 GUARD_NSTATE = 16       # HWGAT_GGUARD_NSTATE: fp64 words of a guard's state block, at the HWGAT_GGUARD_* slots:
@@ -54,40 +52,30 @@ WAVG_ENTRY_BYTES = WAVG_ENTRY.size
 _WAVG_COUNTERS = ("steps_seen", "n_averaged")
 
 
-def _pack_table(records, entry, chunk):
+def build_table(records, chunk=CHUNK):
+    """records: (p, g, s0, s1, w0, w1 addresses -- 0 for an unused one --, n, group) per tensor that has a gradient, n > 0.
+    Returns (the packed hwgat_opt_entry array as bytes, [first_block per entry], total_blocks): entry i owns
+    ceil(n_i / chunk) workgroups from first_block_i on."""
     blob, first, total = bytearray(), [], 0
     for rec in records:
         n = rec[-2]
         if n <= 0:
             raise ValueError("an empty tensor has no table entry")
         first.append(total)
-        blob += entry.pack(*rec, total)
+        blob += ENTRY.pack(*rec, total)
         total += (n + chunk - 1) // chunk
     if total >= 2 ** 31:
         raise ValueError("more workgroups than one launch holds")
     return bytes(blob), first, total
 
 
-def build_table(records, chunk=CHUNK):
-    """records: (p, g, m, v, step addresses, n, group) per tensor that has a gradient, n > 0.  Returns (the packed
-    hwgat_optim_entry array as bytes, [first_block per entry], total_blocks): entry i owns ceil(n_i / chunk) workgroups
-    from first_block_i on."""
-    return _pack_table(records, ENTRY, chunk)
-
-
-def build_family_table(records, chunk=CHUNK):
-    """the same for hwgat_opt_entry: records are (p, g, s0, s1, w0, w1 addresses -- 0 for an unused one --, n, group)"""
-    return _pack_table(records, FAMILY_ENTRY, chunk)
-
-
 class _Table:
     """one device table + its derived block; `records` is what the device holds (or, while `pending`, will hold).
     `guard_ws`: a gradient guard's workspace for this table, two fp64 words per workgroup"""
 
-    def __init__(self, capacity, device, entry_bytes=ENTRY_BYTES, nderived=NDERIVED):
+    def __init__(self, capacity, device, nderived=NDERIVED):
         self.capacity = capacity
-        self.entry_bytes = entry_bytes
-        self.buf = torch.zeros(max(1, capacity) * entry_bytes, dtype=torch.uint8, device=device)
+        self.buf = torch.zeros(max(1, capacity) * ENTRY_BYTES, dtype=torch.uint8, device=device)
         self.derived = torch.zeros(max(1, capacity) * nderived, dtype=torch.float32, device=device)
         self.records, self.n, self.total, self.pending = None, 0, 0, None
         self.guard_ws = None
@@ -177,9 +165,9 @@ class GradGuard:
     def _measure_and_scale(self, table):
         """partial, finish, scale over `table` (a filled _Table with its workspace reserved)"""
         st, s = ptr(self._state), stream()
-        call("hwgat_gguard_partial", ptr(table.buf), table.n, table.entry_bytes, st, ptr(table.guard_ws), table.total, s)
+        call("hwgat_gguard_partial", ptr(table.buf), table.n, st, ptr(table.guard_ws), table.total, s)
         call("hwgat_gguard_finish", ptr(table.guard_ws), table.total, st, s)
-        call("hwgat_gguard_scale", ptr(table.buf), table.n, table.entry_bytes, st, table.total, s)
+        call("hwgat_gguard_scale", ptr(table.buf), table.n, st, table.total, s)
 
     # ---- readouts
     @property
@@ -261,7 +249,7 @@ def clip_grad_norm_(parameters, guard):
     if key != held:
         if table is None or table.capacity < len(grads):
             table = _Table(len(grads), grads[0].device, nderived=0)
-        blob, _, table.total = build_table([(0, a, 0, 0, 0, n, 0) for a, n in key])
+        blob, _, table.total = build_table([(0, a, 0, 0, 0, 0, n, 0) for a, n in key])
         table.n = len(grads)
         table.upload(blob)
         table.reserve_guard_ws(table.total)
@@ -546,9 +534,9 @@ class WeightAverage:
 class DeviceOptimizer(torch.optim.Optimizer):
     """What the device optimizers share: the fp32 / one-device checks, the fp64 hyper-parameter block with its host
     mirror (`push_hyper`), the device table keyed by the (parameter, gradient) addresses, `begin_capture` / `end_capture`,
-    `load_state_dict` into the live tensors, and `snapshot_state` / `restore_state`.  A subclass names its three entry
-    points and its record, says which tensors a parameter's state consists of, and turns a param group into the values
-    its `set` entry point takes.
+    `load_state_dict` into the live tensors, and `snapshot_state` / `restore_state`.  A subclass names its `kind` of the
+    three entry points (hwgat_opt_set / hwgat_opt_advance / hwgat_opt_step), says which tensors a parameter's state
+    consists of and where they go in a table record, and turns a param group into the eight words of its hyper block.
 
     `step()`: pushes the param-group values that differ from what the device holds (one tiny `set` launch per changed
     group), revalidates the table against the current addresses -- a tuple compare; rebuilt and uploaded only on change --
@@ -563,8 +551,8 @@ class DeviceOptimizer(torch.optim.Optimizer):
 
     `guard`: a `GradGuard` or None (the default).  It is an attribute of the optimizer, not a param-group key and not part
     of `state[p]`: `state_dict()` is the torch class's with or without one.  With a guard, `step()` issues the guard's
-    partial, finish and scale launches over the same table and then the guarded `advance` and `step` entry points, which
-    do nothing when the guard decided to skip; without one it issues exactly `advance` and `step`.
+    partial, finish and scale launches over the same table and hands `advance` and `step` the guard's state block, which
+    then do nothing when the guard decided to skip; without one it issues exactly `advance` and `step`.
 
     `averager`: a `WeightAverage` or None (the default), an attribute like `guard` and as little a part of `state_dict()`.
     With one, `step()` issues the averager's `advance` and `update` launches after its own (handing them the guard's state
@@ -572,10 +560,7 @@ class DeviceOptimizer(torch.optim.Optimizer):
     `snapshot_state` / `restore_state` cover its shadows and result words; `step()` raises while the averaged weights are
     swapped in.  Without one the launches are exactly those above."""
 
-    _SET = _ADVANCE = _STEP = None       # entry points
-    _GUARDED_ADVANCE = _GUARDED_STEP = None   # advance and step that take a GradGuard's state block
-    _PACK = staticmethod(build_table)
-    _ENTRY_BYTES, _NDERIVED = ENTRY_BYTES, NDERIVED
+    _KIND = None                         # the `kind` argument of the entry points
     _STATE_KEYS = ()                     # state[p], in torch's order
     _SCALAR_KEYS = ()                    # those of them that are one fp32 word
     _PRIVATE_KEYS = ()                   # per-tensor device words that are not part of state[p] / state_dict()
@@ -622,8 +607,14 @@ class DeviceOptimizer(torch.optim.Optimizer):
         return self._dev
 
     # ---- hyper-parameters
-    def _set_args(self, vals):
-        """the arguments of the `set` entry point between `group` and `stream`, from a `_group_values` tuple"""
+    @staticmethod
+    def _hyper_words(vals):
+        """the NHYPER doubles of a group's device block (the header's layout for this kind), from a `_group_values` tuple"""
+        raise NotImplementedError
+
+    @staticmethod
+    def _decode_hyper(row):
+        """a group's values as `device_hyper()` reports them, from its NHYPER words"""
         raise NotImplementedError
 
     def push_hyper(self):
@@ -644,11 +635,13 @@ class DeviceOptimizer(torch.optim.Optimizer):
             if vals != self._held[i]:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError(f"{self._name}: a hyper-parameter changed inside a capture; push_hyper() before it")
-                call(self._SET, ptr(self._hyper), i, *self._set_args(vals), stream())
+                words = (ctypes.c_double * NHYPER)(*self._hyper_words(vals))
+                call("hwgat_opt_set", ptr(self._hyper), i, self._KIND, words, stream())
                 self._held[i] = vals
 
-    def _hyper_rows(self):
-        return self._hyper.cpu().view(-1, NHYPER).tolist()[:len(self.param_groups)]
+    def device_hyper(self):
+        """what the device block holds, read back: per group the values of `_decode_hyper`"""
+        return [self._decode_hyper(r) for r in self._hyper.cpu().view(-1, NHYPER).tolist()[:len(self.param_groups)]]
 
     # ---- state and table
     def _wants_state(self, group):
@@ -712,15 +705,12 @@ class DeviceOptimizer(torch.optim.Optimizer):
     def _address_key(self):
         return tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in self._params())
 
-    def _new_table(self, capacity, device):
-        return _Table(capacity, device, self._ENTRY_BYTES, self._NDERIVED)
-
     def _fill(self, table, defer):
         recs = self.table_records(create=not defer)
         table.records = recs
         table.n = len(recs)
         if recs:
-            blob, _, table.total = self._PACK(recs)
+            blob, _, table.total = build_table(recs)
             if defer:
                 table.pending = blob
             else:
@@ -729,7 +719,7 @@ class DeviceOptimizer(torch.optim.Optimizer):
     def begin_capture(self):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("begin_capture() goes before the capture")
-        self._capture = self._new_table(len(self._params()), self._device())
+        self._capture = _Table(len(self._params()), self._device())
         if self.guard is not None:           # as many partials as the table can have workgroups at the most
             self._capture.reserve_guard_ws(sum(-(-p.numel() // CHUNK) for p in self._params()))
 
@@ -763,21 +753,19 @@ class DeviceOptimizer(torch.optim.Optimizer):
         else:
             key = self._address_key()
             if self._table is None or self._table.capacity < len(self._params()):
-                self._table, self._key = self._new_table(len(self._params()), dev), None
+                self._table, self._key = _Table(len(self._params()), dev), None
             table = self._table
             if key != self._key:
                 self._fill(table, defer=False)
                 self._key = key
-        if table.n and self.guard is None:
-            call(self._ADVANCE, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), stream())
-            call(self._STEP, ptr(table.buf), table.n, ptr(table.derived), table.total, stream())
-        elif table.n:
-            guard = self.guard
-            table.reserve_guard_ws(table.total)
-            guard._measure_and_scale(table)
-            gs = ptr(guard._state)
-            call(self._GUARDED_ADVANCE, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), gs, stream())
-            call(self._GUARDED_STEP, ptr(table.buf), table.n, ptr(table.derived), table.total, gs, stream())
+        if table.n:
+            gs = None
+            if self.guard is not None:
+                table.reserve_guard_ws(table.total)
+                self.guard._measure_and_scale(table)
+                gs = ptr(self.guard._state)
+            call("hwgat_opt_advance", self._KIND, ptr(table.buf), table.n, ptr(self._hyper), ptr(table.derived), gs, stream())
+            call("hwgat_opt_step", self._KIND, ptr(table.buf), table.n, ptr(table.derived), table.total, gs, stream())
         if table.n and self.averager is not None:            # after the update, and only of a step the guard let happen
             self.averager._issue(self.guard)
         return loss
@@ -859,11 +847,10 @@ class DeviceOptimizer(torch.optim.Optimizer):
 
 class DeviceAdamW(DeviceOptimizer):
     """torch.optim.AdamW (decoupled_weight_decay=True) or Adam (False) with amsgrad = maximize = False on fp32
-    parameters, on hwgat_optim_set / hwgat_optim_advance / hwgat_optim_step (csrc/optim.hip).  See DeviceOptimizer for
-    `step()` and for capturing it in a HIP graph."""
+    parameters, the HWGAT_OPT_ADAMW kind of the entry points (csrc/optim.hip).  See DeviceOptimizer for `step()` and for
+    capturing it in a HIP graph."""
 
-    _SET, _ADVANCE, _STEP = "hwgat_optim_set", "hwgat_optim_advance", "hwgat_optim_step"
-    _GUARDED_ADVANCE, _GUARDED_STEP = "hwgat_gguard_adamw_advance", "hwgat_gguard_adamw_step"
+    _KIND = KIND_ADAMW
     _STATE_KEYS = ("step", "exp_avg", "exp_avg_sq")
     _SCALAR_KEYS = ("step",)
 
@@ -898,18 +885,20 @@ class DeviceAdamW(DeviceOptimizer):
         return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
                 bool(group.get("decoupled_weight_decay", True)))
 
-    def _set_args(self, vals):
-        return (*vals[:5], int(vals[5]))
+    @staticmethod
+    def _hyper_words(vals):
+        """{lr, beta1, beta2, eps, weight_decay, coupled, 0, 0}"""
+        return (*vals[:5], 0.0 if vals[5] else 1.0, 0.0, 0.0)
 
-    def device_hyper(self):
-        """what the device block holds, read back: per group {lr, betas, eps, weight_decay, decoupled_weight_decay}"""
-        return [dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], decoupled_weight_decay=r[5] == 0.0)
-                for r in self._hyper_rows()]
+    @staticmethod
+    def _decode_hyper(r):
+        """{lr, betas, eps, weight_decay, decoupled_weight_decay}"""
+        return dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], decoupled_weight_decay=r[5] == 0.0)
 
     def _record(self, p, g, live, gi):
-        """(p, g, m, v, step addresses, n, group)"""
+        """(p, g, m, v, step, 0 addresses, n, group)"""
         return (p.data_ptr(), g.data_ptr(), live["exp_avg"].data_ptr(), live["exp_avg_sq"].data_ptr(),
-                live["step"].data_ptr(), p.numel(), gi)
+                live["step"].data_ptr(), 0, p.numel(), gi)
 
 
 def _refuse_unsupported(name, group):
@@ -920,18 +909,15 @@ def _refuse_unsupported(name, group):
 
 
 class DeviceSGD(DeviceOptimizer):
-    """torch.optim.SGD with maximize = False on fp32 parameters, on hwgat_sgd_set / hwgat_sgd_advance / hwgat_sgd_step
-    (csrc/optim_family.hip).  `state[p]` is torch's: {"momentum_buffer"} in a group whose momentum is not 0, nothing
+    """torch.optim.SGD with maximize = False on fp32 parameters, the HWGAT_OPT_SGD kind of the entry points
+    (csrc/optim.hip).  `state[p]` is torch's: {"momentum_buffer"} in a group whose momentum is not 0, nothing
     otherwise.  Torch's SGD keeps no step count; that a tensor's FIRST buffer is the gradient itself (torch clones it,
     whatever the dampening) is decided on the device from a private per-tensor word, which is not part of `state_dict()`:
     a buffer the caller seats before the first step is storage and counts as never stepped, one that arrives through
     `load_state_dict` counts as stepped.  A group whose momentum moves between 0 and non-zero is given (or stops using)
     its buffers at the next eager `step()`; after a capture that is refused, because the captured table cannot change."""
 
-    _SET, _ADVANCE, _STEP = "hwgat_sgd_set", "hwgat_sgd_advance", "hwgat_sgd_step"
-    _GUARDED_ADVANCE, _GUARDED_STEP = "hwgat_gguard_sgd_advance", "hwgat_gguard_sgd_step"
-    _PACK = staticmethod(build_family_table)
-    _ENTRY_BYTES, _NDERIVED = FAMILY_ENTRY_BYTES, FAMILY_NDERIVED
+    _KIND = KIND_SGD
     _STATE_KEYS = ("momentum_buffer",)
     _PRIVATE_KEYS = ("stepped",)
     _CAPTURABLE = False
@@ -960,8 +946,10 @@ class DeviceSGD(DeviceOptimizer):
             raise ValueError("nesterov momentum requires a momentum and zero dampening")
         return (lr, mom, damp, wd, bool(group["nesterov"]))
 
-    def _set_args(self, vals):
-        return (*vals[:4], int(vals[4]))
+    @staticmethod
+    def _hyper_words(vals):
+        """{lr, momentum, dampening, weight_decay, nesterov, 0, 0, 0}"""
+        return (*vals[:4], 1.0 if vals[4] else 0.0, 0.0, 0.0, 0.0)
 
     def push_hyper(self):
         if self._captured_momentum is not None:
@@ -977,10 +965,10 @@ class DeviceSGD(DeviceOptimizer):
             self._captured_momentum = [float(g["momentum"]) != 0.0 for g in self.param_groups]
         return table
 
-    def device_hyper(self):
-        """what the device block holds, read back: per group {lr, momentum, dampening, weight_decay, nesterov}"""
-        return [dict(lr=r[0], momentum=r[1], dampening=r[2], weight_decay=r[3], nesterov=r[4] != 0.0)
-                for r in self._hyper_rows()]
+    @staticmethod
+    def _decode_hyper(r):
+        """{lr, momentum, dampening, weight_decay, nesterov}"""
+        return dict(lr=r[0], momentum=r[1], dampening=r[2], weight_decay=r[3], nesterov=r[4] != 0.0)
 
     def _wants_state(self, group):
         return float(group["momentum"]) != 0.0
@@ -1002,14 +990,10 @@ class DeviceSGD(DeviceOptimizer):
 
 
 class DeviceNAdam(DeviceOptimizer):
-    """torch.optim.NAdam (both values of decoupled_weight_decay) with maximize = False on fp32 parameters, on
-    hwgat_nadam_set / hwgat_nadam_advance / hwgat_nadam_step (csrc/optim_family.hip).  `state[p]` is that of a capturable
-    torch NAdam: {"step", "mu_product": 0-d fp32 device tensors, "exp_avg", "exp_avg_sq"}."""
+    """torch.optim.NAdam (both values of decoupled_weight_decay) with maximize = False on fp32 parameters, the
+    HWGAT_OPT_NADAM kind of the entry points (csrc/optim.hip).  `state[p]` is that of a capturable torch NAdam: {"step", "mu_product": 0-d fp32 device tensors, "exp_avg", "exp_avg_sq"}."""
 
-    _SET, _ADVANCE, _STEP = "hwgat_nadam_set", "hwgat_nadam_advance", "hwgat_nadam_step"
-    _GUARDED_ADVANCE, _GUARDED_STEP = "hwgat_gguard_nadam_advance", "hwgat_gguard_nadam_step"
-    _PACK = staticmethod(build_family_table)
-    _ENTRY_BYTES, _NDERIVED = FAMILY_ENTRY_BYTES, FAMILY_NDERIVED
+    _KIND = KIND_NADAM
     _STATE_KEYS = ("step", "mu_product", "exp_avg", "exp_avg_sq")
     _SCALAR_KEYS = ("step", "mu_product")
     _INITIAL = {"mu_product": 1.0}
@@ -1040,14 +1024,16 @@ class DeviceNAdam(DeviceOptimizer):
             raise ValueError(f"invalid momentum_decay: {md}")
         return (lr, b1, b2, eps, wd, md, bool(group.get("decoupled_weight_decay", False)))
 
-    def _set_args(self, vals):
-        return (*vals[:6], int(vals[6]))
+    @staticmethod
+    def _hyper_words(vals):
+        """{lr, beta1, beta2, eps, weight_decay, coupled, momentum_decay, 0}"""
+        return (*vals[:5], 0.0 if vals[6] else 1.0, vals[5], 0.0)
 
-    def device_hyper(self):
-        """what the device block holds, read back: per group {lr, betas, eps, weight_decay, momentum_decay,
-        decoupled_weight_decay}"""
-        return [dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], momentum_decay=r[6],
-                     decoupled_weight_decay=r[5] == 0.0) for r in self._hyper_rows()]
+    @staticmethod
+    def _decode_hyper(r):
+        """{lr, betas, eps, weight_decay, momentum_decay, decoupled_weight_decay}"""
+        return dict(lr=r[0], betas=(r[1], r[2]), eps=r[3], weight_decay=r[4], momentum_decay=r[6],
+                    decoupled_weight_decay=r[5] == 0.0)
 
     def _record(self, p, g, live, gi):
         """(p, g, m, v, step, mu_product addresses, n, group)"""

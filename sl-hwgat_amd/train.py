@@ -238,9 +238,9 @@ class GraphedTrainStep:
     `torch.cuda.graph`), in THIS process: nothing is re-launched or exec'ed.
 
     The optimizer.  With an `optim.DeviceOptimizer` (AdamW / Adam, SGD, NAdam: every optimizer type of the reference) the
-    step is two more nodes of the graph (the class's `advance` and `step` entry points, e.g. hwgat_optim_advance and
-    hwgat_optim_step): its hyper-parameters are fp64 device words that the kernels read when they run, so `__call__` only
-    pushes the param groups' values when they changed (its `set` entry point, one tiny launch, e.g. after
+    step is two more nodes of the graph (hwgat_opt_advance and hwgat_opt_step with the class's `kind`): its
+    hyper-parameters are fp64 device words that the kernels read when they run, so `__call__` only
+    pushes the param groups' values when they changed (hwgat_opt_set, one tiny launch, e.g. after
     `scheduler.step()`) and replays; the optimizer's Python `step` is not entered, and a replay is the whole train step.
     The kernels and their inputs are the eager step's, so a replay and an eager TrainStep step agree bit for bit under
     `deterministic_train`, with any scheduler (tests/test_gpu_optim.py, tests/test_gpu_optim_family.py).  The warm-up's

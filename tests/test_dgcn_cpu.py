@@ -154,7 +154,7 @@ def test_new_entry_points_declared_bound_and_exported():
     handle = hw._lib.lib()
     for n in NEW_SYMBOLS:
         assert getattr(handle, n) is not None
-    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4006
+    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4007
     # argument checks that need no device: null pointers and unsupported shapes are refused before any launch
     assert handle.hwgat_dgcn_agg_fwd(None, None, None, 4, 29, 64, 8, None) == -1
     assert handle.hwgat_dgcn_agg_bwd(None, None, None, None, None, 4, 29, 64, 8, None, 0, None) == -1

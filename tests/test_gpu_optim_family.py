@@ -1,4 +1,4 @@
-"""optim.DeviceSGD and optim.DeviceNAdam on the device: the HIP kernels of csrc/optim_family.hip against the reference's
+"""optim.DeviceSGD and optim.DeviceNAdam on the device: the HIP kernels of csrc/optim.hip against the reference's
 other two optimizer types, torch.optim.SGD / torch.optim.NAdam (cfg.optimizer_type 'sgd' / 'nadam', hwgat/utils.py:73-84),
 run on the CPU in float64; and the whole train step -- optimizer included -- replayed as one HIP graph
 (train.GraphedTrainStep; reference loop hwgat/utils.py:93-116).

@@ -13,8 +13,7 @@ import torch
 hw = importlib.import_module("sl-hwgat_amd")
 optim = importlib.import_module("sl-hwgat_amd.optim")
 ck = hw.checkpoint
-GUARD_SYMBOLS = ({f"hwgat_gguard_{what}" for what in ("set", "partial", "finish", "scale")}
-                 | {f"hwgat_gguard_{kind}_{what}" for kind in ("adamw", "sgd", "nadam") for what in ("advance", "step")})
+GUARD_SYMBOLS = {f"hwgat_gguard_{what}" for what in ("set", "partial", "finish", "scale")}
 OPTIMIZERS = [(optim.DeviceAdamW, torch.optim.AdamW, dict(lr=2e-3, weight_decay=0.05)),
               (optim.DeviceSGD, torch.optim.SGD, dict(lr=2e-3, momentum=0.9)),
               (optim.DeviceNAdam, torch.optim.NAdam, dict(lr=2e-3))]
@@ -27,7 +26,7 @@ def test_symbols_abi_and_constants_follow_the_header():
     L = hw._lib.lib()
     for name in GUARD_SYMBOLS:                               # exported by the library that was built
         assert getattr(L, name) is not None
-    assert hw._lib.header_abi_version() == 4006 and L.hwgat_abi_version() == 4006
+    assert hw._lib.header_abi_version() == 4007 and L.hwgat_abi_version() == 4007
     with open(hw._lib.HEADER) as fh:
         src = fh.read()
     slots = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+HWGAT_GGUARD_(\w+)\s+(\d+)", src)}
@@ -36,8 +35,8 @@ def test_symbols_abi_and_constants_follow_the_header():
                 CLIP_COEF=optim.G_CLIP_COEF, NONFINITE=optim.G_NONFINITE, SKIP=optim.G_SKIP, STEPS=optim.G_STEPS,
                 CLIPPED=optim.G_CLIPPED, SKIPPED=optim.G_SKIPPED)
     assert slots == mine and sorted(mine.values()) == list(range(10))
-    for cls in (optim.DeviceAdamW, optim.DeviceSGD, optim.DeviceNAdam):
-        assert {cls._GUARDED_ADVANCE, cls._GUARDED_STEP} <= GUARD_SYMBOLS
+    for cls, name in ((optim.DeviceAdamW, "ADAMW"), (optim.DeviceSGD, "SGD"), (optim.DeviceNAdam, "NADAM")):
+        assert cls._KIND == int(re.search(rf"HWGAT_OPT_{name}\s*=\s*(\d+)", src).group(1))
 
 
 def test_entry_points_refuse_bad_arguments_without_launching():
@@ -49,38 +48,39 @@ def test_entry_points_refuse_bad_arguments_without_launching():
     for max_norm, norm_type in ((-1.0, 2.0), (math.nan, 2.0), (1.0, 1.0), (1.0, 3.0), (1.0, -inf), (1.0, math.nan)):
         assert L.hwgat_gguard_set(buf, max_norm, norm_type, 0, None) == -1, (max_norm, norm_type)
     part, fin, scale = L.hwgat_gguard_partial, L.hwgat_gguard_finish, L.hwgat_gguard_scale
-    for eb in (56, 64):
-        assert part(None, 1, eb, buf, buf, 1, None) == -1
-        assert part(buf, 1, eb, None, buf, 1, None) == -1
-        assert part(buf, 1, eb, buf, None, 1, None) == -1
-        assert part(buf, 1, eb, buf, odd, 1, None) == -1             # the workspace takes 16-byte stores
-        assert part(buf, 0, eb, buf, buf, 1, None) == -1
-        assert part(buf, -1, eb, buf, buf, 1, None) == -1
-        assert part(buf, 1, eb, buf, buf, 0, None) == -1
-        assert scale(None, 1, eb, buf, 1, None) == -1
-        assert scale(buf, 1, eb, None, 1, None) == -1
-        assert scale(buf, 0, eb, buf, 1, None) == -1
-        assert scale(buf, 1, eb, buf, 0, None) == -1
-    for eb in (0, 48, 60, 128):                                      # neither record type
-        assert part(buf, 1, eb, buf, buf, 1, None) == -1
-        assert scale(buf, 1, eb, buf, 1, None) == -1
+    assert part(None, 1, buf, buf, 1, None) == -1
+    assert part(buf, 1, None, buf, 1, None) == -1
+    assert part(buf, 1, buf, None, 1, None) == -1
+    assert part(buf, 1, buf, odd, 1, None) == -1                     # the workspace takes 16-byte stores
+    assert part(buf, 0, buf, buf, 1, None) == -1
+    assert part(buf, -1, buf, buf, 1, None) == -1
+    assert part(buf, 1, buf, buf, 0, None) == -1
+    assert scale(None, 1, buf, 1, None) == -1
+    assert scale(buf, 1, None, 1, None) == -1
+    assert scale(buf, 0, buf, 1, None) == -1
+    assert scale(buf, 1, buf, 0, None) == -1
     assert fin(None, 1, buf, None) == -1
     assert fin(odd, 1, buf, None) == -1
     assert fin(buf, 1, None, None) == -1
     assert fin(buf, 0, buf, None) == -1
-    for kind in ("adamw", "sgd", "nadam"):
-        advance, step = getattr(L, f"hwgat_gguard_{kind}_advance"), getattr(L, f"hwgat_gguard_{kind}_step")
-        assert advance(buf, 0, buf, buf, buf, None) == -1
-        assert advance(buf, -1, buf, buf, buf, None) == -1
-        for i in range(4):                                           # each pointer in turn
-            args = [buf, buf, buf, buf]
+    advance, step = L.hwgat_opt_advance, L.hwgat_opt_step            # the optimizers' launches with a guard's state block
+    for kind in (optim.KIND_ADAMW, optim.KIND_SGD, optim.KIND_NADAM):
+        assert advance(kind, buf, 0, buf, buf, buf, None) == -1
+        assert advance(kind, buf, -1, buf, buf, buf, None) == -1
+        for i in range(3):                                           # each non-nullable pointer in turn
+            args = [buf, buf, buf]
             args[i] = None
-            assert advance(args[0], 1, args[1], args[2], args[3], None) == -1, (kind, i)
-        assert step(buf, 1, buf, 0, buf, None) == -1
-        assert step(buf, 0, buf, 1, buf, None) == -1
-        assert step(None, 1, buf, 1, buf, None) == -1
-        assert step(buf, 1, None, 1, buf, None) == -1
-        assert step(buf, 1, buf, 1, None, None) == -1
+            # the guard's own pointer may be NULL (no guard): with or without one, the bad argument is refused
+            assert advance(kind, args[0], 1, args[1], args[2], buf, None) == -1, (kind, i)
+            assert advance(kind, args[0], 1, args[1], args[2], None, None) == -1, (kind, i)
+        for guard in (buf, None):
+            assert step(kind, buf, 1, buf, 0, guard, None) == -1
+            assert step(kind, buf, 0, buf, 1, guard, None) == -1
+            assert step(kind, None, 1, buf, 1, guard, None) == -1
+            assert step(kind, buf, 1, None, 1, guard, None) == -1
+    for bad in (-1, 3):
+        assert advance(bad, buf, 1, buf, buf, buf, None) == -1
+        assert step(bad, buf, 1, buf, 1, buf, None) == -1
 
 
 @pytest.mark.parametrize("cls, like, kw", OPTIMIZERS, ids=["adamw", "sgd", "nadam"])

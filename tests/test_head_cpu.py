@@ -36,7 +36,7 @@ def test_entry_points_declared_bound_and_exported():
     handle = hw._lib.lib()
     for n in HEAD_SYMBOLS:
         assert getattr(handle, n) is not None
-    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4006
+    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4007
 
 
 def _calls():

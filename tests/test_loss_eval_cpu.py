@@ -21,7 +21,7 @@ def test_new_entry_points_declared_bound_and_exported():
     handle = hw._lib.lib()
     for n in NEW_SYMBOLS:
         assert getattr(handle, n) is not None
-    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4006
+    assert handle.hwgat_abi_version() == hw._lib.header_abi_version() == 4007
     assert hw.evaluate is evaluate and "evaluate" in hw.__all__
 
 

@@ -11,13 +11,13 @@ hw = importlib.import_module("sl-hwgat_amd")
 optim = importlib.import_module("sl-hwgat_amd.optim")
 ck = hw.checkpoint
 CHUNK = optim.CHUNK
-NEW_SYMBOLS = {"hwgat_optim_set", "hwgat_optim_advance", "hwgat_optim_step"}
+NEW_SYMBOLS = {"hwgat_opt_set", "hwgat_opt_advance", "hwgat_opt_step"}
 
 
 def _header_struct_bytes():
-    """sizeof(hwgat_optim_entry) from the header's own text, laid out by ctypes with the C rules"""
+    """sizeof(hwgat_opt_entry) from the header's own text, laid out by ctypes with the C rules"""
     with open(hw._lib.HEADER) as fh:
-        body = re.search(r"typedef struct \{([^}]*)\}\s*hwgat_optim_entry;", fh.read()).group(1)
+        body = re.search(r"typedef struct \{([^}]*)\}\s*hwgat_opt_entry;", fh.read()).group(1)
     fields = []
     for decl in body.split(";"):
         decl = decl.strip()
@@ -33,22 +33,58 @@ def _header_struct_bytes():
 
 def test_symbols_constants_and_record_size_follow_the_header():
     assert NEW_SYMBOLS <= set(hw._lib.declared_symbols())
-    assert NEW_SYMBOLS == {n for n in hw._lib._SIGS if n.startswith("hwgat_optim_")}
+    assert NEW_SYMBOLS == {n for n in hw._lib._SIGS if n.startswith("hwgat_opt_")}
     size, names = _header_struct_bytes()
-    assert names == ["p", "g", "m", "v", "step", "n", "group", "first_block"]
-    assert optim.ENTRY_BYTES == size == 56
+    assert names == ["p", "g", "s0", "s1", "w0", "w1", "n", "group", "first_block"]
+    assert optim.ENTRY_BYTES == optim.ENTRY.size == size == 64
     with open(hw._lib.HEADER) as fh:
         src = fh.read()
-    for name, val in (("CHUNK", optim.CHUNK), ("NHYPER", optim.NHYPER), ("NDERIVED", optim.NDERIVED)):
-        assert int(re.search(rf"#define\s+HWGAT_OPTIM_{name}\s+(\d+)", src).group(1)) == val
+    assert "hwgat_optim_entry" not in src                    # the one record serves all three optimizers
+    for name, val in (("OPTIM_CHUNK", optim.CHUNK), ("OPTIM_NHYPER", optim.NHYPER), ("OPT_NDERIVED", optim.NDERIVED)):
+        assert int(re.search(rf"#define\s+HWGAT_{name}\s+(\d+)", src).group(1)) == val
+    assert (optim.CHUNK, optim.NHYPER, optim.NDERIVED) == (4096, 8, 16)
+    kinds = {m.group(1): int(m.group(2)) for m in re.finditer(r"HWGAT_OPT_(ADAMW|SGD|NADAM)\s*=\s*(\d+)", src)}
+    assert kinds == dict(ADAMW=optim.KIND_ADAMW, SGD=optim.KIND_SGD, NADAM=optim.KIND_NADAM) == dict(ADAMW=0, SGD=1, NADAM=2)
+    assert optim.DeviceAdamW._KIND == kinds["ADAMW"]
+
+
+def test_entry_points_refuse_bad_arguments_without_launching():
     L = hw._lib.lib()                                        # bad arguments are refused before any HIP call
-    assert L.hwgat_optim_set(None, 0, 1e-3, 0.9, 0.999, 1e-8, 0.01, 1, None) == -1
-    buf = ctypes.cast((ctypes.c_double * 8)(), ctypes.c_void_p)
-    assert L.hwgat_optim_set(buf, -1, 1e-3, 0.9, 0.999, 1e-8, 0.01, 1, None) == -1
-    assert L.hwgat_optim_advance(buf, 0, buf, buf, None) == -1
-    assert L.hwgat_optim_advance(None, 1, buf, buf, None) == -1
-    assert L.hwgat_optim_step(buf, 1, buf, 0, None) == -1
-    assert L.hwgat_optim_step(buf, 1, None, 1, None) == -1
+    buf = ctypes.cast((ctypes.c_double * 8)(), ctypes.c_void_p)      # host memory: never dereferenced by a refused call
+    kind = optim.KIND_ADAMW
+    assert L.hwgat_opt_set(None, 0, kind, buf, None) == -1
+    assert L.hwgat_opt_set(buf, 0, kind, None, None) == -1
+    assert L.hwgat_opt_set(buf, -1, kind, buf, None) == -1
+    for bad in (-1, 3):
+        assert L.hwgat_opt_set(buf, 0, bad, buf, None) == -1
+    advance, step = L.hwgat_opt_advance, L.hwgat_opt_step
+    for guard in (buf, None):                                # a NULL guard is not what is refused: the other argument is
+        assert advance(kind, buf, 0, buf, buf, guard, None) == -1
+        assert advance(kind, buf, -1, buf, buf, guard, None) == -1
+        for i in range(3):                                   # each non-nullable pointer in turn
+            args = [buf, buf, buf]
+            args[i] = None
+            assert advance(kind, args[0], 1, args[1], args[2], guard, None) == -1, i
+        assert step(kind, buf, 0, buf, 1, guard, None) == -1
+        assert step(kind, buf, 1, buf, 0, guard, None) == -1
+        assert step(kind, buf, 1, buf, -1, guard, None) == -1
+        assert step(kind, None, 1, buf, 1, guard, None) == -1
+        assert step(kind, buf, 1, None, 1, guard, None) == -1
+        for bad in (-1, 3):
+            assert advance(bad, buf, 1, buf, buf, guard, None) == -1
+            assert step(bad, buf, 1, buf, 1, guard, None) == -1
+
+
+def test_hyper_words_are_the_device_layout_and_decode_back():
+    """{lr, beta1, beta2, eps, weight_decay, coupled, 0, 0}: `coupled` is the inverse of decoupled_weight_decay"""
+    p = torch.nn.Parameter(torch.zeros(4))
+    for decoupled, coupled in ((True, 0.0), (False, 1.0)):
+        o = optim.DeviceAdamW([p], lr=3e-4, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.02, decoupled_weight_decay=decoupled)
+        words = o._hyper_words(o._group_values(o.param_groups[0]))
+        assert len(words) == optim.NHYPER == 8 and all(type(w) is float for w in words)
+        assert tuple(words) == (3e-4, 0.8, 0.95, 1e-6, 0.02, coupled, 0.0, 0.0)
+        assert o._decode_hyper(list(words)) == dict(lr=3e-4, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.02,
+                                                    decoupled_weight_decay=decoupled)
 
 
 SIZES = [1, 3, CHUNK - 1, CHUNK, CHUNK + 1]
@@ -61,11 +97,11 @@ def test_table_builder_prefix_sums_and_skipped_parameters():
         p.grad = torch.ones_like(p)
     recs = opt.table_records()                               # the last parameter has no gradient: no entry, no state
     assert len(recs) == len(SIZES) and params[-1] not in opt.state
-    assert [r[5] for r in recs] == SIZES and [r[6] for r in recs] == [0, 0, 1, 1, 1]
+    assert [r[6] for r in recs] == SIZES and [r[7] for r in recs] == [0, 0, 1, 1, 1]
     for r, p in zip(recs, params):
         st = opt.state[p]
-        assert r[:5] == (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                         st["step"].data_ptr())
+        assert r[:6] == (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                         st["step"].data_ptr(), 0)
         assert st["step"].shape == () and st["step"].dtype == torch.float32 and float(st["step"]) == 0.0
     blob, first, total = optim.build_table(recs)
     blocks = [-(-n // CHUNK) for n in SIZES]
@@ -76,10 +112,14 @@ def test_table_builder_prefix_sums_and_skipped_parameters():
         assert optim.ENTRY.unpack_from(blob, i * optim.ENTRY_BYTES) == r + (first[i],)
     params[1].grad = None                                    # a gradient that goes away leaves the table, keeps its state
     recs2 = opt.table_records()
-    assert [r[5] for r in recs2] == [1, CHUNK - 1, CHUNK, CHUNK + 1] and params[1] in opt.state
+    assert [r[6] for r in recs2] == [1, CHUNK - 1, CHUNK, CHUNK + 1] and params[1] in opt.state
     assert optim.build_table(recs2)[1] == [0, 1, 2, 3]
     with pytest.raises(ValueError):
-        optim.build_table([(8, 8, 8, 8, 8, 0, 0)])
+        optim.build_table([(8, 8, 8, 8, 8, 0, 0, 0)])       # an empty tensor
+    blocks = 2 ** 30                                         # 2^31 workgroups are more than one launch holds
+    assert optim.build_table([(8, 8, 8, 8, 8, 0, blocks * CHUNK, 0), (8, 8, 8, 8, 8, 0, (blocks - 1) * CHUNK, 0)])[2] == 2 ** 31 - 1
+    with pytest.raises(ValueError, match="one launch"):
+        optim.build_table([(8, 8, 8, 8, 8, 0, blocks * CHUNK, 0)] * 2)
 
 
 def _stepped_torch_adamw(params, **kw):

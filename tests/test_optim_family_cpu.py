@@ -1,4 +1,4 @@
-"""CPU: host logic of optim.DeviceSGD and optim.DeviceNAdam -- the hwgat_opt_entry table's layout, state_dict interchange
+"""CPU: host logic of optim.DeviceSGD and optim.DeviceNAdam -- their hwgat_opt_entry records, state_dict interchange
 with torch.optim.SGD / torch.optim.NAdam (the reference's cfg.optimizer_type 'sgd' / 'nadam', hwgat/utils.py:73-84),
 argument errors, checkpoint.get_device_optimizer."""
 import ctypes
@@ -12,7 +12,8 @@ hw = importlib.import_module("sl-hwgat_amd")
 optim = importlib.import_module("sl-hwgat_amd.optim")
 ck = hw.checkpoint
 CHUNK = optim.CHUNK
-NEW_SYMBOLS = {f"hwgat_{kind}_{what}" for kind in ("sgd", "nadam") for what in ("set", "advance", "step")}
+NEW_SYMBOLS = {f"hwgat_opt_{what}" for what in ("set", "advance", "step")}
+KINDS = [(optim.DeviceSGD, "SGD"), (optim.DeviceNAdam, "NADAM")]
 SIZES = [1, 3, CHUNK - 1, CHUNK, CHUNK + 1]
 
 
@@ -35,37 +36,67 @@ def _header_struct_bytes(name):
 
 def test_symbols_constants_and_record_size_follow_the_header():
     assert NEW_SYMBOLS <= set(hw._lib.declared_symbols())
-    assert NEW_SYMBOLS == {n for n in hw._lib._SIGS if n.startswith(("hwgat_sgd_", "hwgat_nadam_"))}
+    assert NEW_SYMBOLS == {n for n in hw._lib._SIGS if n.startswith("hwgat_opt_")}
+    assert not any(n.startswith(("hwgat_optim_", "hwgat_sgd_", "hwgat_nadam_")) for n in hw._lib._SIGS)
     L = hw._lib.lib()
     for name in NEW_SYMBOLS:                                 # exported by the library that was built
         assert getattr(L, name) is not None
     size, names = _header_struct_bytes("hwgat_opt_entry")
     assert names == ["p", "g", "s0", "s1", "w0", "w1", "n", "group", "first_block"]
-    assert optim.FAMILY_ENTRY_BYTES == size == 64
+    assert optim.ENTRY_BYTES == optim.ENTRY.size == size == 64
     with open(hw._lib.HEADER) as fh:
         src = fh.read()
-    assert int(re.search(r"#define\s+HWGAT_OPT_NDERIVED\s+(\d+)", src).group(1)) == optim.FAMILY_NDERIVED
-    assert optim.DeviceSGD._NDERIVED == optim.DeviceNAdam._NDERIVED == optim.FAMILY_NDERIVED
-    # the AdamW record and constants are where they were
-    assert _header_struct_bytes("hwgat_optim_entry")[0] == optim.ENTRY_BYTES == 56
-    assert (optim.CHUNK, optim.NHYPER, optim.NDERIVED) == (4096, 8, 8)
-    # bad arguments are refused before any HIP call
-    buf = ctypes.cast((ctypes.c_double * 16)(), ctypes.c_void_p)
-    assert L.hwgat_sgd_set(None, 0, 1e-3, 0.9, 0.0, 0.01, 0, None) == -1
-    assert L.hwgat_sgd_set(buf, -1, 1e-3, 0.9, 0.0, 0.01, 0, None) == -1
-    assert L.hwgat_nadam_set(None, 0, 1e-3, 0.9, 0.999, 1e-8, 0.01, 4e-3, 0, None) == -1
-    assert L.hwgat_nadam_set(buf, -1, 1e-3, 0.9, 0.999, 1e-8, 0.01, 4e-3, 0, None) == -1
-    for kind in ("sgd", "nadam"):
-        advance, step = getattr(L, f"hwgat_{kind}_advance"), getattr(L, f"hwgat_{kind}_step")
-        assert advance(buf, 0, buf, buf, None) == -1
-        assert advance(buf, -1, buf, buf, None) == -1
-        assert advance(None, 1, buf, buf, None) == -1
-        assert advance(buf, 1, None, buf, None) == -1
-        assert advance(buf, 1, buf, None, None) == -1
-        assert step(buf, 1, buf, 0, None) == -1
-        assert step(buf, 0, buf, 1, None) == -1
-        assert step(buf, 1, None, 1, None) == -1
-        assert step(None, 1, buf, 1, None) == -1
+    assert "hwgat_optim_entry" not in src                    # one record, one derived width
+    assert int(re.search(r"#define\s+HWGAT_OPT_NDERIVED\s+(\d+)", src).group(1)) == optim.NDERIVED == 16
+    assert (optim.CHUNK, optim.NHYPER) == (4096, 8)
+    for cls, name in KINDS:
+        assert cls._KIND == int(re.search(rf"HWGAT_OPT_{name}\s*=\s*(\d+)", src).group(1))
+
+
+def test_entry_points_refuse_bad_arguments_without_launching():
+    L = hw._lib.lib()
+    buf = ctypes.cast((ctypes.c_double * 16)(), ctypes.c_void_p)     # host memory: never dereferenced by a refused call
+    advance, step = L.hwgat_opt_advance, L.hwgat_opt_step
+    for cls, _ in KINDS:
+        kind = cls._KIND
+        assert L.hwgat_opt_set(None, 0, kind, buf, None) == -1
+        assert L.hwgat_opt_set(buf, 0, kind, None, None) == -1
+        assert L.hwgat_opt_set(buf, -1, kind, buf, None) == -1
+        for guard in (buf, None):                            # a NULL guard is not what is refused: the other argument is
+            assert advance(kind, buf, 0, buf, buf, guard, None) == -1
+            assert advance(kind, buf, -1, buf, buf, guard, None) == -1
+            assert advance(kind, None, 1, buf, buf, guard, None) == -1
+            assert advance(kind, buf, 1, None, buf, guard, None) == -1
+            assert advance(kind, buf, 1, buf, None, guard, None) == -1
+            assert step(kind, buf, 1, buf, 0, guard, None) == -1
+            assert step(kind, buf, 1, buf, -1, guard, None) == -1
+            assert step(kind, buf, 0, buf, 1, guard, None) == -1
+            assert step(kind, buf, 1, None, 1, guard, None) == -1
+            assert step(kind, None, 1, buf, 1, guard, None) == -1
+    for bad in (-1, 3):
+        assert L.hwgat_opt_set(buf, 0, bad, buf, None) == -1
+        assert advance(bad, buf, 1, buf, buf, None, None) == -1
+        assert step(bad, buf, 1, buf, 1, None, None) == -1
+
+
+def test_hyper_words_are_the_device_layout_and_decode_back():
+    """SGD {lr, momentum, dampening, weight_decay, nesterov, 0, 0, 0}; NAdam {lr, beta1, beta2, eps, weight_decay, coupled,
+    momentum_decay, 0}, `coupled` the inverse of decoupled_weight_decay"""
+    p = torch.nn.Parameter(torch.zeros(4))
+    cases = [(optim.DeviceSGD, dict(lr=3e-2, momentum=0.8, dampening=0.0, weight_decay=0.02, nesterov=True),
+              (3e-2, 0.8, 0.0, 0.02, 1.0, 0.0, 0.0, 0.0)),
+             (optim.DeviceSGD, dict(lr=3e-2, momentum=0.8, dampening=0.25, weight_decay=0.02, nesterov=False),
+              (3e-2, 0.8, 0.25, 0.02, 0.0, 0.0, 0.0, 0.0)),
+             (optim.DeviceNAdam, dict(lr=3e-4, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.02, momentum_decay=5e-3,
+                                      decoupled_weight_decay=True), (3e-4, 0.8, 0.95, 1e-6, 0.02, 0.0, 5e-3, 0.0)),
+             (optim.DeviceNAdam, dict(lr=3e-4, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.02, momentum_decay=5e-3,
+                                      decoupled_weight_decay=False), (3e-4, 0.8, 0.95, 1e-6, 0.02, 1.0, 5e-3, 0.0))]
+    for cls, kw, want in cases:
+        o = cls([p], **kw)
+        words = o._hyper_words(o._group_values(o.param_groups[0]))
+        assert len(words) == optim.NHYPER == 8 and all(type(w) is float for w in words)
+        assert tuple(words) == want, kw
+        assert o._decode_hyper(list(words)) == kw
 
 
 def _two_groups(cls, **kw):
@@ -77,13 +108,13 @@ def _two_groups(cls, **kw):
 
 
 def _check_packing(recs):
-    blob, first, total = optim.build_family_table(recs)
+    blob, first, total = optim.build_table(recs)
     blocks = [-(-n // CHUNK) for n in SIZES]
     assert blocks == [1, 1, 1, 1, 2]
     assert first == [sum(blocks[:i]) for i in range(len(blocks))] and total == sum(blocks)
-    assert len(blob) == len(recs) * optim.FAMILY_ENTRY_BYTES
+    assert len(blob) == len(recs) * optim.ENTRY_BYTES
     for i, r in enumerate(recs):                             # every record reads back field by field
-        assert optim.FAMILY_ENTRY.unpack_from(blob, i * optim.FAMILY_ENTRY_BYTES) == r + (first[i],)
+        assert optim.ENTRY.unpack_from(blob, i * optim.ENTRY_BYTES) == r + (first[i],)
 
 
 def test_sgd_table_records_prefix_sums_and_skipped_parameters():
@@ -100,9 +131,9 @@ def test_sgd_table_records_prefix_sums_and_skipped_parameters():
     params[1].grad = None                                    # a gradient that goes away leaves the table, keeps its state
     recs2 = opt.table_records()
     assert [r[6] for r in recs2] == [1, CHUNK - 1, CHUNK, CHUNK + 1] and params[1] in opt.state
-    assert optim.build_family_table(recs2)[1] == [0, 1, 2, 3]
+    assert optim.build_table(recs2)[1] == [0, 1, 2, 3]
     with pytest.raises(ValueError):
-        optim.build_family_table([(8, 8, 8, 0, 8, 0, 0, 0)])
+        optim.build_table([(8, 8, 8, 0, 8, 0, 0, 0)])
     # momentum 0 in one group: its tensors get null state pointers and NO state, as in torch
     params, opt = _two_groups(optim.DeviceSGD, momentum=0.9)
     opt.param_groups[0]["momentum"] = 0.0

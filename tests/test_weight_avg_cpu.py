@@ -39,7 +39,7 @@ def test_symbols_abi_and_constants_follow_the_header():
     L = hw._lib.lib()
     for name in WAVG_SYMBOLS:                                # exported by the library that was built
         assert getattr(L, name) is not None
-    assert hw._lib.header_abi_version() == 4006 and L.hwgat_abi_version() == 4006
+    assert hw._lib.header_abi_version() == 4007 and L.hwgat_abi_version() == 4007
     with open(hw._lib.HEADER) as fh:
         src = fh.read()
     slots = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+HWGAT_WAVG_(\w+)\s+(\d+)", src)}

@@ -72,13 +72,13 @@ def part_launch(args):
         st, ws = _lib.ptr(guard._state), _lib.ptr(table.guard_ws)
 
         def partial():
-            _lib.call("hwgat_gguard_partial", _lib.ptr(table.buf), table.n, table.entry_bytes, st, ws, table.total, _lib.stream())
+            _lib.call("hwgat_gguard_partial", _lib.ptr(table.buf), table.n, st, ws, table.total, _lib.stream())
 
         def finish():
             _lib.call("hwgat_gguard_finish", ws, table.total, st, _lib.stream())
 
         def scale():
-            _lib.call("hwgat_gguard_scale", _lib.ptr(table.buf), table.n, table.entry_bytes, st, table.total, _lib.stream())
+            _lib.call("hwgat_gguard_scale", _lib.ptr(table.buf), table.n, st, table.total, _lib.stream())
 
         def guard_all():
             optim.clip_grad_norm_(ps, guard)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the HIP optimizers (optim.DeviceAdamW / DeviceSGD / DeviceNAdam, csrc/optim.hip and csrc/optim_family.hip) cost and
+"""What the HIP optimizers (optim.DeviceAdamW / DeviceSGD / DeviceNAdam, csrc/optim.hip) cost and
 buy, measured on the device.  Two parts, each a child process of its own under its own time limit (a part that fails ends
 the run; nothing is started after it):
 
