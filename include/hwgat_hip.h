@@ -76,7 +76,9 @@ extern "C" {
  *   4007  one record and one entry-point triple for the device optimizers: hwgat_opt_{set,advance,step} with a `kind` and
  *         a nullable `guard_state` replace hwgat_{optim,sgd,nadam}_{set,advance,step} and
  *         hwgat_gguard_{adamw,sgd,nadam}_{advance,step}; hwgat_opt_entry (64 bytes) is the only table record, and
- *         hwgat_gguard_{partial,scale} lose their record-size argument */
+ *         hwgat_gguard_{partial,scale} lose their record-size argument
+ *         later additions under the same number (additions only, no existing signature changed):
+ *         hwgat_stream_{state_bytes,push,window,decide}, ring-buffered keypoint streams for serve.StreamRecognizer */
 #define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
@@ -766,6 +768,79 @@ int hwgat_aug_hand_fill(float* x, const int32_t* clip_off, const uint8_t* masked
 int hwgat_aug_resample(const float* x, const int32_t* clip_off, const int32_t* src, const double* prm,
                        const int32_t* gather, float* out, int n_clips, int src_len, int J, int J_out, int C,
                        void* stream);
+
+/* ---- streaming recognition (serve.StreamRecognizer): n_streams keypoint streams kept in device ring buffers, cut into the
+ * packed clip / frame map / parameter record that hwgat_aug_hand_fill and hwgat_aug_resample take (the eval transform of
+ * augment.EvalTransform.draw, normalisation included), and a decision rule behind the logits.  Every value that changes
+ * between steps is a DEVICE word, so push -> window -> hand fill -> resample -> forward -> decide replays as one HIP graph.
+ *
+ * ring:  (n_streams, ring_frames, J, C) fp32 raw frames, ring_frames <= HWGAT_AUG_MAX_FRAMES, C in {2, 3}.
+ * state: hwgat_stream_state_bytes(n_streams, log_capacity) bytes of DEVICE memory, 8-byte aligned, zeroed once by the caller
+ *        (the four hyper-parameter words are then written by the caller):
+ *          hwgat_stream_header                       log_count: events in the log; overflow: events that found it full;
+ *                                                    alpha, threshold, hold, blank_class: the decision rule's parameters,
+ *                                                    read when hwgat_stream_decide runs
+ *          hwgat_stream_words[n_streams]             per stream, see the struct
+ *          hwgat_stream_event[log_capacity]          the event log, in the order the events were emitted
+ *
+ * hwgat_stream_push: appends n = clamp(n_new[s], 0, push_frames) frames of frames (n_streams, push_frames, J, C) to ring s at
+ *   slot head, head + 1, .. (mod ring_frames), overwriting the oldest; head = (head + n) mod ring_frames,
+ *   count = min(count + n, ring_frames), frames_seen += n.  push_frames <= ring_frames.  head and count are reduced to
+ *   [0, ring_frames) / [0, ring_frames] when they are read, so no word of device memory can move an address out of the ring.
+ * hwgat_stream_window: per stream, L = min(count, window_frames) (window_frames <= ring_frames):
+ *   clip      (n_streams * window_frames, J, C) fp32: the L newest frames, oldest first, stream after stream
+ *   clip_off  (n_streams + 1) int32 prefix sums of L
+ *   src       (n_streams, src_len) int32: EvalTransform._temporal_sample(L, False).  L <= src_len: centred, padded with the
+ *             first frame in the front half and the last behind; else int(i * ((L - 1) / (src_len - 1))) in fp64 with the last
+ *             entry L - 1 (numpy.linspace(0, L - 1, src_len).astype(int)).  L = 0: zeros.
+ *   prm       (n_streams, HWGAT_AUG_NPRM) fp64 eval record: [0..C) left_top, [3] edge_dist, M = I, [21] = (L <= src_len).
+ *             From the first frame f of the window whose joints origin, anchor0, anchor1 are non-zero in every coordinate, in
+ *             fp32, every operation rounded on its own: unit = sqrt(sum_c (kp[anchor0][c] - kp[anchor1][c])^2),
+ *             left_top[c] = kp[origin][c] - 3 unit, left_top[1] = kp[origin][1] - 2 unit, edge_dist = 6 unit.
+ *   ready     (in hwgat_stream_words) = count >= min_frames and such a frame exists and unit is positive and finite;
+ *             otherwise the record is left_top = 0, edge_dist = 1.  A stream without frames has an empty clip, which both
+ *             transform kernels take (the hand fill returns, the resampler writes zeros).
+ *   hands     HOST int32[6] as for hwgat_aug_hand_fill; origin and the anchors must lie in [0, J) outside both hands.
+ * hwgat_stream_decide: per ready stream s, from logits (n_streams, n_classes) fp32 and q (n_streams, n_classes) fp32:
+ *   p = softmax(logits[s]); q[s] = p on the stream's first ready evaluation, else (1 - alpha) q[s] + alpha p;
+ *   top = lowest arg-max of q[s], conf = q[s][top]; run = run + 1 if top is the previous top, else run = 1 and fired = 0;
+ *   run >= hold and conf >= threshold and fired == 0 and top != blank_class: an event { s, frames_seen, evals, top, conf } is
+ *   appended (or counted in overflow when log_count == log_capacity) and fired = 1; then evals += 1.
+ *   One workgroup: a wave per stream, each sum in one fixed order, the log appended by one thread in stream order.  A stream
+ *   that is not ready is not touched. */
+#define HWGAT_STREAM_MAX_STREAMS 64
+#define HWGAT_STREAM_MAX_CLASSES 65536
+#define HWGAT_STREAM_MAX_LOG (1 << 20)
+typedef struct {
+    int64_t log_count, overflow;
+    float alpha, threshold;
+    int32_t hold, blank_class;                  /* blank_class -1: none */
+    int64_t spare[4];
+} hwgat_stream_header;                          /* 64 bytes */
+typedef struct {
+    int32_t head, count;                        /* next slot to write; frames held, <= ring_frames */
+    int64_t frames_seen;                        /* frames ever pushed */
+    int32_t ready, win_len;                     /* of the last hwgat_stream_window: ready word, L */
+    int32_t top, run;                           /* of the last ready evaluation */
+    float conf;
+    int32_t fired;
+    int64_t evals, events;                      /* ready evaluations; events emitted (overflowed ones included) */
+    int64_t spare;
+} hwgat_stream_words;                           /* 64 bytes */
+typedef struct {
+    int64_t frames_seen, evaluation;            /* the stream's frames_seen and 0-based ready evaluation at the event */
+    int32_t stream, cls;
+    float conf;
+    int32_t pad;
+} hwgat_stream_event;                           /* 32 bytes */
+int64_t hwgat_stream_state_bytes(int n_streams, int log_capacity);
+int hwgat_stream_push(float* ring, void* state, const float* frames, const int32_t* n_new, int n_streams, int ring_frames,
+                      int push_frames, int J, int C, void* stream);
+int hwgat_stream_window(const float* ring, void* state, float* clip, int32_t* clip_off, int32_t* src, double* prm,
+                        int n_streams, int ring_frames, int window_frames, int min_frames, int src_len, int J, int C,
+                        int origin, int anchor0, int anchor1, const int32_t* hands, void* stream);
+int hwgat_stream_decide(void* state, float* q, const float* logits, int n_streams, int n_classes, int log_capacity,
+                        void* stream);
 
 /* ---- Transformer baseline (ABI 4004; reference hwgat/models/Transformer.py).  Activations (B, T, d) with d = nH * 64.
  *

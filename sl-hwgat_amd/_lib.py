@@ -143,6 +143,10 @@ _SIGS = {
     "hwgat_meter_bytes": [_I, _I],
     "hwgat_meter_fold": [_P, _P, _P, _P, _I, _P, _I, _P],
     "hwgat_meter_close": [_P, _I, _I, _P],
+    "hwgat_stream_state_bytes": [_I, _I],
+    "hwgat_stream_push": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "hwgat_stream_window": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "hwgat_stream_decide": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

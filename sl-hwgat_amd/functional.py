@@ -4,6 +4,7 @@ Every function here calls straight into libhwgat_hip.so through `_lib.call`;
 nothing falls back to torch arithmetic.  All activations are in the natural
 token order (B, F, K, d).
 """
+import ctypes
 from typing import Callable, NamedTuple
 
 import torch
@@ -1576,3 +1577,74 @@ def head_linear(feat, weight, bias=None):
     if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],)):
         raise ValueError(f"head: bias must be an fp32 ({weight.shape[0]},) tensor or None")
     return _HeadLinear.apply(feat, weight, bias)
+
+
+# ---------------------------------------------------------------- streaming recognition (csrc/stream.hip, serve.StreamRecognizer)
+# The state block is int64 words (layout: include/hwgat_hip.h, "streaming recognition"): a header, one record per stream and
+# the event log; serve.py mirrors the records as numpy dtypes.
+STREAM_MAX_STREAMS, STREAM_MAX_CLASSES, STREAM_MAX_LOG = 64, 65536, 1 << 20
+STREAM_MAX_FRAMES = 4096                       # HWGAT_AUG_MAX_FRAMES: the longest ring
+STREAM_HEADER_WORDS, STREAM_WORDS, STREAM_EVENT_WORDS = 8, 8, 4
+STREAM_NPRM = 24                               # HWGAT_AUG_NPRM
+
+
+def stream_state_words(n_streams, log_capacity):
+    """size of a recogniser's state block in 8-byte words"""
+    n = _lib.lib().hwgat_stream_state_bytes(int(n_streams), int(log_capacity))
+    if n < 0:
+        raise ValueError(f"no stream state for {n_streams} streams (1..{STREAM_MAX_STREAMS}) and log capacity "
+                         f"{log_capacity} (0..{STREAM_MAX_LOG})")
+    return n // 8
+
+
+def _stream_ring(ring, state, log_capacity):
+    if ring.dtype != torch.float32 or ring.dim() != 4:
+        raise ValueError(f"the ring must be fp32 (streams, ring_frames, J, C), got {ring.dtype} {tuple(ring.shape)}")
+    if state.dtype != torch.int64 or state.numel() < stream_state_words(ring.shape[0], log_capacity):
+        raise ValueError("the stream state must be int64 and stream_state_words(n_streams, log_capacity) long")
+    return tuple(ring.shape)
+
+
+def stream_push(ring, state, frames, n_new):
+    """append clamp(n_new[s], 0, F) frames of frames (S, F, J, C) fp32 to ring s of ring (S, R, J, C), overwriting the oldest;
+    n_new (S,) device int32.  One launch; nothing is read back"""
+    S, R, J, C = _stream_ring(ring, state, 0)
+    if frames.dtype != torch.float32 or frames.dim() != 4 or (frames.shape[0],) + tuple(frames.shape[2:]) != (S, J, C):
+        raise ValueError(f"frames must be fp32 ({S}, push_frames, {J}, {C}), got {frames.dtype} {tuple(frames.shape)}")
+    if n_new.dtype != torch.int32 or tuple(n_new.shape) != (S,):
+        raise ValueError(f"n_new must be a device int32 tensor of {S} elements")
+    call("hwgat_stream_push", ptr(ring), ptr(state), ptr(frames), ptr(n_new), S, R, frames.shape[1], J, C, stream())
+
+
+def stream_window(ring, state, clip, clip_off, src, prm, window_frames, min_frames, origin, anchors, hands):
+    """the newest min(count, window_frames) frames of every ring as the packed clip (S * window_frames, J, C), clip_off
+    (S + 1) int32, the eval frame map src (S, src_len) int32 and parameter record prm (S, 24) fp64 that hand_fill / resample
+    take, and the ready words in `state`.  One launch"""
+    S, R, J, C = _stream_ring(ring, state, 0)
+    Wf = int(window_frames)
+    if clip.dtype != torch.float32 or clip.numel() < S * Wf * J * C:
+        raise ValueError(f"the clip buffer must hold fp32 ({S} * {Wf}, {J}, {C})")
+    if clip_off.dtype != torch.int32 or clip_off.numel() != S + 1:
+        raise ValueError(f"clip_off must be int32 with {S + 1} elements")
+    if src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != S:
+        raise ValueError(f"the frame map must be int32 ({S}, src_len)")
+    if prm.dtype != torch.float64 or tuple(prm.shape) != (S, STREAM_NPRM):
+        raise ValueError(f"the parameter records must be fp64 ({S}, {STREAM_NPRM})")
+    if len(anchors) != 2 or len(hands) != 6:
+        raise ValueError("two anchor joints and six hand words (l0, l1, lw, r0, r1, rw)")
+    hv = (ctypes.c_int32 * 6)(*[int(h) for h in hands])
+    call("hwgat_stream_window", ptr(ring), ptr(state), ptr(clip), ptr(clip_off), ptr(src), ptr(prm), S, R, Wf,
+         int(min_frames), src.shape[1], J, C, int(origin), int(anchors[0]), int(anchors[1]), hv, stream())
+
+
+def stream_decide(state, q, logits, log_capacity):
+    """softmax, smoothing and the event rule of every ready stream from logits (S, N) fp32; q (S, N) fp32 is the smoothed
+    distribution kept between calls.  One launch"""
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError(f"the logits must be fp32 (streams, classes), got {logits.dtype} {tuple(logits.shape)}")
+    S, N = logits.shape
+    if q.dtype != torch.float32 or tuple(q.shape) != (S, N):
+        raise ValueError(f"q must be fp32 {(S, N)}")
+    if state.dtype != torch.int64 or state.numel() < stream_state_words(S, log_capacity):
+        raise ValueError("the stream state must be int64 and stream_state_words(n_streams, log_capacity) long")
+    call("hwgat_stream_decide", ptr(state), ptr(q), ptr(logits), S, N, int(log_capacity), stream())
