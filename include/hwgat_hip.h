@@ -78,7 +78,9 @@ extern "C" {
  *         hwgat_gguard_{adamw,sgd,nadam}_{advance,step}; hwgat_opt_entry (64 bytes) is the only table record, and
  *         hwgat_gguard_{partial,scale} lose their record-size argument
  *         later additions under the same number (additions only, no existing signature changed):
- *         hwgat_stream_{state_bytes,push,window,decide}, ring-buffered keypoint streams for serve.StreamRecognizer */
+ *         hwgat_stream_{state_bytes,push,window,decide}, ring-buffered keypoint streams for serve.StreamRecognizer;
+ *         hwgat_loader_{state_bytes,select,draw}, the device-resident clip store's shuffle and augmentation draw for
+ *         data.DeviceLoader */
 #define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
@@ -841,6 +843,117 @@ int hwgat_stream_window(const float* ring, void* state, float* clip, int32_t* cl
                         int origin, int anchor0, int anchor1, const int32_t* hands, void* stream);
 int hwgat_stream_decide(void* state, float* q, const float* logits, int n_streams, int n_classes, int log_capacity,
                         void* stream);
+
+/* ---- device-resident clip store and train input pipeline (data.DeviceClipStore / data.DeviceLoader, csrc/loader.hip).
+ * The whole dataset lives on the device; "the next batch" is hwgat_loader_select -> hwgat_loader_draw ->
+ * hwgat_aug_hand_fill -> hwgat_aug_resample with no host input: every value that changes between batches is a DEVICE word,
+ * so the four launches replay as one HIP graph.  The shuffle and the augmentation draw are counter-based hashes of a
+ * device-resident seed, as dropout is.
+ *
+ * store (device memory, built once by the caller):
+ *   frames    (store_frames, J, C) fp32: all raw clips one after another, C in {2, 3}
+ *   clip_off  (n_clips + 1) int64 prefix sums of the clip lengths; every clip has 1..max_frames frames
+ *   labels    (n_clips) int64
+ *   norm      (n_clips, 4) fp32: left_top[0..2], edge_dist of NormalizeKeypoints (fp32 values computed once on the host from
+ *             the raw clip: the origin and anchor joints are never masked or hand-corrected)
+ * state: hwgat_loader_state_bytes() = 64 bytes of DEVICE memory, 8-byte aligned (hwgat_loader_state), written by the caller.
+ *   Every word is reduced to its range when a kernel reads it -- n_clips to [1, n_clips argument], batch to [1, batch
+ *   argument], world to [1, 2^20], rank to [0, world), cursor to [0, batches per epoch), clip ids to [0, n_clips), clip
+ *   offsets and lengths to the store, frame numbers to [0, T) -- so no word of device memory can move an address out of
+ *   the store or the batch buffers.
+ *
+ * hashes.  mix32(seed, pair) is the dropout hash of csrc/fused_ops.h (32-bit wrap-around arithmetic):
+ *     x = ((uint32)pair ^ seed) * 0x9E3779B1 + (uint32)(pair >> 32) * 0x85EBCA77;
+ *     x ^= x >> 15; x *= 0x2C1B3C6D; x ^= x >> 12; x *= 0x297A2D39; return x ^ (x >> 15).
+ *   feistel(K, n, x), a bijection of [0, 2^b): b = the smallest EVEN number >= 2 with 2^b >= n, h = b / 2, m = 2^h - 1;
+ *     (L, R) = (x >> h, x & m); for j = 0, 1, 2, 3: (L, R) = (R, L ^ (mix32(K + j, R) & m)); result (L << h) | R.
+ *   perm(K, n, x), a bijection of [0, n) for x in [0, n): n == 1: 0; else y = x; do y = feistel(K, n, y) while y >= n
+ *     (cycle walking).  2^b < 4 n (else b - 2 would do), so a step lands in [0, n) with probability > 1/4 and the expected
+ *     number of steps is below 4.  The walk is bounded by 2^b - n + 1 steps and falls through to y = x at the bound; the
+ *     bound is never reached: feistel is a bijection of [0, 2^b), so the walk runs along the cycle through x, which comes
+ *     back to x -- a point of [0, n) -- after visiting each other point at most once, and only 2^b - n points lie outside.
+ *   K_perm = mix32(seed, epoch)                                  (pair = epoch, high word 0)
+ *   K_row  = mix32(mix32(seed, 2^32 + epoch), id)                (pair = 2^32 + epoch, then pair = id): the draw key of clip
+ *            `id` in `epoch`.  It depends on (seed, epoch, id) only -- not on the batch size, the row or the rank.
+ *   hash(tag, i) = mix32(K_row + tag, i)  with the HWGAT_LOADER_TAG_* below (16 apart: a Feistel key uses tag .. tag + 3)
+ *   U(tag, i) = (hash(tag, i) + 0.5) / 2^32  in fp64 (exact), in (0, 1)
+ *   Z(tag, i) = sqrt(-2 ln U(tag, 2 i)) * cos(6.283185307179586 * U(tag, 2 i + 1))  (Box-Muller, fp64, each product rounded)
+ *   normal(loc, scale, tag, i) = loc + scale * Z(tag, i);  clip01(v) = min(max(v, 0), 1)
+ *
+ * hwgat_loader_select: ONE workgroup.  From the state words (reduced as above): flags bit 0 shuffle, bit 1 drop_last, bit 2
+ *   train.  per = drop_last ? n_clips / world : ceil(n_clips / world); nb0 = drop_last ? per / batch : ceil(per / batch);
+ *   batches per epoch nb = max(nb0, 1); limit = drop_last ? nb0 * batch * world : n_clips.  Row r < batch (state word) takes
+ *   sample s = (cursor * batch + r) * world + rank; s >= limit or r >= batch: the row is empty (id -1, key 0, no frames,
+ *   label 0).  Otherwise id = shuffle ? perm(K_perm, n_clips, s) : s.  It writes, for the `batch` ARGUMENT rows:
+ *     ids (batch) int32; keys (batch) uint32 = K_row; clip_len (batch) int32 = the clip's length (0 for an empty row);
+ *     batch_off (batch + 1) int32 prefix sums of clip_len (an LDS scan); y (batch) int64 = labels[id]; *n_rows = the number
+ *     of non-empty rows (they come first).
+ *   Then cursor += 1, and at cursor == nb: cursor = 0, epoch += 1.
+ * hwgat_loader_draw: one workgroup per row; T = the row's clip length, id / K_row its clip and key.  It writes
+ *   clip     (batch * max_frames, J, C) fp32: the clip's raw frames at frame batch_off[r]
+ *   masked   (batch * max_frames) uint8 at batch_off[r]: train: frame f is 1 iff perm(K_row + TAG_MASK, T, f) < int(mask_p * T)
+ *            (a uniformly random subset of int(mask_p T) frames, as sorted(random.sample(range(T), m))), else 0; eval: 0
+ *   prm      (batch, HWGAT_AUG_NPRM) fp64, the record hwgat_aug_resample takes: [0..3] = norm[id] (as doubles);
+ *            train: [4 + c] = clip01(normal(0.5, 0.1, TAG_SHEAR_ORIGIN, c)), [7] = normal(0, shear_std, TAG_SHEAR, 0),
+ *            [8 + c] = clip01(normal(0.5, 0.1, TAG_ROT_ORIGIN, c)) for c < C (0 beyond);
+ *            C = 2: a = normal(0, rotation_std, TAG_ROT, 0), M = [[cos a, -sin a, 0], [sin a, cos a, 0], [0, 0, 1]];
+ *            C = 3: angles t_k = normal(0, rotation_std, TAG_ROT, k) * 90 * 0.017453292519943295 (radians), k = 0, 1, 2,
+ *            M = Rz(t_2) Ry(t_1) Rx(t_0), extrinsic x-y-z (augment.euler_xyz_degrees):
+ *              [[c2 c1, c2 s1 s0 - s2 c0, c2 s1 c0 + s2 s0], [s2 c1, s2 s1 s0 + c2 c0, s2 s1 c0 - c2 s0], [-s1, c1 s0, c1 c0]];
+ *            [11 + 3 q + c] = M[q][c]; [20] = 1 iff hash(TAG_FLIP, 0) < 2^31; [21] = 1 iff L <= src_len (below); rest 0.
+ *            eval: zero origins and shear, M = I, no flip, [21] = (T <= src_len).  Empty row: [3] = 1, M = I, rest 0.
+ *   src      (batch, src_len) int32, the frame map src[i] = aug[m[i]] of TrainTransform.draw:
+ *            ratio = (ratio_hi - ratio_lo) * U(TAG_RATIO, 0) + ratio_lo and L = int(T * ratio): a separately rounded fp64
+ *            difference, product, sum and product (no FMA), L reduced to [1, 2 * HWGAT_AUG_MAX_FRAMES];
+ *            random = random_sample and hash(TAG_MODE, 0) < 2^31.
+ *            random, ratio <= 1: aug = the frames f with perm(K_row + TAG_SUBSET, T, f) < L in increasing order;
+ *            random, ratio > 1: the L draws (hash(TAG_CHOICE, i) * T) >> 32 (64-bit product), i < L, sorted;
+ *              (both: a count per frame in LDS -- integer atomics -- then an inclusive LDS scan; aug[j] is the first frame
+ *              whose cumulative count exceeds j)
+ *            else aug[j] = numpy.linspace(0, T - 1, L).astype(int)[j] = j == L - 1 ? T - 1 : int(j * ((T - 1) / (L - 1)))
+ *              (fp64 quotient and product, each rounded; L == 1: 0).
+ *            TemporalSample: L <= src_len: s = random_shift ? clip01(normal(0.5, 0.1, TAG_SHIFT, 0)) : 0.5,
+ *            start = int((src_len - L) * s) (a rounded fp64 product); m[i] = i - start for start <= i < start + L, else 0 for
+ *            i < src_len / 2 (integer division) and L - 1 behind; L > src_len: m[i] = linspace(0, L - 1, src_len).astype(int)[i].
+ *            eval: L = T, aug[j] = j, s = 0.5.  Empty row: zeros.
+ *   mask_p in (0, 1), 0 < ratio_lo <= ratio_hi <= 2 (so L <= 2 T), the standard deviations >= 0, else HWGAT_ESHAPE.
+ *   LDS: one int32 counter per frame for HWGAT_AUG_MAX_FRAMES = 4096 frames (16 KiB), 256 scan partials (1 KiB), the
+ *   normals and the record (0.4 KiB): under 18 KiB per workgroup.
+ * Both: batch <= HWGAT_LOADER_MAX_BATCH, n_clips <= 2^30, max_frames <= HWGAT_AUG_MAX_FRAMES, batch * max_frames < 2^31,
+ *   J <= 1024, src_len <= 2^20 (else HWGAT_ESHAPE).  No float atomics; every word has one writer; bit-reproducible.
+ * The packed clip, batch_off, masked, src and prm then go to hwgat_aug_hand_fill / hwgat_aug_resample unchanged, with
+ * n_clips = batch, total_frames = batch * max_frames (an empty row: the hand fill returns, the resampler writes zeros). */
+#define HWGAT_LOADER_MAX_BATCH 1024
+#define HWGAT_LOADER_SHUFFLE 1
+#define HWGAT_LOADER_DROP_LAST 2
+#define HWGAT_LOADER_TRAIN 4
+#define HWGAT_LOADER_TAG_MASK 0x10
+#define HWGAT_LOADER_TAG_SHEAR_ORIGIN 0x20
+#define HWGAT_LOADER_TAG_SHEAR 0x30
+#define HWGAT_LOADER_TAG_ROT_ORIGIN 0x40
+#define HWGAT_LOADER_TAG_ROT 0x50
+#define HWGAT_LOADER_TAG_RATIO 0x60
+#define HWGAT_LOADER_TAG_MODE 0x70
+#define HWGAT_LOADER_TAG_SUBSET 0x80
+#define HWGAT_LOADER_TAG_CHOICE 0x90
+#define HWGAT_LOADER_TAG_SHIFT 0xA0
+#define HWGAT_LOADER_TAG_FLIP 0xB0
+typedef struct {
+    uint32_t seed, epoch;
+    int32_t cursor, n_clips;                    /* batch within the epoch; clips in the store */
+    int32_t batch, rank;
+    int32_t world, flags;                       /* HWGAT_LOADER_SHUFFLE | _DROP_LAST | _TRAIN */
+    int64_t spare[4];
+} hwgat_loader_state;                           /* 64 bytes */
+int64_t hwgat_loader_state_bytes(void);
+int hwgat_loader_select(void* state, const int64_t* clip_off, const int64_t* labels, int32_t* ids, uint32_t* keys,
+                        int32_t* clip_len, int32_t* batch_off, int64_t* y, int32_t* n_rows, int n_clips,
+                        int64_t store_frames, int batch, int max_frames, void* stream);
+int hwgat_loader_draw(const void* state, const float* frames, const int64_t* clip_off, const float* norm,
+                      const int32_t* ids, const uint32_t* keys, const int32_t* batch_off, float* clip, uint8_t* masked,
+                      int32_t* src, double* prm, int n_clips, int64_t store_frames, int batch, int max_frames, int src_len,
+                      int J, int C, double mask_p, double ratio_lo, double ratio_hi, double shear_std, double rotation_std,
+                      int random_sample, int random_shift, void* stream);
 
 /* ---- Transformer baseline (ABI 4004; reference hwgat/models/Transformer.py).  Activations (B, T, d) with d = nH * 64.
  *

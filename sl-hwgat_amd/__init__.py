@@ -13,6 +13,7 @@ from . import checkpoint
 from . import augment
 from . import evaluate
 from . import optim
+from . import data
 from .parts import part_table
 from .models.HWGATE import Model
 from .models.HGATE import Model as HGATEModel
@@ -27,4 +28,4 @@ from .models.model_params import (HWGATEParams, HGATEParams, WGATEParams, GATEPa
 __all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
            "TransformerModel",
            "TransformerParams", "STGCNModel", "STGCNParams", "DecoupledGCNModel", "DecoupledGCNParams", "functional",
-           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim"]
+           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim", "data"]

@@ -147,6 +147,9 @@ _SIGS = {
     "hwgat_stream_push": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "hwgat_stream_window": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "hwgat_stream_decide": [_P, _P, _P, _I, _I, _I, _P],
+    "hwgat_loader_state_bytes": [],
+    "hwgat_loader_select": [_P] * 9 + [_I, _L, _I, _I, _P],
+    "hwgat_loader_draw": [_P] * 11 + [_I, _L, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _I, _I, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "linspace.h"
 
 namespace {
 
@@ -154,8 +155,7 @@ __global__ __launch_bounds__(WIN_THREADS) void stream_window_k(const float* __re
             m = (i >= st && i < st + L) ? i - st : (i < n / 2 ? 0 : L - 1);
         } else if (L > n && n > 1) {
             // numpy.linspace(0, L - 1, n).astype(int): arange(n) * ((L - 1) / (n - 1)) in fp64, the last entry L - 1
-            const double step = __ddiv_rn((double)(L - 1), (double)(n - 1));
-            m = i == n - 1 ? L - 1 : min((int)__dmul_rn((double)i, step), L - 1);
+            m = linspace_int(i, L - 1, n);
         }
         src[(int64_t)s * n + i] = m;
     }

@@ -1648,3 +1648,65 @@ def stream_decide(state, q, logits, log_capacity):
     if state.dtype != torch.int64 or state.numel() < stream_state_words(S, log_capacity):
         raise ValueError("the stream state must be int64 and stream_state_words(n_streams, log_capacity) long")
     call("hwgat_stream_decide", ptr(state), ptr(q), ptr(logits), S, N, int(log_capacity), stream())
+
+
+# ---------------------------------------------------------------- device-resident clip store (csrc/loader.hip, data.DeviceLoader)
+# The loader state is hwgat_loader_state of include/hwgat_hip.h: 8 int32 words and 4 spare int64 words, kept as int64 words.
+LOADER_STATE_WORDS = 8
+LOADER_MAX_BATCH = 1024                        # HWGAT_LOADER_MAX_BATCH
+LOADER_SHUFFLE, LOADER_DROP_LAST, LOADER_TRAIN = 1, 2, 4
+
+
+def _loader_store(state, frames, clip_off):
+    if state.dtype != torch.int64 or state.numel() < LOADER_STATE_WORDS:
+        raise ValueError(f"the loader state must be int64 with {LOADER_STATE_WORDS} words")
+    if frames.dtype != torch.float32 or frames.dim() != 3:
+        raise ValueError(f"the store's frames must be fp32 (store_frames, J, C), got {frames.dtype} {tuple(frames.shape)}")
+    if clip_off.dtype != torch.int64 or clip_off.dim() != 1 or clip_off.numel() < 2:
+        raise ValueError("the store's clip_off must be int64 (n_clips + 1)")
+    return clip_off.numel() - 1
+
+
+def loader_select(state, frames, clip_off, labels, ids, keys, clip_len, batch_off, y, n_rows, max_frames):
+    """the next batch's rows from the loader state: ids / keys / clip_len (B) int32, batch_off (B + 1) int32, y (B) int64,
+    n_rows (1) int32; moves the cursor (and the epoch) in `state`.  One launch; nothing is read back"""
+    n = _loader_store(state, frames, clip_off)
+    B = ids.numel()
+    if labels.dtype != torch.int64 or labels.numel() != n:
+        raise ValueError(f"labels must be int64 with {n} elements")
+    for name, t in (("ids", ids), ("keys", keys), ("clip_len", clip_len)):
+        if t.dtype != torch.int32 or t.numel() != B:
+            raise ValueError(f"{name} must be int32 with {B} elements")
+    if batch_off.dtype != torch.int32 or batch_off.numel() != B + 1:
+        raise ValueError(f"batch_off must be int32 with {B + 1} elements")
+    if y.dtype != torch.int64 or y.numel() != B:
+        raise ValueError(f"y must be int64 with {B} elements")
+    if n_rows.dtype != torch.int32 or n_rows.numel() != 1:
+        raise ValueError("n_rows must be one int32 word")
+    call("hwgat_loader_select", ptr(state), ptr(clip_off), ptr(labels), ptr(ids), ptr(keys), ptr(clip_len), ptr(batch_off),
+         ptr(y), ptr(n_rows), n, frames.shape[0], B, int(max_frames), stream())
+
+
+def loader_draw(state, frames, clip_off, norm, ids, keys, batch_off, clip, masked, src, prm, max_frames, mask_p, ratio,
+                shear_std, rotation_std, random_sample, random_shift):
+    """the selected rows' raw frames into the packed clip (B * max_frames, J, C), the masked bytes (B * max_frames) uint8,
+    the frame map src (B, src_len) int32 and the parameter records prm (B, 24) fp64 that hand_fill / resample take.  One
+    launch"""
+    n = _loader_store(state, frames, clip_off)
+    B, (_, J, C) = ids.numel(), frames.shape
+    if norm.dtype != torch.float32 or tuple(norm.shape) != (n, 4):
+        raise ValueError(f"norm must be fp32 ({n}, 4)")
+    if clip.dtype != torch.float32 or clip.numel() < B * int(max_frames) * J * C:
+        raise ValueError(f"the clip buffer must hold fp32 ({B} * {max_frames}, {J}, {C})")
+    if masked.dtype != torch.uint8 or masked.numel() < B * int(max_frames):
+        raise ValueError(f"the masked bytes must be uint8 with {B} * {max_frames} elements")
+    if src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != B:
+        raise ValueError(f"the frame map must be int32 ({B}, src_len)")
+    if prm.dtype != torch.float64 or tuple(prm.shape) != (B, STREAM_NPRM):
+        raise ValueError(f"the parameter records must be fp64 ({B}, {STREAM_NPRM})")
+    if keys.dtype != torch.int32 or keys.numel() != B or batch_off.dtype != torch.int32 or batch_off.numel() != B + 1:
+        raise ValueError(f"keys must be int32 ({B}) and batch_off int32 ({B + 1})")
+    call("hwgat_loader_draw", ptr(state), ptr(frames), ptr(clip_off), ptr(norm), ptr(ids), ptr(keys), ptr(batch_off),
+         ptr(clip), ptr(masked), ptr(src), ptr(prm), n, frames.shape[0], B, int(max_frames), src.shape[1], J, C,
+         float(mask_p), float(ratio[0]), float(ratio[1]), float(shear_std), float(rotation_std), int(bool(random_sample)),
+         int(bool(random_shift)), stream())
