@@ -4,7 +4,8 @@
 // aggregation  hwgat_dgcn_agg_fwd / _bwd: the per-channel-group adjacency product.  A workgroup serves ONE group g
 //              (blockIdx.y): its three V x V matrices sit in LDS (12 KiB, whatever G is) and its threads walk the
 //              (frame, channel c = j G + g) pairs, the V outputs of a pair in registers.  d An through per-block images
-//              added in block order (16 phases of every 16th image, then the phases).
+//              added in block order (16 phases of every 16th image, then the phases).  The kernels are gcn_agg.h's,
+//              shared with stgcn_ops.hip; this file states the matrix source (GroupTable) and the cap on block images.
 // gates        hwgat_dgcn_gate_sum: the squeezes (and, in the backward, the gate gradients) as sums over t or over v with
 //              the gate factors applied while reading; 64 channels x 4 phases per workgroup, phases added in order.
 //              hwgat_dgcn_gate_apply / _bwd: element-wise.
@@ -14,131 +15,20 @@
 // No kernel here uses an atomic.
 #include "common.h"
 #include "fused_ops.h"
+#include "gcn_agg.h"
 
 namespace {
 
-constexpr int VMAX = 32;
-constexpr int DA_BLOCKS = 128;      // frame chunks of the d An kernel (times G workgroups)
-constexpr int FIN_PH = 16;
+constexpr int DA_BLOCKS = 128;      // cap on the frame chunks of d An (times G workgroups)
 
-inline int grid1(int64_t n) { return (int)((n + 255) / 256); }
-
-__device__ __forceinline__ void load_group(float* As, const float* __restrict__ An, int g, int G, int V) {
-    for (int q = threadIdx.x; q < 3 * VMAX * VMAX; q += 256) {
-        const int k = q / (VMAX * VMAX), v = (q / VMAX) % VMAX, w = q % VMAX;
-        As[q] = (v < V && w < V) ? An[(((int64_t)k * G + g) * V + v) * V + w] : 0.f;
-    }
-}
-
-// TRANS 0: out[f, w, c] = sum_{k, v} An[k, g, v, w] y[f, v, k C + c];  TRANS 1: dy[f, v, k C + c] = sum_w An[k, g, v, w] d[f, w, c]
-template <int TRANS>
-__global__ __launch_bounds__(256) void agg_k(const float* __restrict__ src, const float* __restrict__ An,
-                                              float* __restrict__ dst, int64_t NT, int V, int C, int G) {
-    __shared__ float As[3 * VMAX * VMAX];
-    const int g = blockIdx.y, J = C / G;
-    load_group(As, An, g, G, V);
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= NT * J) return;
-    const int64_t f = i / J;
-    const int c = (int)(i % J) * G + g;
-    if (TRANS == 0) {
-        float acc[VMAX];
-#pragma unroll
-        for (int w = 0; w < VMAX; ++w) acc[w] = 0.f;
-        const float* yp = src + f * V * 3 * C + c;
-        for (int k = 0; k < 3; ++k)
-            for (int v = 0; v < V; ++v) {
-                const float val = yp[((int64_t)v * 3 + k) * C];
-                const float* ar = As + (k * VMAX + v) * VMAX;
-#pragma unroll
-                for (int w = 0; w < VMAX; ++w) acc[w] = fmaf(ar[w], val, acc[w]);
-            }
-        float* op = dst + f * V * C + c;
-#pragma unroll
-        for (int w = 0; w < VMAX; ++w)
-            if (w < V) op[(int64_t)w * C] = acc[w];
-    } else {
-        float d[VMAX];
-        const float* dp = src + f * V * C + c;
-#pragma unroll
-        for (int w = 0; w < VMAX; ++w) d[w] = w < V ? dp[(int64_t)w * C] : 0.f;
-        float* op = dst + f * V * 3 * C + c;
-        for (int k = 0; k < 3; ++k)
-            for (int v = 0; v < V; ++v) {
-                const float* ar = As + (k * VMAX + v) * VMAX;
-                float s = 0.f;
-#pragma unroll
-                for (int w = 0; w < VMAX; ++w) s = fmaf(ar[w], d[w], s);
-                op[((int64_t)v * 3 + k) * C] = s;
-            }
-    }
-}
-
-// ws[b][g][k][v][w] (32 x 32 slots) = sum over block b's frames and the channels of group g of y[f, v, k C + c] d[f, w, c]
-__global__ __launch_bounds__(256) void agg_da_k(const float* __restrict__ y, const float* __restrict__ d,
-                                                 float* __restrict__ ws, int64_t NT, int V, int C, int G, int64_t fpb) {
-    __shared__ float Ys[VMAX][3][33];
-    __shared__ float Ds[VMAX][33];
-    const int tid = threadIdx.x, v = tid & 31, wq = tid >> 5;
-    const int g = blockIdx.y, J = C / G;
-    float acc[3][4];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[k][j] = 0.f;
-    const int64_t f0 = (int64_t)blockIdx.x * fpb, f1 = min(NT, f0 + fpb);
-    for (int64_t f = f0; f < f1; ++f)
-        for (int j0 = 0; j0 < J; j0 += 32) {
-            const int jn = min(32, J - j0);
-            __syncthreads();
-            for (int q = tid; q < VMAX * 3 * 32; q += 256) {
-                const int cc = q & 31, k = (q >> 5) % 3, vv = q / 96;
-                Ys[vv][k][cc] = (vv < V && cc < jn) ? y[((f * V + vv) * 3 + k) * C + (int64_t)(j0 + cc) * G + g] : 0.f;
-            }
-            for (int q = tid; q < VMAX * 32; q += 256) {
-                const int cc = q & 31, ww = q >> 5;
-                Ds[ww][cc] = (ww < V && cc < jn) ? d[(f * V + ww) * C + (int64_t)(j0 + cc) * G + g] : 0.f;
-            }
-            __syncthreads();
-            for (int cc = 0; cc < jn; ++cc) {
-                float dv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dv[j] = Ds[wq * 4 + j][cc];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float yv = Ys[v][k][cc];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[k][j] = fmaf(yv, dv[j], acc[k][j]);
-                }
-            }
-        }
-    float* img = ws + ((int64_t)blockIdx.x * G + g) * 3 * VMAX * VMAX;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) img[(k * VMAX + v) * VMAX + wq * 4 + j] = acc[k][j];
-}
-
-// dAn[k, g, v, w] = the sum over the P block images: FIN_PH phases of every FIN_PH-th image, added in phase order
-__global__ __launch_bounds__(64 * FIN_PH) void agg_da_reduce_k(const float* __restrict__ ws, int P, float* __restrict__ dAn,
-                                                                int V, int G) {
-    __shared__ float red[FIN_PH][64];
-    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + cl;
-    const bool live = i < 3 * G * V * V;
-    float s = 0.f;
-    if (live) {
-        const int w = i % V, v = (i / V) % V, g = (i / (V * V)) % G, k = i / (V * V * G);
-        for (int p = ph; p < P; p += FIN_PH)
-            s += ws[((int64_t)p * G + g) * 3 * VMAX * VMAX + (k * VMAX + v) * VMAX + w];
-    }
-    red[ph][cl] = s;
-    __syncthreads();
-    if (ph != 0 || !live) return;
-    for (int q = 1; q < FIN_PH; ++q) s += red[q][cl];
-    dAn[i] = s;
-}
+// the DecoupledGCN matrix source of gcn_agg.h: M[k, g] = An[k, g] of (3, G, V, V); the gradient is the image sum itself
+struct GroupTable {
+    static constexpr bool kGrouped = true;
+    const float* An;
+    int G;
+    __device__ float at(int k, int g, int v, int w, int V) const { return An[(((int64_t)k * G + g) * V + v) * V + w]; }
+    __device__ float grad(int, float s) const { return s; }
+};
 
 // AXIS 0: out[n, v, c] = scale sum_t val;  AXIS 1: out[n, t, c] = scale sum_v val
 // val = h (g' (1 + sv[n, v]) (1 + st[n, t]) (1 + sc[n, c]) + m[n, t, c] m_scale)
@@ -340,13 +230,13 @@ extern "C" int hwgat_dgcn_agg_fwd(const float* y, const float* An, float* out, i
                                   void* stream) {
     if (!y || !An || !out || NT <= 0 || C <= 0 || V <= 0 || G <= 0) return HWGAT_EINVAL;
     if (V > VMAX || C % G || G > 65535 || NT * (C / G) / 256 > 0x7fffffff) return HWGAT_ESHAPE;
-    agg_k<0><<<dim3(grid1(NT * (C / G)), G), 256, 0, (hipStream_t)stream>>>(y, An, out, NT, V, C, G);
+    agg_launch<0>(y, GroupTable{An, G}, out, NT, V, C, G, (hipStream_t)stream);
     HWGAT_LAUNCH_CHECK();
 }
 
 extern "C" int64_t hwgat_dgcn_agg_bwd_bytes(int64_t NT, int G) {
     if (NT <= 0 || G <= 0) return -1;
-    return (int64_t)(NT < DA_BLOCKS ? NT : DA_BLOCKS) * G * 3 * VMAX * VMAX * 4;
+    return agg_bwd_bytes(NT, G, DA_BLOCKS);
 }
 
 extern "C" int hwgat_dgcn_agg_bwd(const float* y, const float* d, const float* An, float* dy, float* dAn, int64_t NT, int V,
@@ -354,15 +244,7 @@ extern "C" int hwgat_dgcn_agg_bwd(const float* y, const float* d, const float* A
     if (!y || !d || !An || !dy || NT <= 0 || C <= 0 || V <= 0 || G <= 0) return HWGAT_EINVAL;
     if (dAn && (!ws || ws_bytes < hwgat_dgcn_agg_bwd_bytes(NT, G))) return HWGAT_EINVAL;
     if (V > VMAX || C % G || G > 65535 || NT * (C / G) / 256 > 0x7fffffff) return HWGAT_ESHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    agg_k<1><<<dim3(grid1(NT * (C / G)), G), 256, 0, st>>>(d, An, dy, NT, V, C, G);
-    if (dAn) {
-        int P = (int)(NT < DA_BLOCKS ? NT : DA_BLOCKS);
-        const int64_t fpb = (NT + P - 1) / P;
-        P = (int)((NT + fpb - 1) / fpb);
-        agg_da_k<<<dim3(P, G), 256, 0, st>>>(y, d, ws, NT, V, C, G, fpb);
-        agg_da_reduce_k<<<(3 * G * V * V + 63) / 64, 64 * FIN_PH, 0, st>>>(ws, P, dAn, V, G);
-    }
+    agg_bwd_launch(y, d, GroupTable{An, G}, dy, dAn, NT, V, C, G, DA_BLOCKS, ws, (hipStream_t)stream);
     HWGAT_LAUNCH_CHECK();
 }
 

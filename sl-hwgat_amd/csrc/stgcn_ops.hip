@@ -9,17 +9,19 @@
 //              same two levels, then dx; d gamma / d beta written.
 // aggregation  hwgat_stgcn_agg_fwd: out[f, w, c] = sum_{k,v} Ae[k, v, w] y[f, v, k C + c], Ae = A o edge_importance built
 //              in LDS; one thread per (frame, channel), the V outputs in registers.  hwgat_stgcn_agg_bwd: the transposed
-//              product for dy and the (3, V, V) gradient through per-block images added in block order.
+//              product for dy and the (3, V, V) gradient through per-block images added in block order.  The kernels are
+//              gcn_agg.h's, shared with dgcn_ops.hip, at one group; this file states the matrix source (EdgeWeighted)
+//              and the cap on block images.
 // pool         mean over the T V rows of a clip, head dropout fused (mask index n C + c), and its backward.
 // No kernel here uses an atomic: every cross-block sum is a fixed-order sum of partial images.
 #include "common.h"
 #include "fused_ops.h"
+#include "gcn_agg.h"
 
 namespace {
 
 constexpr int RED_BLOCKS = 256;      // partial images of a column reduction
-constexpr int VMAX = 32;
-constexpr int AGG_BLOCKS = 512;
+constexpr int AGG_BLOCKS = 512;      // cap on the block images of d edge_importance
 
 enum { RED_STATS = 0, RED_BWD = 1, RED_SUM = 2 };
 
@@ -68,8 +70,6 @@ __global__ __launch_bounds__(256) void colred_k(const float* __restrict__ x, con
 // Second level of a column reduction: one workgroup per 64 columns, FIN_PH phases each adding every FIN_PH-th partial
 // image in double, the phases then added in phase order -- a fixed order, so the sums are bit-reproducible.  Returns
 // true in the one thread per column that holds the two sums.
-constexpr int FIN_PH = 16;
-
 __device__ __forceinline__ bool fin_sums(const float* __restrict__ ws, int P, int C, int& c, double& s1, double& s2) {
     __shared__ double red[FIN_PH][64][2];
     const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
@@ -169,125 +169,17 @@ __global__ __launch_bounds__(256) void bn_eval_stats_k(const float* __restrict__
     rstd[c] = (float)(1.0 / sqrt((double)rv[c] + (double)eps));
 }
 
-__device__ __forceinline__ void load_ae(float* Ae, const float* A, const float* E, int V) {
-    for (int q = threadIdx.x; q < 3 * VMAX * VMAX; q += 256) {
-        const int k = q / (VMAX * VMAX), v = (q / VMAX) % VMAX, w = q % VMAX;
-        float a = 0.f;
-        if (v < V && w < V) {
-            const int i = (k * V + v) * V + w;
-            a = A[i] * (E ? E[i] : 1.f);
-        }
-        Ae[q] = a;
+// the ST-GCN matrix source of gcn_agg.h: M = A o edge_importance (E null: ones), one group; the gradient is dE = A . s
+struct EdgeWeighted {
+    static constexpr bool kGrouped = false;
+    const float* A;
+    const float* E;
+    __device__ float at(int k, int, int v, int w, int V) const {
+        const int i = (k * V + v) * V + w;
+        return A[i] * (E ? E[i] : 1.f);
     }
-}
-
-// TRANS 0: out[f, w, c] = sum_{k, v} Ae[k, v, w] y[f, v, k C + c];  TRANS 1: dy[f, v, k C + c] = sum_w Ae[k, v, w] d[f, w, c]
-template <int TRANS>
-__global__ __launch_bounds__(256) void agg_k(const float* __restrict__ src, const float* __restrict__ A,
-                                              const float* __restrict__ E, float* __restrict__ dst, int64_t NT, int V,
-                                              int C) {
-    __shared__ float Ae[3 * VMAX * VMAX];
-    load_ae(Ae, A, E, V);
-    __syncthreads();
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= NT * C) return;
-    const int64_t f = g / C;
-    const int c = (int)(g % C);
-    if (TRANS == 0) {
-        float acc[VMAX];
-#pragma unroll
-        for (int w = 0; w < VMAX; ++w) acc[w] = 0.f;
-        const float* yp = src + f * V * 3 * C + c;
-        for (int k = 0; k < 3; ++k)
-            for (int v = 0; v < V; ++v) {
-                const float val = yp[((int64_t)v * 3 + k) * C];
-                const float* ar = Ae + (k * VMAX + v) * VMAX;
-#pragma unroll
-                for (int w = 0; w < VMAX; ++w) acc[w] = fmaf(ar[w], val, acc[w]);
-            }
-        float* op = dst + f * V * C + c;
-#pragma unroll
-        for (int w = 0; w < VMAX; ++w)
-            if (w < V) op[(int64_t)w * C] = acc[w];
-    } else {
-        float d[VMAX];
-        const float* dp = src + f * V * C + c;
-#pragma unroll
-        for (int w = 0; w < VMAX; ++w) d[w] = w < V ? dp[(int64_t)w * C] : 0.f;
-        float* op = dst + f * V * 3 * C + c;
-        for (int k = 0; k < 3; ++k)
-            for (int v = 0; v < V; ++v) {
-                const float* ar = Ae + (k * VMAX + v) * VMAX;
-                float s = 0.f;
-#pragma unroll
-                for (int w = 0; w < VMAX; ++w) s = fmaf(ar[w], d[w], s);
-                op[((int64_t)v * 3 + k) * C] = s;
-            }
-    }
-}
-
-// ws[b][k][v][w] (32 x 32 slots) = sum over block b's frames and all channels of y[f, v, k C + c] d[f, w, c]
-__global__ __launch_bounds__(256) void agg_da_k(const float* __restrict__ y, const float* __restrict__ d,
-                                                 float* __restrict__ ws, int64_t NT, int V, int C, int64_t fpb) {
-    __shared__ float Ys[VMAX][3][33];
-    __shared__ float Ds[VMAX][33];
-    const int tid = threadIdx.x, v = tid & 31, wq = tid >> 5;
-    float acc[3][4];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[k][j] = 0.f;
-    const int64_t f0 = (int64_t)blockIdx.x * fpb, f1 = min(NT, f0 + fpb);
-    for (int64_t f = f0; f < f1; ++f)
-        for (int c0 = 0; c0 < C; c0 += 32) {
-            __syncthreads();
-            for (int q = tid; q < VMAX * 3 * 32; q += 256) {
-                const int cc = q & 31, k = (q >> 5) % 3, vv = q / 96;
-                Ys[vv][k][cc] = vv < V ? y[((f * V + vv) * 3 + k) * C + c0 + cc] : 0.f;
-            }
-            for (int q = tid; q < VMAX * 32; q += 256) {
-                const int cc = q & 31, ww = q >> 5;
-                Ds[ww][cc] = ww < V ? d[(f * V + ww) * C + c0 + cc] : 0.f;
-            }
-            __syncthreads();
-#pragma unroll 4
-            for (int cc = 0; cc < 32; ++cc) {
-                float dv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dv[j] = Ds[wq * 4 + j][cc];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float yv = Ys[v][k][cc];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[k][j] = fmaf(yv, dv[j], acc[k][j]);
-                }
-            }
-        }
-    float* img = ws + (int64_t)blockIdx.x * 3 * VMAX * VMAX;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) img[(k * VMAX + v) * VMAX + wq * 4 + j] = acc[k][j];
-}
-
-// dE[k, v, w] = A[k, v, w] * sum over the block images: FIN_PH phases of every FIN_PH-th image, added in phase order
-__global__ __launch_bounds__(64 * FIN_PH) void agg_da_reduce_k(const float* __restrict__ ws, int P,
-                                                                const float* __restrict__ A, float* __restrict__ dE, int V) {
-    __shared__ float red[FIN_PH][64];
-    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + cl;
-    const bool live = i < 3 * V * V;
-    float s = 0.f;
-    if (live) {
-        const int w = i % V, v = (i / V) % V, k = i / (V * V);
-        for (int p = ph; p < P; p += FIN_PH) s += ws[(int64_t)p * 3 * VMAX * VMAX + (k * VMAX + v) * VMAX + w];
-    }
-    red[ph][cl] = s;
-    __syncthreads();
-    if (ph != 0 || !live) return;
-    for (int q = 1; q < FIN_PH; ++q) s += red[q][cl];
-    dE[i] = A[i] * s;
-}
+    __device__ float grad(int i, float s) const { return A[i] * s; }
+};
 
 __global__ __launch_bounds__(256) void pool_fwd_k(const float* __restrict__ x, float* __restrict__ out, int R, int C,
                                                    uint32_t seed, float p, const uint32_t* seed_base) {
@@ -340,8 +232,6 @@ int red_launch(int mode, const float* x, const float* dy, const float* y, const 
     else colred_k<RED_SUM><<<grid, 256, 0, st>>>(x, dy, y, mean, rstd, ws, M, C, chunk);
     return P;
 }
-
-inline int grid1(int64_t n) { return (int)((n + 255) / 256); }
 
 }  // namespace
 
@@ -410,13 +300,13 @@ extern "C" int hwgat_stgcn_agg_fwd(const float* y, const float* A, const float* 
                                    void* stream) {
     if (!y || !A || !out || NT <= 0 || C <= 0) return HWGAT_EINVAL;
     if (V <= 0 || V > VMAX || NT * C / 256 > 0x7fffffff) return HWGAT_ESHAPE;
-    agg_k<0><<<grid1(NT * C), 256, 0, (hipStream_t)stream>>>(y, A, E, out, NT, V, C);
+    agg_launch<0>(y, EdgeWeighted{A, E}, out, NT, V, C, 1, (hipStream_t)stream);
     HWGAT_LAUNCH_CHECK();
 }
 
 extern "C" int64_t hwgat_stgcn_agg_bwd_bytes(int64_t NT) {
     if (NT <= 0) return -1;
-    return (int64_t)(NT < AGG_BLOCKS ? NT : AGG_BLOCKS) * 3 * VMAX * VMAX * 4;
+    return agg_bwd_bytes(NT, 1, AGG_BLOCKS);
 }
 
 extern "C" int hwgat_stgcn_agg_bwd(const float* y, const float* d, const float* A, const float* E, float* dy, float* dE,
@@ -424,15 +314,7 @@ extern "C" int hwgat_stgcn_agg_bwd(const float* y, const float* d, const float* 
     if (!y || !d || !A || !dy || NT <= 0 || C <= 0) return HWGAT_EINVAL;
     if (dE && (!ws || ws_bytes < hwgat_stgcn_agg_bwd_bytes(NT))) return HWGAT_EINVAL;
     if (V <= 0 || V > VMAX || C % 32 || NT * C / 256 > 0x7fffffff) return HWGAT_ESHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    agg_k<1><<<grid1(NT * C), 256, 0, st>>>(d, A, E, dy, NT, V, C);
-    if (dE) {
-        int P = (int)(NT < AGG_BLOCKS ? NT : AGG_BLOCKS);
-        const int64_t fpb = (NT + P - 1) / P;
-        P = (int)((NT + fpb - 1) / fpb);
-        agg_da_k<<<P, 256, 0, st>>>(y, d, ws, NT, V, C, fpb);
-        agg_da_reduce_k<<<(3 * V * V + 63) / 64, 64 * FIN_PH, 0, st>>>(ws, P, A, dE, V);
-    }
+    agg_bwd_launch(y, d, EdgeWeighted{A, E}, dy, dE, NT, V, C, 1, AGG_BLOCKS, ws, (hipStream_t)stream);
     HWGAT_LAUNCH_CHECK();
 }
 

@@ -31,7 +31,7 @@ rows goes through partial images added in a fixed order: two backward runs are b
 import torch
 
 from . import functional as HF
-from .stgcn_block import _bn_stats, RES_IDENTITY, RES_CONV
+from .stgcn_block import _bn_stats, pad_channels, project, residual_forward, crop_dx, RES_IDENTITY, RES_CONV
 
 TCN_DROP_BLOCK = 41      # the reference's TCNUnit builds its temporal DropGraph with the default block size, always
 
@@ -93,10 +93,9 @@ class _Unit(torch.autograd.Function):
                 wt, bt, g2, b2, wr, br, gr, ber):
         groups, stride, res, training, bn0, bn1, bnd, bn2, bnr, drop = cfg
         N, T, V, Cin = x.shape
-        CinP = HF.pad32(Cin)
-        xp = x if CinP == Cin else HF.stgcn_copy_cols(x, CinP)
-        wg = _linear_master(lw)
-        y = HF.stgcn_conv(xp, HF.stgcn_weight_image(wg, 0, CinP), lb.reshape(-1).contiguous())
+        xp = pad_channels(x)
+        CinP = xp.shape[3]
+        y = project(xp, _linear_master(lw), lb.reshape(-1).contiguous())
         m0, r0 = _bn_stats(y, bn0, training)
         yb = HF.stgcn_bn_apply(y, m0, r0, g0, b0, relu=False)
         a = HF.dgcn_aggregate(yb, An, groups)
@@ -116,14 +115,8 @@ class _Unit(torch.autograd.Function):
         h3 = HF.dgcn_gate_apply(h, s_v, s_t, s_c)
         c = HF.stgcn_conv(h3, HF.stgcn_weight_image(wt, 0), bt, stride, wt.shape[2] // 2)
         m2, r2 = _bn_stats(c, bn2, training)
-        rc = mr = rr = None
-        r, rbn = None, None
-        if res == RES_CONV:
-            rc = HF.stgcn_conv(xp, HF.stgcn_weight_image(wr, 0, CinP), br, stride, 0)
-            mr, rr = _bn_stats(rc, bnr, training)
-            r, rbn = rc, (mr, rr, gr, ber)
-        elif res == RES_IDENTITY:
-            r = x
+        r, rbn = residual_forward(res, x, xp, wr, br, gr, ber, bnr, stride, training)
+        rc, mr, rr = (r, rbn[0], rbn[1]) if rbn else (None, None, None)
         fs1 = ft1 = fs2 = ft2 = None
         if drop is not None:
             A, keep_prob, drop_size, block, seeds, seed_base, injected, tap, unit = drop
@@ -208,9 +201,7 @@ class _Unit(torch.autograd.Function):
         d_lw = HF.stgcn_conv_dw(xp, dy, wg.shape, 1, 0).view(wg.shape[0], wg.shape[1]).t().contiguous()
         d_lb = HF.stgcn_colsum(dy).view(1, -1, 1, 1)
         dx = HF.stgcn_conv_dx(dy, HF.stgcn_weight_image(wg, 1, CinP), T, 1, 0, add=add, mask=mask)
-        if CinP != Cin:
-            dx = HF.stgcn_copy_cols(dx, Cin)
-        return (dx, None, dAn, d_lw, d_lb, d_g0, d_b0, d_g1, d_b1, d_wd, d_bd, d_gd, d_bed, d_w_sa, d_b_sa, d_w_ta, d_b_ta,
+        return (crop_dx(dx, Cin), None, dAn, d_lw, d_lb, d_g0, d_b0, d_g1, d_b1, d_wd, d_bd, d_gd, d_bed, d_w_sa, d_b_sa, d_w_ta, d_b_ta,
                 d_w1, d_bc1, d_w2, d_bc2, d_wt, d_bt, d_g2, d_b2, d_wr, d_br, d_gr, d_ber)
 
 

@@ -1043,7 +1043,7 @@ STGCN_MAX_NODES = 32
 
 def _ws(nbytes, device):
     if nbytes <= 0:
-        raise NotImplementedError("shape not supported by the ST-GCN kernels")
+        raise NotImplementedError("shape not supported by the GCN baselines' kernels")
     return torch.empty(nbytes // 4, device=device, dtype=torch.float32), nbytes
 
 

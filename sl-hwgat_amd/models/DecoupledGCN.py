@@ -39,38 +39,28 @@ import numpy as np
 import torch
 from torch import nn
 
-from .. import functional as HF
-from ..seeding import DeviceSeeds
-from ..stgcn_block import batch_norm_rows, mean_pool, RES_NONE, RES_IDENTITY, RES_CONV
+from ..stgcn_block import RES_NONE, RES_IDENTITY, RES_CONV
 from ..dgcn_block import dgcn_unit
+from ._gcn import (GCNModel, Head, TEMPORAL_TAPS, HEAD_SITE, width_plan, stem_problem, width_problem,  # noqa: F401
+                   edge_problem)
 
-TEMPORAL_TAPS = 9
-HEAD_SITE = 0          # the head dropout's site: _site_seeds(0)[0]; unit N (1..10) draws with _site_seeds(N)
-FIRST_DROP_UNIT = 7    # l1-l6 run at keep_prob 1
+FIRST_DROP_UNIT = 7    # l1-l6 run at keep_prob 1; unit N (1..10) draws with _site_seeds(N), the head with HEAD_SITE
 
 
 def shape_problem(in_channels, num_nodes, edges, groups, block_size, n_out_features, batch_norm):
     """None, or the message naming the rule a configuration breaks"""
-    if batch_norm:
-        return ("batch_norm=True: the reference's head fails on it (FC reads self.n_features before it exists), so there "
-                "is no behaviour to reproduce; the DecoupledGCN backend takes batch_norm=False only")
-    if not 1 <= in_channels <= 4:
-        return f"in_channels {in_channels}: the DecoupledGCN backend takes 1 to 4 coordinates per joint"
-    if not 1 <= num_nodes <= HF.STGCN_MAX_NODES:
-        return f"num_nodes {num_nodes}: the graph aggregation kernels take at most {HF.STGCN_MAX_NODES} joints"
+    problem = stem_problem("DecoupledGCN", in_channels, num_nodes, batch_norm)
+    if problem is not None:
+        return problem
     if groups < 1 or 64 % groups:
         return f"groups {groups}: must divide 64, the narrowest unit's width"
     if block_size < 1 or block_size % 2 == 0:
         return (f"block_size {block_size}: must be odd (the reference's max-pool widening returns T + 1 frames for an even "
                 f"block and fails)")
-    if n_out_features <= 0 or n_out_features % 64 or n_out_features > 1024:
-        return f"n_out_features {n_out_features}: the DecoupledGCN backend takes multiples of 64 up to 1024"
-    if edges is None:
-        return "edges None: an edge list is required for the decoupled GCN"
-    for e in edges:
-        if len(e) != 2 or not (0 <= e[0] < num_nodes and 0 <= e[1] < num_nodes):
-            return f"edge {list(e)}: not a pair of joints of a {num_nodes}-joint graph"
-    return None
+    problem = width_problem("DecoupledGCN", n_out_features)
+    if problem is None and edges is None:
+        problem = "edges None: an edge list is required for the decoupled GCN"
+    return problem or edge_problem(num_nodes, edges)
 
 
 def spatial_graph(num_nodes, edges):
@@ -182,79 +172,45 @@ class Unit(nn.Module):
         nn.init.constant_(self.fc2c.bias, 0)
 
 
-class Head(nn.Module):
-    """the reference's FC head: dropout (fused into the pool kernel here) and `classifier`"""
+class Model(GCNModel):
+    _backend = "DecoupledGCN"
+    _bf16_needs = "the BatchNorm statistics and the DropGraph statistics"
 
-    def __init__(self, n_features, num_class, dropout_ratio):
-        super().__init__()
-        self.dropout_ratio = float(dropout_ratio)
-        self.classifier = nn.Linear(n_features, num_class)
-        nn.init.normal_(self.classifier.weight, 0, math.sqrt(2.0 / num_class))
-
-
-class Model(DeviceSeeds, nn.Module):
     def __init__(self, in_channels=2, num_nodes=29, edges=None, groups=8, block_size=41, n_out_features=256, n_classes=1000,
                  dropout_ratio=0.1, batch_norm=False):
-        super().__init__()
-        problem = shape_problem(in_channels, num_nodes, edges, groups, block_size, n_out_features, batch_norm)
-        if problem is not None:
-            raise NotImplementedError(problem)
-        if not 0.0 <= float(dropout_ratio) < 1.0:
-            raise ValueError(f"dropout_ratio {dropout_ratio}: must be in [0, 1)")
-        self.in_channels, self.num_nodes, self.n_out_features = in_channels, num_nodes, n_out_features
+        super().__init__(shape_problem(in_channels, num_nodes, edges, groups, block_size, n_out_features, batch_norm),
+                         in_channels, num_nodes, n_out_features, dropout_ratio)
         self.groups, self.block_size = groups, block_size
         self.drop_size = find_drop_size(num_nodes, len(edges))
         A = spatial_graph(num_nodes, edges)
         self.data_bn = nn.BatchNorm1d(in_channels * num_nodes)
-        widths = [(in_channels, 64, 1), (64, 64, 1), (64, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 128, 1),
-                  (128, 256, 2), (256, 256, 1), (256, n_out_features, 1)]
-        for i, (ci, co, s) in enumerate(widths):
+        for i, (ci, co, s) in enumerate(width_plan(in_channels, n_out_features)):
             setattr(self, f"l{i + 1}", Unit(ci, co, A, groups, num_nodes, stride=s, residual=i > 0))
         self.head = Head(n_out_features, n_classes, dropout_ratio)
         _bn_init(self.data_bn, 1)
-        self.activation_dtype = torch.float32
-        self.block_tap = None              # a list: every unit's output (N, T, V, C) is appended to it (tests, debugging)
         self.drop_tap = None               # a list: every DropGraph draw's record is appended to it
         self.drop_seeds = None             # {(unit, site): seed tensor} used in place of the hash draw
-        self._init_device_seeds(clips_independent_in_train=False)      # BatchNorm's batch statistics and DropGraph's normalisers
+        self._finish()                     # (DropGraph's batch-wide normalisers couple the clips too)
 
     @property
     def units(self):
         return [getattr(self, f"l{i}") for i in range(1, 11)]
 
-    def set_activation_dtype(self, dtype):
-        if dtype != torch.float32:
-            raise NotImplementedError(
-                f"activation dtype {dtype}: the DecoupledGCN backend runs in fp32 only (bf16 needs its own parity contract "
-                f"for the BatchNorm statistics and the DropGraph statistics)")
-        return self
-
-    def frames_out(self, T):
-        for u in self.units:
-            T = (T - 1) // u.stride + 1
-        return T
+    def _blocks(self):
+        return self.units
 
     def forward_features(self, x, keep_prob=0.9):
-        if x.dim() != 4 or x.shape[2] != self.num_nodes or x.shape[3] != self.in_channels:
-            raise ValueError(f"expected (N, T, {self.num_nodes}, {self.in_channels}), got {tuple(x.shape)}")
+        self._check_input(x)
         if not 0.0 < float(keep_prob) <= 1.0:
             raise ValueError(f"keep_prob {keep_prob}: must be in (0, 1]")
-        N, T, V, C = x.shape
-        if T < 1:
-            raise ValueError("at least one frame")
         training = self.training
         seed_base = self._next_step_seed() if training else None
-        h = batch_norm_rows(x.contiguous().float().view(N * T, V * C), self.data_bn, training).view(N, T, V, C)
+        h = self._stem(x)
         for i, unit in enumerate(self.units, start=1):
             drop = None
             if training and i >= FIRST_DROP_UNIT and float(keep_prob) != 1.0:
                 drop = (float(keep_prob), self.drop_size, self.block_size, self._site_seeds(i), seed_base, self.drop_seeds,
                         self.drop_tap, i)
             h = dgcn_unit(h, unit, training, drop)
-            if self.block_tap is not None:
-                self.block_tap.append(h.detach())
-        p = self.head.dropout_ratio if training else 0.0
-        return mean_pool(h.view(N, -1, h.shape[-1]), p, self._site_seeds(HEAD_SITE)[0], seed_base)
-
-    def forward(self, x, keep_prob=0.9):
-        return self._classify(self.head.classifier, self.forward_features(x, keep_prob))
+            self._tap(h)
+        return self._pool(h, seed_base)

@@ -19,37 +19,21 @@ host synchronisation in forward); eval() normalises with the running values.  No
 Supported: in_channels 1..4, num_nodes <= 32, n_out_features a multiple of 64 up to 1024, edge_importance_weighting True
 or False, any T >= 1.  `batch_norm=True` is refused (the reference's head crashes on it: no behaviour to match).
 """
-import math
-
 import numpy as np
 import torch
 from torch import nn
 
-from .. import functional as HF
-from ..seeding import DeviceSeeds
-from ..stgcn_block import st_gcn_block, batch_norm_rows, mean_pool, RES_NONE, RES_IDENTITY, RES_CONV
-
-TEMPORAL_TAPS = 9
-HEAD_SITE = 0          # the head dropout's site: _site_seeds(0)[0]
+from ..stgcn_block import st_gcn_block, RES_NONE, RES_IDENTITY, RES_CONV
+from ._gcn import (GCNModel, Head, TEMPORAL_TAPS, HEAD_SITE, width_plan, stem_problem, width_problem,  # noqa: F401
+                   edge_problem)
 
 
 def shape_problem(in_channels, num_nodes, n_out_features, batch_norm, center=0, inward_edges=()):
     """None, or the message naming the rule a configuration breaks"""
-    if batch_norm:
-        return ("batch_norm=True: the reference's head fails on it (FC reads self.n_features before it exists), so there "
-                "is no behaviour to reproduce; the ST-GCN backend takes batch_norm=False only")
-    if not 1 <= in_channels <= 4:
-        return f"in_channels {in_channels}: the ST-GCN backend takes 1 to 4 coordinates per joint"
-    if not 1 <= num_nodes <= HF.STGCN_MAX_NODES:
-        return f"num_nodes {num_nodes}: the graph aggregation kernels take at most {HF.STGCN_MAX_NODES} joints"
-    if n_out_features <= 0 or n_out_features % 64 or n_out_features > 1024:
-        return f"n_out_features {n_out_features}: the ST-GCN backend takes multiples of 64 up to 1024"
-    if not 0 <= center < num_nodes:
-        return f"center {center}: not a joint of a {num_nodes}-joint graph"
-    for e in inward_edges or ():
-        if len(e) != 2 or not (0 <= e[0] < num_nodes and 0 <= e[1] < num_nodes):
-            return f"edge {list(e)}: not a pair of joints of a {num_nodes}-joint graph"
-    return None
+    problem = stem_problem("ST-GCN", in_channels, num_nodes, batch_norm) or width_problem("ST-GCN", n_out_features)
+    if problem is None and not 0 <= center < num_nodes:
+        problem = f"center {center}: not a joint of a {num_nodes}-joint graph"
+    return problem or edge_problem(num_nodes, inward_edges)
 
 
 def spatial_adjacency(num_nodes, center, inward_edges):
@@ -120,68 +104,33 @@ class Block(nn.Module):
             )
 
 
-class Head(nn.Module):
-    """the reference's FC head: dropout (fused into the pool kernel here) and `classifier`"""
+class Model(GCNModel):
+    _backend = "ST-GCN"
+    _bf16_needs = "the BatchNorm statistics and bf16 MFMA temporal-convolution kernels"
 
-    def __init__(self, n_features, num_class, dropout_ratio):
-        super().__init__()
-        self.dropout_ratio = float(dropout_ratio)
-        self.classifier = nn.Linear(n_features, num_class)
-        nn.init.normal_(self.classifier.weight, 0, math.sqrt(2.0 / num_class))
-
-
-class Model(DeviceSeeds, nn.Module):
     def __init__(self, in_channels=2, num_nodes=29, center=0, inward_edges=None, edge_importance_weighting=True,
                  n_out_features=256, n_classes=1000, dropout_ratio=0.05, batch_norm=False):
-        super().__init__()
-        problem = shape_problem(in_channels, num_nodes, n_out_features, batch_norm, center, inward_edges)
-        if problem is not None:
-            raise NotImplementedError(problem)
-        if not 0.0 <= float(dropout_ratio) < 1.0:
-            raise ValueError(f"dropout_ratio {dropout_ratio}: must be in [0, 1)")
-        self.in_channels, self.num_nodes, self.n_out_features = in_channels, num_nodes, n_out_features
+        super().__init__(shape_problem(in_channels, num_nodes, n_out_features, batch_norm, center, inward_edges),
+                         in_channels, num_nodes, n_out_features, dropout_ratio)
         A = torch.tensor(spatial_adjacency(num_nodes, center, inward_edges or []), dtype=torch.float32, requires_grad=False)
         self.register_buffer("A", A)
         self.data_bn = nn.BatchNorm1d(in_channels * num_nodes)
-        widths = [(in_channels, 64, 1), (64, 64, 1), (64, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 128, 1),
-                  (128, 256, 2), (256, 256, 1), (256, n_out_features, 1)]
-        self.st_gcn_networks = nn.ModuleList([Block(ci, co, s, residual=i > 0) for i, (ci, co, s) in enumerate(widths)])
+        self.st_gcn_networks = nn.ModuleList([Block(ci, co, s, residual=i > 0)
+                                              for i, (ci, co, s) in enumerate(width_plan(in_channels, n_out_features))])
         if edge_importance_weighting:
             self.edge_importance = nn.ParameterList([nn.Parameter(torch.ones(self.A.size())) for _ in self.st_gcn_networks])
         else:
             self.edge_importance = [None] * len(self.st_gcn_networks)
         self.head = Head(n_out_features, n_classes, dropout_ratio)
-        self.activation_dtype = torch.float32
-        self.block_tap = None              # a list: every block's output (N, T, V, C) is appended to it (tests, debugging)
-        self._init_device_seeds(clips_independent_in_train=False)      # BatchNorm's batch statistics
+        self._finish()
 
-    def set_activation_dtype(self, dtype):
-        if dtype != torch.float32:
-            raise NotImplementedError(
-                f"activation dtype {dtype}: the ST-GCN backend runs in fp32 only (bf16 needs its own parity contract for "
-                f"the BatchNorm statistics and bf16 MFMA temporal-convolution kernels)")
-        return self
-
-    def frames_out(self, T):
-        for blk in self.st_gcn_networks:
-            T = (T - 1) // blk.stride + 1
-        return T
+    def _blocks(self):
+        return self.st_gcn_networks
 
     def forward_features(self, x):
-        if x.dim() != 4 or x.shape[2] != self.num_nodes or x.shape[3] != self.in_channels:
-            raise ValueError(f"expected (N, T, {self.num_nodes}, {self.in_channels}), got {tuple(x.shape)}")
-        N, T, V, C = x.shape
-        if T < 1:
-            raise ValueError("at least one frame")
-        training = self.training
-        h = batch_norm_rows(x.contiguous().float().view(N * T, V * C), self.data_bn, training).view(N, T, V, C)
+        self._check_input(x)
+        h = self._stem(x)
         for blk, importance in zip(self.st_gcn_networks, self.edge_importance):
-            h = st_gcn_block(h, blk, self.A, importance, training)
-            if self.block_tap is not None:
-                self.block_tap.append(h.detach())
-        p = self.head.dropout_ratio if training else 0.0
-        seed_base = self._next_step_seed() if training else None
-        return mean_pool(h.view(N, -1, h.shape[-1]), p, self._site_seeds(HEAD_SITE)[0], seed_base)
-
-    def forward(self, x):
-        return self._classify(self.head.classifier, self.forward_features(x))
+            h = st_gcn_block(h, blk, self.A, importance, self.training)
+            self._tap(h)
+        return self._pool(h, self._next_step_seed() if self.training else None)

@@ -30,28 +30,47 @@ def _bn_stats(x, bn, training):
     return HF.stgcn_bn_eval_stats(bn.running_mean, bn.running_var, bn.eps)
 
 
+# The three launch sequences that the ST-GCN block and the DecoupledGCN unit (dgcn_block._Unit) have in common.
+def pad_channels(x):
+    """x with its channels zero-padded to a multiple of 32 (x itself when they are one)"""
+    CinP = HF.pad32(x.shape[3])
+    return x if CinP == x.shape[3] else HF.stgcn_copy_cols(x, CinP)
+
+
+def project(xp, wg, bg):
+    """the 1x1 projection of the padded input by the master weight wg (3 C_out, C_in, 1, 1) and bias bg"""
+    return HF.stgcn_conv(xp, HF.stgcn_weight_image(wg, 0, xp.shape[3]), bg)
+
+
+def residual_forward(res, x, xp, wr, br, gr, ber, bnr, stride, training):
+    """(r, rbn): the residual operand (None | x | the strided 1x1 convolution of xp) and, for RES_CONV, the (mean, rstd,
+    gamma, beta) of its BatchNorm, which the block's last launch applies while it adds"""
+    if res == RES_CONV:
+        rc = HF.stgcn_conv(xp, HF.stgcn_weight_image(wr, 0, xp.shape[3]), br, stride, 0)
+        return rc, _bn_stats(rc, bnr, training) + (gr, ber)
+    return (x if res == RES_IDENTITY else None), None
+
+
+def crop_dx(dx, Cin):
+    """the input gradient without the padding channels of pad_channels"""
+    return dx if dx.shape[3] == Cin else HF.stgcn_copy_cols(dx, Cin)
+
+
 class _Block(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, E, wg, bg, g1, b1, wt, bt, g2, b2, wr, br, gr, ber):
         A, stride, res, training, bn1, bn2, bnr = cfg
-        N, T, V, Cin = x.shape
-        CinP = HF.pad32(Cin)
-        xp = x if CinP == Cin else HF.stgcn_copy_cols(x, CinP)
-        y = HF.stgcn_conv(xp, HF.stgcn_weight_image(wg, 0, CinP), bg)
+        Cin = x.shape[3]
+        xp = pad_channels(x)
+        y = project(xp, wg, bg)
         a = HF.stgcn_aggregate(y, A, E)
         m1, r1 = _bn_stats(a, bn1, training)
         h = HF.stgcn_bn_apply(a, m1, r1, g1, b1, relu=True)
         c = HF.stgcn_conv(h, HF.stgcn_weight_image(wt, 0), bt, stride, wt.shape[2] // 2)
         m2, r2 = _bn_stats(c, bn2, training)
-        rc = mr = rr = None
-        if res == RES_CONV:
-            rc = HF.stgcn_conv(xp, HF.stgcn_weight_image(wr, 0, CinP), br, stride, 0)
-            mr, rr = _bn_stats(rc, bnr, training)
-            out = HF.stgcn_bn_apply(c, m2, r2, g2, b2, relu=True, res=rc, res_bn=(mr, rr, gr, ber))
-        elif res == RES_IDENTITY:
-            out = HF.stgcn_bn_apply(c, m2, r2, g2, b2, relu=True, res=x)
-        else:
-            out = HF.stgcn_bn_apply(c, m2, r2, g2, b2, relu=True)
+        r, rbn = residual_forward(res, x, xp, wr, br, gr, ber, bnr, stride, training)
+        rc, mr, rr = (r, rbn[0], rbn[1]) if rbn else (None, None, None)
+        out = HF.stgcn_bn_apply(c, m2, r2, g2, b2, relu=True, res=r, res_bn=rbn)
         ctx.save_for_backward(xp, y, a, h, c, rc, out, m1, r1, m2, r2, mr, rr, E, wg, g1, wt, g2, wr, gr)
         ctx.cfg = (A, stride, res, training, Cin)
         return out
@@ -83,9 +102,7 @@ class _Block(torch.autograd.Function):
             dx = HF.stgcn_conv_dx(dy, wg_t, T, 1, 0, add=dout, mask=out)
         else:
             dx = HF.stgcn_conv_dx(dy, wg_t, T, 1, 0, add=dx_res)
-        if CinP != Cin:
-            dx = HF.stgcn_copy_cols(dx, Cin)
-        return dx, None, dE, d_wg, d_bg, d_g1, d_b1, d_wt, d_bt, d_g2, d_b2, d_wr, d_br, d_gr, d_ber
+        return crop_dx(dx, Cin), None, dE, d_wg, d_bg, d_g1, d_b1, d_wt, d_bt, d_g2, d_b2, d_wr, d_br, d_gr, d_ber
 
 
 def st_gcn_block(x, block, A, importance=None, training=True):

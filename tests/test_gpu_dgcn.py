@@ -83,9 +83,11 @@ def _agg_reference(y, An, d, dtype):
     return out.detach(), yr.grad, Ar.grad
 
 
-@pytest.mark.parametrize("NT", [1, 58])
+@pytest.mark.parametrize("NT", [1, 58, 129, 300])
 @pytest.mark.parametrize("V,C,G", [(29, 64, 8), (32, 128, 4), (17, 64, 1), (29, 256, 8)])
 def test_aggregation_against_fp64(V, C, G, NT):
+    """NT 129 and 300 exceed the 128 block images of d An: two frames per image with a short last one (65 images), and
+    three frames per image (100 images); groups 8 of 64 and 4 of 128 channels are ragged 8- and 32-channel chunks"""
     g = torch.Generator().manual_seed(V + C + G + NT)
     y = torch.randn(1, NT, V, 3 * C, generator=g)
     An = torch.rand(3, G, V, V, generator=g) * (torch.rand(3, G, V, V, generator=g) < 0.3).float()

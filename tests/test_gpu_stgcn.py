@@ -107,13 +107,17 @@ def test_conv_refuses_other_shapes():
 
 
 # ------------------------------------------------------------------------------------------ projection + aggregation
-@pytest.mark.parametrize("V,Cin,Cout,imp", [(29, 64, 64, True), (32, 64, 128, True), (17, 128, 64, True), (29, 3, 64, True),
-                                            (29, 64, 64, False)])
-def test_projection_and_aggregation_against_fp64(V, Cin, Cout, imp):
+@pytest.mark.parametrize("N,T,V,Cin,Cout,imp", [
+    pytest.param(2, 5, 29, 64, 64, True, id="29-64-64-True"), pytest.param(2, 5, 32, 64, 128, True, id="32-64-128-True"),
+    pytest.param(2, 5, 17, 128, 64, True, id="17-128-64-True"), pytest.param(2, 5, 29, 3, 64, True, id="29-3-64-True"),
+    pytest.param(2, 5, 29, 64, 64, False, id="29-64-64-False"),
+    pytest.param(3, 171, 29, 64, 64, True, id="frames513-29-64-64-True")])
+def test_projection_and_aggregation_against_fp64(N, T, V, Cin, Cout, imp):
     """the graph convolution: 1x1 projection with bias, then the importance-weighted aggregation; forward, input gradient,
-    weight / bias gradients and the (3, V, V) importance gradient.  C_in = 3 runs the zero-padded input path."""
+    weight / bias gradients and the (3, V, V) importance gradient.  C_in = 3 runs the zero-padded input path.  N T = 513
+    frames are one more than the 512 block images of d edge_importance: two frames per image, 257 images, the last with
+    one frame."""
     g = torch.Generator().manual_seed(V + Cin)
-    N, T = 2, 5
     x = torch.randn(N, T, V, Cin, generator=g)
     W = torch.randn(3 * Cout, Cin, 1, 1, generator=g) / Cin ** 0.5
     b = 0.3 * torch.randn(3 * Cout, generator=g)
