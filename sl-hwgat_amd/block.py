@@ -219,20 +219,16 @@ class _FusedBlock(torch.autograd.Function):
             dwq.run(lambda: HF.linear_tn(d_h1, y, dw1, db1, ln=(m2, r2, n2w, n2b), deterministic=det, pad_stage=True))
         d_z = HF.linear_nt(d_h1, wT("w1T", w1), None, epi=HF.EPI_NONE)
         # ---- attention branch: y = x + drop1(o Wp^T + bp)
-        if p > 0.0 and HF.MASK_ONCE >= 1 and d >= HF.MASK_ONCE_MIN_D:
-            if xn_path:
-                d_y, d_ym, yn = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, mask=(seeds[0], p), beta=n2b, seed_base=sb, deterministic=det)
-                dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det, pad_stage=True))
-            else:
-                d_y, d_ym = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, mask=(seeds[0], p), seed_base=sb, deterministic=det)   # + shortcut; and dropmask1 * d_y
+        mask_once = p > 0.0 and HF.MASK_ONCE >= 1 and d >= HF.MASK_ONCE_MIN_D
+        # d_y = dLN2(d_z) + the shortcut gradient; with mask_once also d_ym = dropmask1 * d_y; on the xn path also yn = LN2(y)
+        d_y, d_ym, yn = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, mask=(seeds[0], p) if mask_once else None,
+                                       beta=n2b if xn_path else None, seed_base=sb, deterministic=det)
+        if xn_path:
+            dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det, pad_stage=True))
+        if mask_once:
             dwq.run(lambda: HF.linear_tn(d_ym, o, dwp, dbp, deterministic=det, pad_stage=True))
             d_o = HF.linear_nt(d_ym, wT("wpT", wp), None, epi=HF.EPI_NONE, out=d_z)
         else:
-            if xn_path:
-                d_y, yn = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, beta=n2b, deterministic=det)
-                dwq.run(lambda: HF.linear_tn(d_h1, yn, dw1, db1, deterministic=det, pad_stage=True))
-            else:
-                d_y = HF.ln_backward(d_z, y, m2, r2, n2w, dout, dn2w, dn2b, deterministic=det)          # + shortcut gradient
             dwq.run(lambda: HF.linear_tn(d_y, o, dwp, dbp, pro_seed=seeds[0], pro_p=p, seed_base=sb, deterministic=det, pad_stage=True))
             d_o = HF.linear_nt(d_y, wT("wpT", wp), None, pro=HF.PRO_DROP, pro_seed=seeds[0], pro_p=p,
                                epi=HF.EPI_NONE, out=d_z, seed_base=sb)
@@ -252,16 +248,9 @@ class _FusedBlock(torch.autograd.Function):
         if not xn_path:
             dwq.run(lambda: HF.linear_tn(dqkv, x, dwqkv, dbqkv, ln=(m1, r1, n1w, n1b), deterministic=det, pad_stage=True))
         d_xn = HF.linear_nt(dqkv, wT("wqkvT", wqkv), None, epi=HF.EPI_NONE, out=d_o)
-        dxm = None
-        if ctx.send_up:           # the block that produced x gets dropmask3(its seed) * dx through the carrier's gradient
-            if xn_path:
-                dx, dxm, xn = HF.ln_backward(d_xn, x, m1, r1, n1w, d_y, dn1w, dn1b, mask=up, beta=n1b, seed_base=sb, deterministic=det)
-            else:
-                dx, dxm = HF.ln_backward(d_xn, x, m1, r1, n1w, d_y, dn1w, dn1b, mask=up, seed_base=sb, deterministic=det)
-        elif xn_path:
-            dx, xn = HF.ln_backward(d_xn, x, m1, r1, n1w, d_y, dn1w, dn1b, beta=n1b, deterministic=det)
-        else:
-            dx = HF.ln_backward(d_xn, x, m1, r1, n1w, d_y, dn1w, dn1b, deterministic=det)
+        # send_up: the block that produced x gets dxm = dropmask3(its seed) * dx through the carrier's gradient
+        dx, dxm, xn = HF.ln_backward(d_xn, x, m1, r1, n1w, d_y, dn1w, dn1b, mask=up if ctx.send_up else None,
+                                     beta=n1b if xn_path else None, seed_base=sb, deterministic=det)
         if xn_path:
             dwq.run(lambda: HF.linear_tn(dqkv, xn, dwqkv, dbqkv, deterministic=det, pad_stage=True))
         if dxm is not None:

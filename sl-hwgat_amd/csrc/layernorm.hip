@@ -366,46 +366,88 @@ inline int ln_grid(int64_t N, int rpw) {
     return (int)(need < 2048 ? (need < 1 ? 1 : need) : 2048);
 }
 
-template <typename T>
-int ln_fwd_t(const void* x, const float* gm, const float* bt, void* y, float* mean, float* rstd, int64_t N,
-             int d, hipStream_t st) {
-#define GO(D) ln_fwd_k<T, D><<<ln_grid(N, RowMap<D>::RPW), 256, 0, st>>>((const T*)x, gm, bt, (T*)y, mean, rstd, N)
-    switch (d) {
-        case 128: GO(128); break;
-        case 256: GO(256); break;
-        case 512: GO(512); break;
-        case 1024: GO(1024); break;
-        default: return HWGAT_ESHAPE;
-    }
-#undef GO
+// ---- host dispatch, one per operation: the widths of layernorm_w64.hip go there; here the dtype is checked first, then
+// the width, and the record's options become the template arguments (ln_args.h)
+// f(LnElem<T>, std::integral_constant<int, d>) for the widths this file serves
+template <typename F> int with_kernel(int dtype, int d, F&& f) {
+    return ln_with_dtype(dtype, [&](auto elem) {
+        return ln_with_int<128, 256, 512, 1024>(d, [&](auto width) { return f(elem, width); });
+    });
+}
+
+int ln_fwd(const void* x, const float* gm, const float* bt, void* y, float* mean, float* rstd, int64_t N, int d, int dtype,
+           hipStream_t st) {
+    if (hwgat_lnw_takes(d)) return hwgat_lnw_fwd(x, gm, bt, y, mean, rstd, N, d, dtype, st);
+    const int rc = with_kernel(dtype, d, [&](auto elem, auto width) {
+        using T = typename decltype(elem)::type;
+        constexpr int D = width();
+        ln_fwd_k<T, D><<<ln_grid(N, RowMap<D>::RPW), 256, 0, st>>>((const T*)x, gm, bt, (T*)y, mean, rstd, N);
+        return 0;
+    });
+    if (rc) return rc;
     HWGAT_LAUNCH_CHECK();
 }
-template <typename T, bool RES, bool MASK = false, bool XN = false, bool DET = false>
-int ln_bwd_t(const void* dy, const void* x, const float* mean, const float* rstd, const float* gm,
-             const void* dres, void* dx, float* dg, float* db, int64_t N, int d, hipStream_t st,
-             void* dxm = nullptr, uint32_t mseed = 0, float mp = 0.f, const float* bt = nullptr, void* xn = nullptr,
-             const uint32_t* sbase = nullptr, float* det_ws = nullptr) {
-    // DET: the kernel writes per-block images into det_ws (1024 x 2 d floats), then two fixed-order reductions
+
+int ln_bwd(const LnBwdArgs& a, hipStream_t st) {
+    if (hwgat_lnw_takes(a.d)) return hwgat_lnw_bwd(a, st);
     int grid = 0;
-#define GO(D)                                                                                                        \
-    grid = ln_grid(N, RowMap<D>::RPW) < 1024 ? ln_grid(N, RowMap<D>::RPW) : 1024;                                    \
-    ln_bwd_k<T, D, RES, MASK, XN, DET><<<grid, 256, 0, st>>>((const T*)dy, (const T*)x, mean, rstd, gm, (const T*)dres, (T*)dx, \
-                                          DET ? det_ws : dg, DET ? det_ws : db, N, (T*)dxm, mseed, mp, bt, (T*)xn, sbase)
-    switch (d) {
-        case 128: GO(128); break;
-        case 256: GO(256); break;
-        case 512: GO(512); break;
-        case 1024: GO(1024); break;
-        default: return HWGAT_ESHAPE;
-    }
-#undef GO
-    if constexpr (DET) {
-        int rc = hwgat_tn_det_reduce(det_ws, dg, grid, 2 * (int64_t)d, d, st);
-        if (rc) return rc;
-        return hwgat_tn_det_reduce(det_ws + d, db, grid, 2 * (int64_t)d, d, st);
-    }
+    const int rc = with_kernel(a.dtype, a.d, [&](auto elem, auto width) {
+        using T = typename decltype(elem)::type;
+        constexpr int D = width();
+        grid = ln_grid(a.N, RowMap<D>::RPW) < 1024 ? ln_grid(a.N, RowMap<D>::RPW) : 1024;
+        auto launch = [&](auto res, auto mask, auto xn, auto det) {
+            ln_bwd_k<T, D, res(), mask(), xn(), det()><<<grid, 256, 0, st>>>(
+                (const T*)a.dy, (const T*)a.x, a.mean, a.rstd, a.gamma, (const T*)a.dres, (T*)a.dx,
+                det() ? a.det_ws : a.dgamma, det() ? a.det_ws : a.dbeta, a.N, (T*)a.dx_masked, a.mask_seed, a.mask_p,
+                a.beta, (T*)a.xn, a.seed_base);
+            return 0;
+        };
+        return ln_with_bool(a.det(), [&](auto det) -> int {
+            // the residual-free kernel exists only without the masked copy and without xn: ten combinations, not sixteen
+            constexpr std::false_type no{};
+            if (!a.res()) return a.mask() || a.with_xn() ? HWGAT_EINVAL : launch(no, no, no, det);
+            return ln_with_bool(a.mask(), [&](auto mask) {
+                return ln_with_bool(a.with_xn(), [&](auto xn) { return launch(std::true_type{}, mask, xn, det); });
+            });
+        });
+    });
+    return rc ? rc : ln_bwd_finish(a, grid, st);
+}
+
+int lnpool_fwd(const LnPoolArgs& a, hipStream_t st) {
+    // (the weighted pool has no kernels in layernorm_w64.hip: its widths end as HWGAT_ESHAPE in with_kernel)
+    int rc = 0;
+    if (!a.weighted() && hwgat_lnw_takes(a.d)) rc = hwgat_lnw_pool_fwd(a, st);
+    else rc = with_kernel(a.dtype, a.d, [&](auto elem, auto width) {
+        using T = typename decltype(elem)::type;
+        constexpr int D = width();
+        return ln_with_bool(a.weighted(), [&](auto wt) {
+            lnpool_fwd_k<T, D, wt()><<<a.B * a.chunks, 256, 0, st>>>((const T*)a.x, a.xhat_sum, a.mean, a.rstd, a.n_tok,
+                                                                    a.chunks, a.partial, a.wtok);
+            return 0;
+        });
+    });
+    if (rc) return rc;
+    if (a.partial) lnpool_reduce_k<<<a.B, 256, 0, st>>>(a.partial, a.xhat_sum, a.chunks, a.d);
     HWGAT_LAUNCH_CHECK();
 }
+
+int lnpool_bwd(const LnPoolArgs& a, hipStream_t st) {
+    if (!a.weighted() && hwgat_lnw_takes(a.d)) return hwgat_lnw_pool_bwd(a, st);
+    const int rc = with_kernel(a.dtype, a.d, [&](auto elem, auto width) {
+        using T = typename decltype(elem)::type;
+        constexpr int D = width();
+        return ln_with_bool(a.weighted(), [&](auto wt) {
+            lnpool_bwd_k<T, D, wt()><<<a.B * a.chunks, 256, 0, st>>>(a.g, (const T*)a.x, a.mean, a.rstd, (T*)a.dx, a.n_tok,
+                                                                    a.chunks, (T*)a.dx_masked, a.mask_seed, a.mask_p,
+                                                                    a.seed_base, a.wtok, a.gdot);
+            return 0;
+        });
+    });
+    if (rc) return rc;
+    HWGAT_LAUNCH_CHECK();
+}
+
 inline int pool_chunks(int B, int n_tok) {
     int c = 2048 / (B > 0 ? B : 1);
     if (c < 1) c = 1;
@@ -470,31 +512,20 @@ extern "C" int hwgat_ln_finalize(float* sum_mean, float* sq_rstd, int64_t n, int
     HWGAT_LAUNCH_CHECK();
 }
 
+// ---- the C entry points: each checks its own arguments (its contract, include/hwgat_hip.h), fills the record and
+// leaves the rest to the dispatch above
 extern "C" int hwgat_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                             float* rstd, int64_t N, int d, int dtype, void* stream) {
     if (!x || !gamma || !beta || !mean || !rstd || N <= 0) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (hwgat_lnw_takes(d)) return hwgat_lnw_fwd(x, gamma, beta, y, mean, rstd, N, d, dtype, st);   // d = 64 n, layernorm_w64.hip
-    if (dtype == HWGAT_F32) return ln_fwd_t<float>(x, gamma, beta, y, mean, rstd, N, d, st);
-    if (dtype == HWGAT_BF16) return ln_fwd_t<bf16_t>(x, gamma, beta, y, mean, rstd, N, d, st);
-    return HWGAT_EDTYPE;
+    return ln_fwd(x, gamma, beta, y, mean, rstd, N, d, dtype, (hipStream_t)stream);
 }
 
 extern "C" int hwgat_ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
                             const float* gamma, const void* dres, void* dx, float* dgamma, float* dbeta,
                             int64_t N, int d, int dtype, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || N <= 0) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (hwgat_lnw_takes(d))
-        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, nullptr, dres, dx, dgamma, dbeta, N, d, dtype, nullptr, 0, 0.f, nullptr,
-                             nullptr, nullptr, st);
-    if (dtype == HWGAT_F32)
-        return dres ? ln_bwd_t<float, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st)
-                    : ln_bwd_t<float, false>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st);
-    if (dtype == HWGAT_BF16)
-        return dres ? ln_bwd_t<bf16_t, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st)
-                    : ln_bwd_t<bf16_t, false>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st);
-    return HWGAT_EDTYPE;
+    return ln_bwd({dy, x, mean, rstd, gamma, nullptr, dres, dx, dgamma, dbeta, N, d, dtype,
+                   nullptr, 0, 0.f, nullptr, nullptr, nullptr}, (hipStream_t)stream);
 }
 
 extern "C" int hwgat_ln_bwd_masked(const void* dy, const void* x, const float* mean, const float* rstd,
@@ -503,15 +534,8 @@ extern "C" int hwgat_ln_bwd_masked(const void* dy, const void* x, const float* m
                                    const uint32_t* seed_base, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !dres || !dx_masked || N <= 0) return HWGAT_EINVAL;
     if (mask_p <= 0.f || mask_p >= 1.f) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (hwgat_lnw_takes(d))
-        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, nullptr, dres, dx, dgamma, dbeta, N, d, dtype, dx_masked, mask_seed,
-                             mask_p, nullptr, seed_base, nullptr, st);
-    if (dtype == HWGAT_F32)
-        return ln_bwd_t<float, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, dx_masked, mask_seed, mask_p, nullptr, nullptr, seed_base);
-    if (dtype == HWGAT_BF16)
-        return ln_bwd_t<bf16_t, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, dx_masked, mask_seed, mask_p, nullptr, nullptr, seed_base);
-    return HWGAT_EDTYPE;
+    return ln_bwd({dy, x, mean, rstd, gamma, nullptr, dres, dx, dgamma, dbeta, N, d, dtype,
+                   dx_masked, mask_seed, mask_p, nullptr, seed_base, nullptr}, (hipStream_t)stream);
 }
 
 // hwgat_ln_bwd (+ optional masked copy) that ALSO writes xn = LN(x) (see ln_bwd_k<.., XN>); dres required
@@ -521,49 +545,8 @@ extern "C" int hwgat_ln_bwd_xn(const void* dy, const void* x, const float* mean,
                                const uint32_t* seed_base, void* stream) {
     if (!dy || !x || !mean || !rstd || !gamma || !beta || !dx || !dgamma || !dbeta || !dres || !xn || N <= 0) return HWGAT_EINVAL;
     if (dx_masked && (mask_p <= 0.f || mask_p >= 1.f)) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (hwgat_lnw_takes(d))
-        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, beta, dres, dx, dgamma, dbeta, N, d, dtype, dx_masked, mask_seed, mask_p,
-                             xn, seed_base, nullptr, st);
-#define GO(T)                                                                                                             \
-    return dx_masked ? ln_bwd_t<T, true, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, dx_masked, \
-                                                     mask_seed, mask_p, beta, xn, seed_base)                              \
-                     : ln_bwd_t<T, true, false, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, nullptr, \
-                                                      0, 0.f, beta, xn)
-    if (dtype == HWGAT_F32) { GO(float); }
-    if (dtype == HWGAT_BF16) { GO(bf16_t); }
-#undef GO
-    return HWGAT_EDTYPE;
-}
-
-extern "C" int hwgat_lnpool_partial_rows(int B, int n_tok) { return (B <= 0 || n_tok <= 0) ? HWGAT_EINVAL : pool_chunks(B, n_tok); }
-
-extern "C" int hwgat_lnpool_fwd_det(const void* x, float* xhat_sum, float* mean, float* rstd, int B, int n_tok, int d,
-                                    int dtype, float* partial, void* stream) {
-    if (!x || !xhat_sum || !mean || !rstd || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = pool_chunks(B, n_tok);
-    if (hwgat_lnw_takes(d)) {
-        const int rc = hwgat_lnw_pool_fwd(x, xhat_sum, mean, rstd, B, n_tok, ch, d, dtype, partial, st);
-        if (rc) return rc;
-        if (partial) lnpool_reduce_k<<<B, 256, 0, st>>>(partial, xhat_sum, ch, d);
-        HWGAT_LAUNCH_CHECK();
-    }
-#define GO(T, D) lnpool_fwd_k<T, D><<<B * ch, 256, 0, st>>>((const T*)x, xhat_sum, mean, rstd, n_tok, ch, partial)
-#define SW(T)                                  \
-    switch (d) {                               \
-        case 128: GO(T, 128); break;           \
-        case 256: GO(T, 256); break;           \
-        case 512: GO(T, 512); break;           \
-        case 1024: GO(T, 1024); break;         \
-        default: return HWGAT_ESHAPE;          \
-    }
-    if (dtype == HWGAT_F32) { SW(float) }
-    else if (dtype == HWGAT_BF16) { SW(bf16_t) }
-    else return HWGAT_EDTYPE;
-#undef GO
-    if (partial) lnpool_reduce_k<<<B, 256, 0, st>>>(partial, xhat_sum, ch, d);
-    HWGAT_LAUNCH_CHECK();
+    return ln_bwd({dy, x, mean, rstd, gamma, beta, dres, dx, dgamma, dbeta, N, d, dtype,
+                   dx_masked, mask_seed, mask_p, xn, seed_base, nullptr}, (hipStream_t)stream);
 }
 
 // Deterministic LayerNorm backward: every option of the three entry points above in one (beta / xn: both or neither; dres
@@ -579,25 +562,17 @@ extern "C" int hwgat_ln_bwd_det(const void* dy, const void* x, const float* mean
     if ((dx_masked || xn) && !dres) return HWGAT_EINVAL;
     if (dx_masked && (mask_p <= 0.f || mask_p >= 1.f)) return HWGAT_EINVAL;
     if (ws_bytes < hwgat_ln_bwd_det_bytes(d)) return HWGAT_ESHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (hwgat_lnw_takes(d))
-        return hwgat_lnw_bwd(dy, x, mean, rstd, gamma, beta, dres, dx, dgamma, dbeta, N, d, dtype, dx_masked, mask_seed, mask_p,
-                             xn, seed_base, ws, st);
-#define GO(T)                                                                                                              \
-    if (xn) return dx_masked ? ln_bwd_t<T, true, true, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, \
-                                                                   dx_masked, mask_seed, mask_p, beta, xn, seed_base, ws)  \
-                             : ln_bwd_t<T, true, false, true, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, \
-                                                                    nullptr, 0, 0.f, beta, xn, seed_base, ws);             \
-    if (dx_masked) return ln_bwd_t<T, true, true, false, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st,    \
-                                                               dx_masked, mask_seed, mask_p, nullptr, nullptr, seed_base, ws); \
-    return dres ? ln_bwd_t<T, true, false, false, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, nullptr, \
-                                                        0, 0.f, nullptr, nullptr, nullptr, ws)                             \
-                : ln_bwd_t<T, false, false, false, true>(dy, x, mean, rstd, gamma, dres, dx, dgamma, dbeta, N, d, st, nullptr, \
-                                                         0, 0.f, nullptr, nullptr, nullptr, ws)
-    if (dtype == HWGAT_F32) { GO(float); }
-    if (dtype == HWGAT_BF16) { GO(bf16_t); }
-#undef GO
-    return HWGAT_EDTYPE;
+    return ln_bwd({dy, x, mean, rstd, gamma, beta, dres, dx, dgamma, dbeta, N, d, dtype,
+                   dx_masked, mask_seed, mask_p, xn, seed_base, ws}, (hipStream_t)stream);
+}
+
+extern "C" int hwgat_lnpool_partial_rows(int B, int n_tok) { return (B <= 0 || n_tok <= 0) ? HWGAT_EINVAL : pool_chunks(B, n_tok); }
+
+extern "C" int hwgat_lnpool_fwd_det(const void* x, float* xhat_sum, float* mean, float* rstd, int B, int n_tok, int d,
+                                    int dtype, float* partial, void* stream) {
+    if (!x || !xhat_sum || !mean || !rstd || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
+    return lnpool_fwd({x, nullptr, xhat_sum, mean, rstd, nullptr, nullptr, nullptr, B, n_tok, pool_chunks(B, n_tok), d, dtype,
+                       nullptr, 0, 0.f, nullptr, partial}, (hipStream_t)stream);
 }
 
 extern "C" int hwgat_lnpool_fwd(const void* x, float* xhat_sum, float* mean, float* rstd, int B, int n_tok, int d,
@@ -605,53 +580,27 @@ extern "C" int hwgat_lnpool_fwd(const void* x, float* xhat_sum, float* mean, flo
     return hwgat_lnpool_fwd_det(x, xhat_sum, mean, rstd, B, n_tok, d, dtype, nullptr, stream);
 }
 
+// (mean / rstd: written by the forward, only read here)
 extern "C" int hwgat_lnpool_bwd_masked(const float* g, const void* x, const float* mean, const float* rstd, void* dx,
-                                       int B, int n_tok, int d, int dtype, void* dx_masked, uint32_t mask_seed,
-                                       float mask_p, const uint32_t* seed_base, void* stream);
+                                       int B, int n_tok, int d, int dtype, void* dxm, uint32_t mseed, float mp,
+                                       const uint32_t* seed_base, void* stream) {
+    if (!g || !x || !mean || !rstd || !dx || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
+    if (dxm && (mp <= 0.f || mp >= 1.f)) return HWGAT_EINVAL;
+    return lnpool_bwd({x, nullptr, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), g, dx, nullptr, B, n_tok,
+                       pool_chunks(B, n_tok), d, dtype, dxm, mseed, mp, seed_base, nullptr}, (hipStream_t)stream);
+}
 
 extern "C" int hwgat_lnpool_bwd(const float* g, const void* x, const float* mean, const float* rstd, void* dx,
                                 int B, int n_tok, int d, int dtype, void* stream) {
     return hwgat_lnpool_bwd_masked(g, x, mean, rstd, dx, B, n_tok, d, dtype, nullptr, 0, 0.f, nullptr, stream);
 }
 
-extern "C" int hwgat_lnpool_bwd_masked(const float* g, const void* x, const float* mean, const float* rstd, void* dx,
-                                       int B, int n_tok, int d, int dtype, void* dxm, uint32_t mseed, float mp,
-                                       const uint32_t* seed_base, void* stream) {
-    if (!g || !x || !mean || !rstd || !dx || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
-    if (dxm && (mp <= 0.f || mp >= 1.f)) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = pool_chunks(B, n_tok);
-    if (hwgat_lnw_takes(d)) return hwgat_lnw_pool_bwd(g, x, mean, rstd, dx, B, n_tok, ch, d, dtype, dxm, mseed, mp, seed_base, st);
-#define GO(T, D) lnpool_bwd_k<T, D><<<B * ch, 256, 0, st>>>(g, (const T*)x, mean, rstd, (T*)dx, n_tok, ch, (T*)dxm, mseed, mp, seed_base)
-    if (dtype == HWGAT_F32) { SW(float) }
-    else if (dtype == HWGAT_BF16) { SW(bf16_t) }
-    else return HWGAT_EDTYPE;
-#undef GO
-#undef SW
-    HWGAT_LAUNCH_CHECK();
-}
-
 // ---- LayerNorm + weighted token pool (GATE.py:208-210): xhat_wsum[b][c] = sum_t wtok[t] xhat[b][t][c]
 extern "C" int hwgat_lnwpool_fwd_det(const void* x, const float* wtok, float* xhat_wsum, float* mean, float* rstd, int B,
                                      int n_tok, int d, int dtype, float* partial, void* stream) {
     if (!x || !wtok || !xhat_wsum || !mean || !rstd || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = pool_chunks(B, n_tok);
-#define GO(T, D) lnpool_fwd_k<T, D, true><<<B * ch, 256, 0, st>>>((const T*)x, xhat_wsum, mean, rstd, n_tok, ch, partial, wtok)
-#define SW(T)                                  \
-    switch (d) {                               \
-        case 128: GO(T, 128); break;           \
-        case 256: GO(T, 256); break;           \
-        case 512: GO(T, 512); break;           \
-        case 1024: GO(T, 1024); break;         \
-        default: return HWGAT_ESHAPE;          \
-    }
-    if (dtype == HWGAT_F32) { SW(float) }
-    else if (dtype == HWGAT_BF16) { SW(bf16_t) }
-    else return HWGAT_EDTYPE;
-#undef GO
-    if (partial) lnpool_reduce_k<<<B, 256, 0, st>>>(partial, xhat_wsum, ch, d);
-    HWGAT_LAUNCH_CHECK();
+    return lnpool_fwd({x, wtok, xhat_wsum, mean, rstd, nullptr, nullptr, nullptr, B, n_tok, pool_chunks(B, n_tok), d, dtype,
+                       nullptr, 0, 0.f, nullptr, partial}, (hipStream_t)stream);
 }
 
 extern "C" int hwgat_lnwpool_fwd(const void* x, const float* wtok, float* xhat_wsum, float* mean, float* rstd, int B,
@@ -664,15 +613,8 @@ extern "C" int hwgat_lnwpool_bwd_masked(const float* g, const float* wtok, const
                                         void* dxm, uint32_t mseed, float mp, const uint32_t* seed_base, void* stream) {
     if (!g || !wtok || !x || !mean || !rstd || !dx || !gdot || B <= 0 || n_tok <= 0) return HWGAT_EINVAL;
     if (dxm && (mp <= 0.f || mp >= 1.f)) return HWGAT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = pool_chunks(B, n_tok);
-#define GO(T, D) lnpool_bwd_k<T, D, true><<<B * ch, 256, 0, st>>>(g, (const T*)x, mean, rstd, (T*)dx, n_tok, ch, (T*)dxm, mseed, mp, seed_base, wtok, gdot)
-    if (dtype == HWGAT_F32) { SW(float) }
-    else if (dtype == HWGAT_BF16) { SW(bf16_t) }
-    else return HWGAT_EDTYPE;
-#undef GO
-#undef SW
-    HWGAT_LAUNCH_CHECK();
+    return lnpool_bwd({x, wtok, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), g, dx, gdot, B, n_tok,
+                       pool_chunks(B, n_tok), d, dtype, dxm, mseed, mp, seed_base, nullptr}, (hipStream_t)stream);
 }
 
 // ---- parameter gradients of a LayerNorm -> Linear pair from G = dY^T xhat (N x K) and db = colsum(dY) (N), for the block

@@ -309,8 +309,14 @@ inline int lnw_grid(int64_t N) {
     return (int)(need < 2048 ? (need < 1 ? 1 : need) : 2048);
 }
 
-// d / 64 for the widths this file serves (every multiple of 64 up to 1024 but 128, 256, 512, 1024)
-#define LNW_WIDTHS(X) X(1) X(3) X(5) X(6) X(7) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+// f(LnElem<T>, std::integral_constant<int, d / 64>): the dtype first, then the widths this file serves (every multiple of
+// 64 up to 1024 but 128, 256, 512, 1024)
+template <typename F> int with_kernel(int dtype, int d, F&& f) {
+    return ln_with_dtype(dtype, [&](auto elem) {
+        if (!hwgat_lnw_takes(d)) return (int)HWGAT_ESHAPE;
+        return ln_with_int<1, 3, 5, 6, 7, 9, 10, 11, 12, 13, 14, 15>(d / 64, [&](auto n) { return f(elem, n); });
+    });
+}
 
 }  // namespace
 
@@ -320,82 +326,50 @@ bool hwgat_lnw_takes(int d) {
 
 int hwgat_lnw_fwd(const void* x, const float* gm, const float* bt, void* y, float* mean, float* rstd, int64_t N, int d,
                   int dtype, hipStream_t st) {
-    if (!hwgat_lnw_takes(d)) return HWGAT_ESHAPE;
-#define GO(n) case n: lnw_fwd_k<T, n><<<lnw_grid(N), 256, 0, st>>>((const T*)x, gm, bt, (T*)y, mean, rstd, N); break;
-#define SW()                             \
-    switch (d / 64) {                    \
-        LNW_WIDTHS(GO)                   \
-        default: return HWGAT_ESHAPE;    \
-    }
-    if (dtype == HWGAT_F32) { using T = float; SW() }
-    else if (dtype == HWGAT_BF16) { using T = bf16_t; SW() }
-    else return HWGAT_EDTYPE;
-#undef GO
-#undef SW
+    const int rc = with_kernel(dtype, d, [&](auto elem, auto n) {
+        using T = typename decltype(elem)::type;
+        lnw_fwd_k<T, n()><<<lnw_grid(N), 256, 0, st>>>((const T*)x, gm, bt, (T*)y, mean, rstd, N);
+        return 0;
+    });
+    if (rc) return rc;
     HWGAT_LAUNCH_CHECK();
 }
 
-int hwgat_lnw_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gm, const float* bt,
-                  const void* dres, void* dx, float* dg, float* db, int64_t N, int d, int dtype, void* dxm, uint32_t mseed,
-                  float mp, void* xn, const uint32_t* sbase, float* det_ws, hipStream_t st) {
-    if (!hwgat_lnw_takes(d)) return HWGAT_ESHAPE;
-    const int grid = lnw_grid(N) < 1024 ? lnw_grid(N) : 1024;
-#define GO(n)                                                                                                          \
-    case n:                                                                                                            \
-        if (det_ws) lnw_bwd_k<T, n, true><<<grid, 256, 0, st>>>((const T*)dy, (const T*)x, mean, rstd, gm, (const T*)dres, \
-                                                               (T*)dx, det_ws, det_ws, N, (T*)dxm, mseed, mp, bt, (T*)xn, sbase); \
-        else lnw_bwd_k<T, n, false><<<grid, 256, 0, st>>>((const T*)dy, (const T*)x, mean, rstd, gm, (const T*)dres,   \
-                                                          (T*)dx, dg, db, N, (T*)dxm, mseed, mp, bt, (T*)xn, sbase);   \
-        break;
-#define SW()                             \
-    switch (d / 64) {                    \
-        LNW_WIDTHS(GO)                   \
-        default: return HWGAT_ESHAPE;    \
-    }
-    if (dtype == HWGAT_F32) { using T = float; SW() }
-    else if (dtype == HWGAT_BF16) { using T = bf16_t; SW() }
-    else return HWGAT_EDTYPE;
-#undef GO
-#undef SW
-    if (det_ws) {                              // the per-block images, added in block order
-        int rc = hwgat_tn_det_reduce(det_ws, dg, grid, 2 * (int64_t)d, d, st);
-        if (rc) return rc;
-        return hwgat_tn_det_reduce(det_ws + d, db, grid, 2 * (int64_t)d, d, st);
-    }
+int hwgat_lnw_bwd(const LnBwdArgs& a, hipStream_t st) {
+    const int grid = lnw_grid(a.N) < 1024 ? lnw_grid(a.N) : 1024;
+    const int rc = with_kernel(a.dtype, a.d, [&](auto elem, auto n) {
+        using T = typename decltype(elem)::type;
+        constexpr int CPL = n();
+        return ln_with_bool(a.det(), [&](auto det) {
+            lnw_bwd_k<T, CPL, det()><<<grid, 256, 0, st>>>(
+                (const T*)a.dy, (const T*)a.x, a.mean, a.rstd, a.gamma, (const T*)a.dres, (T*)a.dx,
+                det() ? a.det_ws : a.dgamma, det() ? a.det_ws : a.dbeta, a.N, (T*)a.dx_masked, a.mask_seed, a.mask_p,
+                a.beta, (T*)a.xn, a.seed_base);
+            return 0;
+        });
+    });
+    return rc ? rc : ln_bwd_finish(a, grid, st);
+}
+
+int hwgat_lnw_pool_fwd(const LnPoolArgs& a, hipStream_t st) {
+    const int rc = with_kernel(a.dtype, a.d, [&](auto elem, auto n) {
+        using T = typename decltype(elem)::type;
+        lnw_pool_fwd_k<T, n()><<<a.B * a.chunks, 256, 0, st>>>((const T*)a.x, a.xhat_sum, a.mean, a.rstd, a.n_tok, a.chunks,
+                                                              a.partial);
+        return 0;
+    });
+    if (rc) return rc;
     HWGAT_LAUNCH_CHECK();
 }
 
-int hwgat_lnw_pool_fwd(const void* x, float* xhat_sum, float* mean, float* rstd, int B, int n_tok, int chunks, int d,
-                       int dtype, float* partial, hipStream_t st) {
-    if (!hwgat_lnw_takes(d)) return HWGAT_ESHAPE;
-#define GO(n) case n: lnw_pool_fwd_k<T, n><<<B * chunks, 256, 0, st>>>((const T*)x, xhat_sum, mean, rstd, n_tok, chunks, partial); break;
-#define SW()                             \
-    switch (d / 64) {                    \
-        LNW_WIDTHS(GO)                   \
-        default: return HWGAT_ESHAPE;    \
-    }
-    if (dtype == HWGAT_F32) { using T = float; SW() }
-    else if (dtype == HWGAT_BF16) { using T = bf16_t; SW() }
-    else return HWGAT_EDTYPE;
-#undef GO
-#undef SW
+int hwgat_lnw_pool_bwd(const LnPoolArgs& a, hipStream_t st) {
+    const int rc = with_kernel(a.dtype, a.d, [&](auto elem, auto n) {
+        using T = typename decltype(elem)::type;
+        lnw_pool_bwd_k<T, n()><<<a.B * a.chunks, 256, 0, st>>>(a.g, (const T*)a.x, a.mean, a.rstd, (T*)a.dx, a.n_tok, a.chunks,
+                                                              (T*)a.dx_masked, a.mask_seed, a.mask_p, a.seed_base);
+        return 0;
+    });
+    if (rc) return rc;
     HWGAT_LAUNCH_CHECK();
 }
 
-int hwgat_lnw_pool_bwd(const float* g, const void* x, const float* mean, const float* rstd, void* dx, int B, int n_tok,
-                       int chunks, int d, int dtype, void* dxm, uint32_t mseed, float mp, const uint32_t* sbase,
-                       hipStream_t st) {
-    if (!hwgat_lnw_takes(d)) return HWGAT_ESHAPE;
-#define GO(n) case n: lnw_pool_bwd_k<T, n><<<B * chunks, 256, 0, st>>>(g, (const T*)x, mean, rstd, (T*)dx, n_tok, chunks, (T*)dxm, mseed, mp, sbase); break;
-#define SW()                             \
-    switch (d / 64) {                    \
-        LNW_WIDTHS(GO)                   \
-        default: return HWGAT_ESHAPE;    \
-    }
-    if (dtype == HWGAT_F32) { using T = float; SW() }
-    else if (dtype == HWGAT_BF16) { using T = bf16_t; SW() }
-    else return HWGAT_EDTYPE;
-#undef GO
-#undef SW
-    HWGAT_LAUNCH_CHECK();
-}

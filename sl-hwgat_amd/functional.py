@@ -5,7 +5,7 @@ nothing falls back to torch arithmetic.  All activations are in the natural
 token order (B, F, K, d).
 """
 import ctypes
-from typing import Callable, NamedTuple
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -227,12 +227,8 @@ class _LayerNorm(torch.autograd.Function):
         d = x.shape[-1]
         dy = dy.contiguous()
         dg = torch.zeros(2, d, device=x.device, dtype=torch.float32)
-        if ctx.deterministic:          # dgamma / dbeta through per-block images added in a fixed order (hwgat_ln_bwd_det)
-            dx = ln_backward(dy, x, mean, rstd, gamma, None, dg[0], dg[1], deterministic=True)
-            return dx, dg[0], dg[1], None
-        dx = torch.empty_like(x)
-        call("hwgat_ln_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), None, ptr(dx),
-             ptr(dg[0]), ptr(dg[1]), x.numel() // d, d, dtype_code(x), stream())
+        # deterministic: dgamma / dbeta through per-block images added in a fixed order (hwgat_ln_bwd_det)
+        dx = ln_backward(dy, x, mean, rstd, gamma, None, dg[0], dg[1], deterministic=ctx.deterministic).dx
         return dx, dg[0], dg[1], None
 
 
@@ -427,43 +423,76 @@ def temporal_merge(x):
 
 
 # ---------------------------------------------------------------- LN + pool
+def _pool_tokens(x):
+    B, d = x.shape[0], x.shape[-1]
+    return B, x.numel() // (B * d), d
+
+
+def _pool_carry(x, carrier, up, book):
+    """(x contiguous, carrier, up) of a pool call.  carrier / up / book (block.fused_block) count only together: a carrier
+    that is not shaped like a contiguous x or comes without a book is dropped, and `up` = (seed, p) stays -- the backward
+    then makes the masked copy -- only with a carrier and p > 0"""
+    xcont = x.contiguous()
+    if carrier is not None and (xcont is not x or carrier.shape != x.shape or book is None):
+        carrier = None
+    if carrier is None or up is None or up[1] <= 0.0:
+        up = None
+    return xcont, carrier, up
+
+
+def _pool_forward(x, wt, deterministic):
+    """hwgat_ln[w]pool_fwd[_det] -> (mean, rstd, hat): the row statistics and the (B, d) fp32 sum over a clip's tokens
+    of xhat, times the token weights `wt` where given"""
+    B, n_tok, d = _pool_tokens(x)
+    mean = torch.empty(B * n_tok, device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    name = "hwgat_lnpool_fwd" if wt is None else "hwgat_lnwpool_fwd"
+    wts = () if wt is None else (ptr(wt),)
+    if deterministic:      # per-block partial sums added in index order: the same bits on every run
+        rows = _lib.lib().hwgat_lnpool_partial_rows(B, n_tok)
+        hat = torch.empty(B, d, device=x.device, dtype=torch.float32)
+        part = torch.empty(B * rows, d, device=x.device, dtype=torch.float32)
+        call(name + "_det", ptr(x), *wts, ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x), ptr(part), stream())
+    else:
+        hat = torch.zeros(B, d, device=x.device, dtype=torch.float32)
+        call(name, ptr(x), *wts, ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x), stream())
+    return mean, rstd, hat
+
+
+def _pool_backward(ctx, g, x, mean, rstd, wt=None):
+    """hwgat_ln[w]pool_bwd_masked for the per-clip upstream gradient g (B, d) -> (dx, dx_masked or None, gdot or None);
+    the masked copy is made with ctx.up and registered with the book; gdot (B, n_tok): the weighted pool's
+    sum_c g[b][c] xhat[b][t][c]"""
+    B, n_tok, d = _pool_tokens(x)
+    dx = torch.empty_like(x)
+    dxm = torch.empty_like(x) if ctx.up is not None else None
+    seed, p = ctx.up if ctx.up else (0, 0.0)
+    gdot = None if wt is None else torch.empty(B, n_tok, device=x.device, dtype=torch.float32)
+    front = (ptr(g), ptr(x)) if wt is None else (ptr(g), ptr(wt), ptr(x))
+    call("hwgat_lnpool_bwd_masked" if wt is None else "hwgat_lnwpool_bwd_masked", *front, ptr(mean), ptr(rstd), ptr(dx),
+         *(() if wt is None else (ptr(gdot),)), B, n_tok, d, dtype_code(x), ptr(dxm), seed & 0xFFFFFFFF, float(p),
+         ptr(ctx.seed_base), stream())
+    if dxm is not None:
+        ctx.book.register(dx, dxm)
+    return dx, dxm, gdot
+
+
 class _LnPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, xc=None, up=None, book=None, deterministic=False, seed_base=None):
-        # xc / up / book: carrier of the masked gradient for the block that produced x (block.fused_block)
-        ctx.up = up if (xc is not None and up is not None and up[1] > 0.0 and book is not None) else None
-        ctx.book = book
-        ctx.seed_base = seed_base
-        B, d = x.shape[0], x.shape[-1]
-        n_tok = x.numel() // (B * d)
-        mean = torch.empty(B * n_tok, device=x.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        if deterministic:      # per-block partial sums added in index order: the same bits on every run
-            rows = _lib.lib().hwgat_lnpool_partial_rows(B, n_tok)
-            hat = torch.empty(B, d, device=x.device, dtype=torch.float32)
-            part = torch.empty(B * rows, d, device=x.device, dtype=torch.float32)
-            call("hwgat_lnpool_fwd_det", ptr(x), ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x), ptr(part), stream())
-        else:
-            hat = torch.zeros(B, d, device=x.device, dtype=torch.float32)
-            call("hwgat_lnpool_fwd", ptr(x), ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x), stream())
-        hat_mean = hat / n_tok
+        # xc / up / book: carrier of the masked gradient for the block that produced x, as _pool_carry resolved them
+        ctx.up, ctx.book, ctx.seed_base = up, book, seed_base
+        mean, rstd, hat = _pool_forward(x, None, deterministic)
+        hat_mean = hat / _pool_tokens(x)[1]
         ctx.save_for_backward(x, gamma, mean, rstd, hat_mean)
         return hat_mean * gamma + beta
 
     @staticmethod
     def backward(ctx, dfeat):
         x, gamma, mean, rstd, hat_mean = ctx.saved_tensors
-        B, d = x.shape[0], x.shape[-1]
-        n_tok = x.numel() // (B * d)
         dfeat = dfeat.float()
-        g = (dfeat * gamma / n_tok).contiguous()
-        dx = torch.empty_like(x)
-        dxm = torch.empty_like(x) if ctx.up is not None else None
-        call("hwgat_lnpool_bwd_masked", ptr(g), ptr(x), ptr(mean), ptr(rstd), ptr(dx), B, n_tok, d,
-             dtype_code(x), ptr(dxm), (ctx.up[0] if ctx.up else 0) & 0xFFFFFFFF, float(ctx.up[1]) if ctx.up else 0.0,
-             ptr(ctx.seed_base), stream())
-        if dxm is not None:
-            ctx.book.register(dx, dxm)
+        g = (dfeat * gamma / _pool_tokens(x)[1]).contiguous()
+        dx, dxm, _ = _pool_backward(ctx, g, x, mean, rstd)
         return dx, (dfeat * hat_mean).sum(0), dfeat.sum(0), dxm, None, None, None, None
 
 
@@ -471,34 +500,19 @@ def ln_mean_pool(x, gamma, beta, carrier=None, up=None, book=None, deterministic
     """final LayerNorm + mean over all tokens -> (B, d) fp32.  carrier / up / book: see block.fused_block (the last
     block's fc2-dropout mask is applied to its incoming gradient here, once).  `deterministic`: fixed summation order
     (two launches, no atomics), what eval() uses so that two forwards are bit-identical like the reference's."""
-    xcont = x.contiguous()
-    if carrier is not None and (xcont is not x or carrier.shape != x.shape or book is None):
-        carrier = None
+    xcont, carrier, up = _pool_carry(x, carrier, up, book)
     return _LnPool.apply(xcont, gamma, beta, carrier, up, book, bool(deterministic), seed_base)
 
 
 class _LnWeightedPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, w, bias, xc=None, up=None, book=None, deterministic=False, seed_base=None):
-        ctx.up = up if (xc is not None and up is not None and up[1] > 0.0 and book is not None) else None
-        ctx.book = book
-        ctx.seed_base = seed_base
-        B, d = x.shape[0], x.shape[-1]
-        n_tok = x.numel() // (B * d)
+        ctx.up, ctx.book, ctx.seed_base = up, book, seed_base
+        n_tok = _pool_tokens(x)[1]
         wt = w.detach().reshape(-1).float().contiguous()
         if wt.numel() != n_tok:
             raise ValueError(f"the pool has {wt.numel()} token weights, the activations have {n_tok} tokens per clip")
-        mean = torch.empty(B * n_tok, device=x.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        if deterministic:      # per-block partial sums added in index order: the same bits on every run
-            rows = _lib.lib().hwgat_lnpool_partial_rows(B, n_tok)
-            hat = torch.empty(B, d, device=x.device, dtype=torch.float32)
-            part = torch.empty(B * rows, d, device=x.device, dtype=torch.float32)
-            call("hwgat_lnwpool_fwd_det", ptr(x), ptr(wt), ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x),
-                 ptr(part), stream())
-        else:
-            hat = torch.zeros(B, d, device=x.device, dtype=torch.float32)
-            call("hwgat_lnwpool_fwd", ptr(x), ptr(wt), ptr(hat), ptr(mean), ptr(rstd), B, n_tok, d, dtype_code(x), stream())
+        mean, rstd, hat = _pool_forward(x, wt, deterministic)
         ctx.save_for_backward(x, gamma, beta, wt, mean, rstd, hat)
         ctx.w_shape = w.shape
         return hat * gamma + (beta * wt.sum() + bias.reshape(()))
@@ -506,18 +520,8 @@ class _LnWeightedPool(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat):
         x, gamma, beta, wt, mean, rstd, hat = ctx.saved_tensors
-        B, d = x.shape[0], x.shape[-1]
-        n_tok = x.numel() // (B * d)
         dfeat = dfeat.float()
-        g = (dfeat * gamma).contiguous()
-        dx = torch.empty_like(x)
-        dxm = torch.empty_like(x) if ctx.up is not None else None
-        gdot = torch.empty(B, n_tok, device=x.device, dtype=torch.float32)
-        call("hwgat_lnwpool_bwd_masked", ptr(g), ptr(wt), ptr(x), ptr(mean), ptr(rstd), ptr(dx), ptr(gdot), B, n_tok, d,
-             dtype_code(x), ptr(dxm), (ctx.up[0] if ctx.up else 0) & 0xFFFFFFFF, float(ctx.up[1]) if ctx.up else 0.0,
-             ptr(ctx.seed_base), stream())
-        if dxm is not None:
-            ctx.book.register(dx, dxm)
+        dx, dxm, gdot = _pool_backward(ctx, (dfeat * gamma).contiguous(), x, mean, rstd, wt)
         dsum = dfeat.sum(0)                                                 # (d)
         # d w[t] = sum_b sum_c dfeat[b,c] (gamma_c xhat[b,t,c] + beta_c): the kernel did the channel sums per (b, t)
         dw = (gdot.sum(0) + (dsum * beta).sum()).reshape(ctx.w_shape)
@@ -529,11 +533,9 @@ def ln_weighted_pool(x, gamma, beta, w, bias, carrier=None, up=None, book=None, 
     along the token axis): feat[b, c] = sum_tok w[tok] LN(x)[b, tok, c] + bias -> (B, d) fp32.  w (n_tok) or (1, n_tok),
     bias (1).  Gradients to x, gamma, beta, w and bias.  carrier / up / book / deterministic / seed_base: as ln_mean_pool.
     Widths 128, 256, 512 and 1024."""
-    xcont = x.contiguous()
+    xcont, carrier, up = _pool_carry(x, carrier, up, book)
     if xcont.shape[-1] not in (128, 256, 512, 1024):
         raise NotImplementedError(f"width {xcont.shape[-1]}: the weighted token pool takes d in 128, 256, 512, 1024")
-    if carrier is not None and (xcont is not x or carrier.shape != x.shape or book is None):
-        carrier = None
     return _LnWeightedPool.apply(xcont, gamma, beta, w, bias, carrier, up, book, bool(deterministic), seed_base)
 
 
@@ -832,39 +834,44 @@ def ln_stats(x, gamma, beta):
     return mean, rstd
 
 
+class LnGrads(NamedTuple):
+    """what ln_backward returns; a member its options did not ask for is None"""
+    dx: torch.Tensor
+    dx_masked: Optional[torch.Tensor]       # with `mask`
+    xn: Optional[torch.Tensor]              # with `beta`
+
+
 def ln_backward(dy, x, mean, rstd, gamma, dres, dgamma, dbeta, mask=None, beta=None, seed_base=None, deterministic=False):
-    """dx = dLN(dy) (+ dres); dgamma/dbeta accumulated in place.  mask = (seed, p): also returns dx * dropout-mask
-    (the gradient in front of the dropout that produced this tensor) -> (dx, dx_masked).  `beta` given: ALSO returns
-    xn = LN(x) (appended), for the weight-gradient launch of the Linear behind this LayerNorm (hwgat_ln_bwd_xn).
-    `deterministic`: dgamma / dbeta through per-block images added in a fixed order (hwgat_ln_bwd_det)."""
+    """dx = dLN(dy) (+ dres); dgamma/dbeta accumulated in place.  mask = (seed, p): also dx_masked = dx * dropout-mask
+    (the gradient in front of the dropout that produced this tensor).  `beta` given: ALSO xn = LN(x), for the
+    weight-gradient launch of the Linear behind this LayerNorm (hwgat_ln_bwd_xn).
+    `deterministic`: dgamma / dbeta through per-block images added in a fixed order (hwgat_ln_bwd_det).  -> LnGrads"""
     d = x.shape[-1]
     dx = torch.empty_like(x)
-    if deterministic:
-        dxm = torch.empty_like(x) if mask is not None else None
-        xn = torch.empty_like(x) if beta is not None else None
-        need = _lib.lib().hwgat_ln_bwd_det_bytes(d)
-        ws = torch.empty(need // 4, device=x.device, dtype=torch.float32)
-        call("hwgat_ln_bwd_det", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dres), ptr(dx), ptr(dgamma),
-             ptr(dbeta), x.numel() // d, d, dtype_code(x), ptr(dxm), (mask[0] if mask else 0) & 0xFFFFFFFF,
-             float(mask[1]) if mask else 0.0, ptr(xn), ptr(seed_base), ptr(ws), need, stream())
-        out = (dx,) + ((dxm,) if mask is not None else ()) + ((xn,) if beta is not None else ())
-        return out if len(out) > 1 else dx
-    if beta is not None:
-        dxm = torch.empty_like(x) if mask is not None else None
-        xn = torch.empty_like(x)
-        call("hwgat_ln_bwd_xn", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dres), ptr(dx),
-             ptr(dgamma), ptr(dbeta), x.numel() // d, d, dtype_code(x), ptr(dxm), (mask[0] if mask else 0) & 0xFFFFFFFF,
-             float(mask[1]) if mask else 0.0, ptr(xn), ptr(seed_base), stream())
-        return (dx, dxm, xn) if mask is not None else (dx, xn)
-    if mask is not None:
-        dxm = torch.empty_like(x)
-        call("hwgat_ln_bwd_masked", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx),
-             ptr(dgamma), ptr(dbeta), x.numel() // d, d, dtype_code(x), ptr(dxm), mask[0] & 0xFFFFFFFF, float(mask[1]),
-             ptr(seed_base), stream())
-        return dx, dxm
-    call("hwgat_ln_bwd", ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx),
-         ptr(dgamma), ptr(dbeta), x.numel() // d, d, dtype_code(x), stream())
-    return dx
+    dxm = torch.empty_like(x) if mask is not None else None
+    xn = torch.empty_like(x) if beta is not None else None
+    # the parameter lists of the four entry points are cuts of one: what a restricted form lacks, it does not take
+    # (built up in place: this is host time of every block's backward, and the plain form is the most frequent)
+    takes_xn = deterministic or beta is not None
+    name = "hwgat_ln_bwd"
+    args = (ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma))
+    if takes_xn:
+        args += (ptr(beta),)
+    args += (ptr(dres), ptr(dx), ptr(dgamma), ptr(dbeta), x.numel() // d, d, dtype_code(x))
+    if takes_xn or mask is not None:
+        name = "hwgat_ln_bwd_masked"
+        args += (ptr(dxm), (mask[0] if mask else 0) & 0xFFFFFFFF, float(mask[1]) if mask else 0.0)
+        if takes_xn:
+            name = "hwgat_ln_bwd_xn"
+            args += (ptr(xn),)
+        args += (ptr(seed_base),)
+        if deterministic:
+            name = "hwgat_ln_bwd_det"
+            need = _lib.lib().hwgat_ln_bwd_det_bytes(d)
+            ws = torch.empty(need // 4, device=x.device, dtype=torch.float32)
+            args += (ptr(ws), need)
+    call(name, *args, stream())
+    return LnGrads(dx, dxm, xn)
 
 
 _LN_IDENTITY = {}

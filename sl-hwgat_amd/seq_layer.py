@@ -73,13 +73,10 @@ class _EncoderLayer(torch.autograd.Function):
         # shared by both LayerNorms of the layer
         zero_res = torch.zeros_like(dout) if p > 0.0 else None
 
-        def ln_bwd(dy, xin, mean, rstd, gamma, dg, db, seed):
-            if p > 0.0:
-                dres = zero_res
-                return HF.ln_backward(dy, xin, mean, rstd, gamma, dres, dg, db, mask=(seed, p), seed_base=seed_base,
-                                      deterministic=det)
-            dx = HF.ln_backward(dy, xin, mean, rstd, gamma, None, dg, db, deterministic=det)
-            return dx, dx
+        def ln_bwd(dy, xin, mean, rstd, gamma, dg, db, seed):       # -> dx and its masked copy (p = 0: dx itself)
+            r = HF.ln_backward(dy, xin, mean, rstd, gamma, zero_res, dg, db, mask=(seed, p) if p > 0.0 else None,
+                               seed_base=seed_base, deterministic=det)
+            return r.dx, r.dx if r.dx_masked is None else r.dx_masked
 
         dy2, dy2m = ln_bwd(dout, y2, m2, r2, g_2, d_g2, d_be2, seeds[2])
         HF.linear_tn(dy2m, u, d_2_w, d_2_b, deterministic=det)

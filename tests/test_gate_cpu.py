@@ -210,6 +210,18 @@ def test_new_entry_points_reject_bad_arguments_without_launching():
     assert L.hwgat_lnwpool_bwd_masked(p, p, p, p, p, p, None, 1, 4, 128, 0, None, 0, 0.0, None, None) == -1
     assert L.hwgat_lnwpool_bwd_masked(p, p, p, p, p, p, p, 1, 4, 128, 0, p, 0, 0.0, None, None) == -1   # masked copy, p = 0
     assert L.hwgat_lnwpool_bwd_masked(p, p, p, p, p, p, p, 1, 4, 96, 0, None, 0, 0.0, None, None) == -2
+    # (width, dtype) left open: a width no kernel takes is HWGAT_ESHAPE -- the odd multiples of 64 among them, which only
+    # the mean pool has kernels for -- and an unknown dtype is HWGAT_EDTYPE whatever the width
+    wpool = {
+        "hwgat_lnwpool_fwd": lambda d, t: (p, p, p, p, p, 1, 4, d, t, None),
+        "hwgat_lnwpool_fwd_det": lambda d, t: (p, p, p, p, p, 1, 4, d, t, p, None),
+        "hwgat_lnwpool_bwd_masked": lambda d, t: (p,) * 7 + (1, 4, d, t, p, 1, 0.5, None, None),
+    }
+    for name, args in wpool.items():
+        for d in (100, 1088, 0, 192):
+            assert getattr(L, name)(*args(d, 0)) == -2, (name, d)
+        for d in (100, 128, 192):
+            assert getattr(L, name)(*args(d, 9)) == -3, (name, d)
 
 
 def test_gate_backend_resolves_by_file_name_like_the_reference(scratch_tree):      # noqa: F811

@@ -110,12 +110,13 @@ def test_deterministic_gradient_entry_points_against_the_atomic_forms():
         for kw in ({}, {"mask": (11, 0.1)}, {"beta": beta}, {"mask": (11, 0.1), "beta": beta}):
             dg0 = torch.zeros(2, d, device=DEV)
             ref = HF.ln_backward(dy, x, mean, rstd, gamma, res, dg0[0], dg0[1], **kw)
-            ref = ref if isinstance(ref, tuple) else (ref,)
             rep = []
             for _ in range(2):
                 dg = torch.zeros(2, d, device=DEV)
                 out = HF.ln_backward(dy, x, mean, rstd, gamma, res, dg[0], dg[1], deterministic=True, **kw)
-                rep.append((out if isinstance(out, tuple) else (out,), dg))
+                rep.append((out, dg))
             assert torch.equal(rep[0][1], rep[1][1])
-            assert len(rep[0][0]) == len(ref) and all(torch.equal(a, b) for a, b in zip(rep[0][0], ref))   # dx / masked copy / LN(x): same code
+            # dx / masked copy / LN(x): same code; exactly the members the options ask for
+            assert (ref.dx_masked is not None, ref.xn is not None) == ("mask" in kw, "beta" in kw)
+            assert all((a is None) == (b is None) and (a is None or torch.equal(a, b)) for a, b in zip(rep[0][0], ref))
             assert float((rep[0][1] - dg0).norm() / dg0.norm()) < 1e-5

@@ -465,15 +465,17 @@ def test_ln_bwd_xn_also_writes_the_layernorm_output(d, dtype):
     w, b = (1 + 0.2 * torch.randn(d, generator=g)).to(DEV), (0.2 * torch.randn(d, generator=g)).to(DEV)
     mean, rstd = HF.ln_stats(x, w, b)
     dgr, dbr = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
-    dx0, dxm0 = HF.ln_backward(dy, x, mean, rstd, w, res, dgr, dbr, mask=(99, 0.1))
+    dx0, dxm0, xn0 = HF.ln_backward(dy, x, mean, rstd, w, res, dgr, dbr, mask=(99, 0.1))
+    assert dxm0 is not None and xn0 is None
     for mask in (None, (99, 0.1)):
         dg1, db1 = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
         out = HF.ln_backward(dy, x, mean, rstd, w, res, dg1, db1, mask=mask, beta=b)
-        dx1, xn = out[0], out[-1]
+        dx1, xn = out.dx, out.xn
         assert torch.equal(dx1, dx0)
         assert torch.allclose(dg1, dgr, rtol=1e-5, atol=1e-4) and torch.allclose(db1, dbr, rtol=1e-5, atol=1e-4)
+        assert (out.dx_masked is not None) == (mask is not None)
         if mask is not None:
-            assert torch.equal(out[1], dxm0)
+            assert torch.equal(out.dx_masked, dxm0)
         ref = O.layer_norm(x.cpu().double(), w.cpu().double(), b.cpu().double())
         assert rel_err(xn.float().cpu(), ref) < (F32_TOL if dtype == torch.float32 else BF16_TOL)
         f32 = dtype == torch.float32
@@ -538,15 +540,13 @@ def test_layernorm_model_widths_every_output_against_fp64(d, dtype):
                 if "xn" in variant:
                     kw.update(beta=bt)
                 r = HF.ln_backward(dy, x, mean, rstd, gm, res, dg, db, **kw)
-                r = r if isinstance(r, tuple) else (r,)
                 v = f"{tag} {variant} det {det}"
-                tensor_parity(r[0], want_dx, tol_norm=tol, **par, what=f"{fam}: dx {v}")
-                k = 1
+                assert (r.dx_masked is not None, r.xn is not None) == ("masked" in variant, "xn" in variant), v
+                tensor_parity(r.dx, want_dx, tol_norm=tol, **par, what=f"{fam}: dx {v}")
                 if "masked" in variant:
-                    tensor_parity(r[1], want_dx * mk, tol_norm=tol, **par, what=f"{fam}: dxm {v}")
-                    k = 2
+                    tensor_parity(r.dx_masked, want_dx * mk, tol_norm=tol, **par, what=f"{fam}: dxm {v}")
                 if "xn" in variant:
-                    tensor_parity(r[k], yr, tol_norm=tol, **par, what=f"{fam}: xn {v}")
+                    tensor_parity(r.xn, yr, tol_norm=tol, **par, what=f"{fam}: xn {v}")
                 tensor_parity(dg, gr.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dgamma {dtype} {v}")
                 tensor_parity(db, br.grad, tol_norm=F32_TOL, tol_entry=LN_DG, what=f"ln_dg: dbeta {dtype} {v}")
         # the autograd path (hwgat_ln_bwd without a residual through _LayerNorm.backward)

@@ -236,27 +236,26 @@ def test_layernorm_new_widths(dt, d):
                 if "xn" in variant:
                     kw.update(beta=bg)
                 r = HF.ln_backward(dy.to(DEV), xg, mean, rstd, gg, dres.to(DEV), dg, db, **kw)
-                r = r if isinstance(r, tuple) else (r,)
                 outs.append((r, dg.cpu(), db.cpu()))
             r, dg, db = outs[0]
             if det:
                 assert torch.equal(outs[0][1], outs[1][1]) and torch.equal(outs[0][2], outs[1][2]), variant
-            assert rel_err(r[0].float().cpu(), want_dx) < _tol(dt), (variant, det)
-            tensor_parity(r[0], want_dx, tol_norm=_tol(dt), **par, what=f"{fam}: dx d {d} {variant} det {det}")
-            k = 1
+            assert (r.dx_masked is not None, r.xn is not None) == ("masked" in variant, "xn" in variant), (variant, det)
+            assert rel_err(r.dx.float().cpu(), want_dx) < _tol(dt), (variant, det)
+            tensor_parity(r.dx, want_dx, tol_norm=_tol(dt), **par, what=f"{fam}: dx d {d} {variant} det {det}")
             if "masked" in variant:
-                assert rel_err(r[1].float().cpu(), want_dx * mk) < _tol(dt), (variant, det)
-                tensor_parity(r[1], want_dx * mk, tol_norm=_tol(dt), **par, what=f"{fam}: dxm d {d} {variant} det {det}")
-                k = 2
+                assert rel_err(r.dx_masked.float().cpu(), want_dx * mk) < _tol(dt), (variant, det)
+                tensor_parity(r.dx_masked, want_dx * mk, tol_norm=_tol(dt), **par, what=f"{fam}: dxm d {d} {variant} det {det}")
             if "xn" in variant:
-                assert rel_err(r[k].float().cpu(), xn_want) < _tol(dt), (variant, det)
-                tensor_parity(r[k], xn_want, tol_norm=_tol(dt), **par, what=f"{fam}: xn d {d} {variant} det {det}")
+                assert rel_err(r.xn.float().cpu(), xn_want) < _tol(dt), (variant, det)
+                tensor_parity(r.xn, xn_want, tol_norm=_tol(dt), **par, what=f"{fam}: xn d {d} {variant} det {det}")
             assert rel_err(dg, gr.grad) < 1e-4 and rel_err(db, br.grad) < 1e-4, (variant, det)
             tensor_parity(dg, gr.grad, tol_norm=1e-4, tol_entry=LN64_DG, what=f"ln64_dg: dgamma d {d} {dt} {variant} det {det}")
             tensor_parity(db, br.grad, tol_norm=1e-4, tol_entry=LN64_DG, what=f"ln64_dg: dbeta d {d} {dt} {variant} det {det}")
     # no residual
     dg, db = torch.zeros(d, device=DEV), torch.zeros(d, device=DEV)
-    dx = HF.ln_backward(dy.to(DEV), xg, mean, rstd, gg, None, dg, db)
+    dx, dxm, xn = HF.ln_backward(dy.to(DEV), xg, mean, rstd, gg, None, dg, db)
+    assert dxm is None and xn is None
     assert rel_err(dx.float().cpu(), xr.grad) < _tol(dt)
     tensor_parity(dx, xr.grad, tol_norm=_tol(dt), **par, what=f"{fam}: dx d {d} no residual")
 

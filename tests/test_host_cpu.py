@@ -98,6 +98,26 @@ def test_c_abi_rejects_bad_arguments_without_launching():
     assert L.hwgat_linear_tn_f32(p, p, p, None, 64, 128, 100, 0, 0.0, None, None, None, None, None, None) == -2
     assert L.hwgat_embed_fwd(p, None, p, None, p, 1, 4, 29, 64, 2, 128, 0, 0, 0.0, None, None) == -2   # J != K without a table
     assert L.hwgat_merge(p, p, 1, 3, 16, 128, 0, 0, None) == -2
+    # the LayerNorm family, (width, dtype) left open: a width no kernel takes is HWGAT_ESHAPE, an unknown dtype is
+    # HWGAT_EDTYPE whatever the width -- the dtype is looked at first
+    ln = {
+        "hwgat_ln_fwd": lambda d, t: (p, p, p, p, p, p, 8, d, t, None),
+        "hwgat_ln_bwd": lambda d, t: (p,) * 9 + (8, d, t, None),
+        "hwgat_ln_bwd_masked": lambda d, t: (p,) * 9 + (8, d, t, p, 1, 0.5, None, None),
+        "hwgat_ln_bwd_xn": lambda d, t: (p,) * 10 + (8, d, t, p, 1, 0.5, p, None, None),
+        "hwgat_ln_bwd_det": lambda d, t: (p,) * 10 + (8, d, t, p, 1, 0.5, p, None, p, 1 << 30, None),
+        "hwgat_lnpool_fwd": lambda d, t: (p, p, p, p, 1, 4, d, t, None),
+        "hwgat_lnpool_fwd_det": lambda d, t: (p, p, p, p, 1, 4, d, t, p, None),
+        "hwgat_lnpool_bwd": lambda d, t: (p,) * 5 + (1, 4, d, t, None),
+        "hwgat_lnpool_bwd_masked": lambda d, t: (p,) * 5 + (1, 4, d, t, p, 1, 0.5, None, None),
+    }
+    for name, args in ln.items():
+        for d in (100, 1088, 0):
+            assert getattr(L, name)(*args(d, 0)) == -2, (name, d)
+        for d in (100, 128, 192):
+            assert getattr(L, name)(*args(d, 9)) == -3, (name, d)
+    for t in (0, 9):        # a short workspace of the deterministic form: HWGAT_ESHAPE before anything about the dtype
+        assert L.hwgat_ln_bwd_det(*(p,) * 10, 8, 128, t, p, 1, 0.5, p, None, p, 16, None) == -2
 
 
 EINVAL, ESHAPE = -1, -2
