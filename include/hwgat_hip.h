@@ -80,7 +80,7 @@ extern "C" {
  *         later additions under the same number (additions only, no existing signature changed):
  *         hwgat_stream_{state_bytes,push,window,decide}, ring-buffered keypoint streams for serve.StreamRecognizer;
  *         hwgat_loader_{state_bytes,select,draw}, the device-resident clip store's shuffle and augmentation draw for
- *         data.DeviceLoader */
+ *         data.DeviceLoader; hwgat_attn_probs(_numel), the attention-map export of the five attention kinds */
 #define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
@@ -315,6 +315,33 @@ int hwgat_wband_attn_fwd_drop(const void* qkv, void* o, const uint32_t* maskrows
 int hwgat_wband_attn_bwd_drop(const void* qkv, const void* dO, void* dqkv, const uint32_t* maskrows, int B, int F, int nW,
                               int W, int nH, int hd, int dtype, uint32_t drop_seed, float drop_p,
                               const uint32_t* seed_base, void* stream);
+
+/* ---- attention-map export: the eval-mode probabilities the five fused forwards above multiply into V (no train-mode
+ * threshold, no attention dropout), written out instead of kept in registers, and / or their head-mean column sums.  An
+ * addition under ABI 4007 (no existing signature changed).
+ *   kind     one of HWGAT_ATTN_*; qkv (B, F, K, 3, nH, hd) `dtype` and `mask` are exactly what that kind's _fwd reads
+ *            (W = 16 for WIN / BAND, W = K for BLK); `shifted` as in the forward, ignored by the band kinds
+ *   probs    fp32, hwgat_attn_probs_numel(...) elements, or NULL.
+ *            pair kinds (WIN, PWIN, BLK): (B, F/2, nW, nH, n, n), n = 2 W, token = tp W + joint -- the reference's
+ *            (B f nW, nH, n, n) attention tensor element for element (the tensor the _drop entry points index); BLK has
+ *            nW = 1 and no pad slots.  In a shifted block window fi holds frames (2 fi + 1) % F and (2 fi + 2) % F.
+ *            band kinds (BAND, WBAND): (B, nW, nH, F, W, 3, W); [b][w][h][f][i][t][j] = the weight query joint i of frame f
+ *            gives key joint j of frame f - 1 + t; key frames outside the clip and masked entries are 0 (the whole of the
+ *            reference's dense (F W)^2 row outside the band is 0 in fp32), a WBAND row without a visible key is zeros.
+ *   received fp32 (B, F, K), or NULL: received[b][f][s] = (1 / nH) sum_h sum_q P_h[q -> key (f, s)], in the frame and slot
+ *            coordinates of the block's INPUT (the roll of a shifted block undone).  Computed without materialising P.
+ * probs and received must not both be NULL (HWGAT_EINVAL).  fp32 arithmetic for both storage dtypes.  No atomics: two runs
+ * are bit-equal and a clip's values do not depend on the batch around it.  HWGAT_ESHAPE for an unknown kind and for every
+ * shape the kind's _fwd refuses (hd: WIN 32 / 64 / 128, PWIN and BLK 32 / 64, BAND and WBAND 16 / 32; odd F for a pair
+ * kind; W outside 1..32; K % W != 0); the shape arguments are checked before any pointer is looked at. */
+#define HWGAT_ATTN_WIN 0   /* HWGATE, W = 16            mask (2,nW,32) u32   */
+#define HWGAT_ATTN_PWIN 1  /* HWGATE, any W <= 32       mask (2,nW,2W) u64   */
+#define HWGAT_ATTN_BLK 2   /* HGATE, W = KJ = K <= 32   mask (2,64,2) u32    */
+#define HWGAT_ATTN_BAND 3  /* WGATE, W = 16             mask (nW,16) u64     */
+#define HWGAT_ATTN_WBAND 4 /* GATE / WGATE W <= 32      mask (nW,32,3) u32   */
+int64_t hwgat_attn_probs_numel(int kind, int B, int F, int K, int W, int nH);
+int hwgat_attn_probs(int kind, const void* qkv, const void* mask, float* probs, float* received, int B, int F, int K,
+                     int W, int nH, int hd, int shifted, int dtype, void* stream);
 
 /* debug: one v_mfma_f32_16x16x4_f32 with a (16x4), b (4x16) row-major -> out (64 lanes x 4 regs) */
 int hwgat_debug_mfma16x16x4(const float* a, const float* b, float* out, void* stream);

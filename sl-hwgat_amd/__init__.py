@@ -24,8 +24,9 @@ from .models.STGCN import Model as STGCNModel
 from .models.DecoupledGCN import Model as DecoupledGCNModel
 from .models.model_params import (HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams, STGCNParams,
                                   DecoupledGCNParams)
+from . import explain
 
 __all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
            "TransformerModel",
            "TransformerParams", "STGCNModel", "STGCNParams", "DecoupledGCNModel", "DecoupledGCNParams", "functional",
-           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim", "data"]
+           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim", "data", "explain"]

@@ -59,6 +59,8 @@ _SIGS = {
     "hwgat_wband_attn_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "hwgat_wband_attn_fwd_drop": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _U, _F, _P, _P],
     "hwgat_wband_attn_bwd_drop": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _U, _F, _P, _P],
+    "hwgat_attn_probs_numel": [_I, _I, _I, _I, _I, _I],
+    "hwgat_attn_probs": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "hwgat_debug_mfma16x16x4": [_P, _P, _P, _P],
     "hwgat_lnpool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hwgat_lnpool_partial_rows": [_I, _I],
@@ -198,7 +200,7 @@ def lib():
         for name, args in _SIGS.items():
             fn = getattr(handle, name)
             fn.argtypes = args
-            fn.restype = _L if name.endswith("_bytes") else _I
+            fn.restype = _L if name.endswith(("_bytes", "_numel")) else _I
         have, want = handle.hwgat_abi_version(), header_abi_version()
         if have != want:
             raise RuntimeError(f"{LIB_PATH} reports ABI {have}, include/hwgat_hip.h declares {want}: rebuild the library")

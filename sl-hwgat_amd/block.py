@@ -19,7 +19,7 @@ all dropout masks are recomputed (masks are a hash of (seed, element index)).
 backward (4 dW/db GEMMs, 4 dX GEMMs, attention backward, 2 LN backward launches; where x needs no gradient -- the first
 block, fp32 -- 3 dX GEMMs, 1 LN backward launch and one small launch that turns dqkv^T xhat into norm1's and qkv's gradients).
 """
-from typing import Any, NamedTuple, Optional, Tuple
+from typing import Any, Callable, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -90,6 +90,7 @@ class BlockConfig(NamedTuple):
     prep: Optional[dict]                    # this block's entry of the call's functional.WeightPrep
     seed_base: Optional[torch.Tensor]
     deterministic_backward: bool            # fixed-order parameter gradients (functional.linear_tn / ln_backward)
+    tap: Optional[Callable] = None          # called with qkv right after it exists (explain.AttentionTap); None: no call
 
 
 class _FusedBlock(torch.autograd.Function):
@@ -125,6 +126,8 @@ class _FusedBlock(torch.autograd.Function):
         if m1 is None:
             m1, r1 = HF.ln_stats(x, n1w, n1b)
         qkv = HF.linear_nt_ln(x, wqkv, bqkv, (m1, r1, n1w, n1b), folded=prep.get("qkv_f"))
+        if cfg.tap is not None:
+            cfg.tap(qkv)                          # reads qkv only; without a tap the launches are exactly the ones below
         o = torch.empty_like(x)
         HF.attn_fwd(kind, qkv, o, bits, thr, n_heads, shifted, (seeds[3], attn_p, sb) if attn_p > 0.0 else None)
         wp_c = prep["wp_c"] if "wp_c" in prep else cw(wp)
@@ -261,7 +264,8 @@ class _FusedBlock(torch.autograd.Function):
 
 def fused_block(x, thr, blk, bits, n_heads, shifted, p, seeds, kind="win", stats=None, want_stats=False,
                 merge_out=False, return_stats=False, carrier=None, up=None, carry_out=False, return_carrier=None,
-                book=None, deterministic=False, attn_p=0.0, prep=None, seed_base=None, deterministic_backward=False):
+                book=None, deterministic=False, attn_p=0.0, prep=None, seed_base=None, deterministic_backward=False,
+                tap=None):
     """x (B,F,K,d) contiguous; `blk` holds norm1/attn.qkv/attn.proj/norm2/ff.fc1/ff.fc2.
     `kind`: a key of functional.ATTN_KINDS -- 'win' = HWGATE part windows (W = 16), 'pwin' = HWGATE part windows of any
     other size W <= 32, 'blk' = HGATE blocks, 'band' = WGATE (W = 16), 'wband' = GATE and WGATE with any other W <= 32;
@@ -280,6 +284,8 @@ def fused_block(x, thr, blk, bits, n_heads, shifted, p, seeds, kind="win", stats
     `deterministic_backward`: bit-reproducible parameter gradients (per-split / per-block partial images added in a fixed
     order instead of float atomics; token counts must be multiples of 32) -- with `deterministic` a whole train step repeats
     bit for bit, like the reference's on one device.
+    `tap`: None, or a callable the forward calls with this block's qkv (B,F,K,3d) right after the qkv linear, before the
+    attention launch (explain.AttentionTap exports the attention map from it); it must only read qkv.
     `deterministic`: bit-reproducible forward (eval mode): statistics / merged store stay in the epilogue only where a
     row collects at most two atomic partials.
     Returns out, or (out, (mean, rstd) or None) with `return_stats`; with `carry_out` / `return_carrier` the carrier (or None) is appended."""
@@ -294,7 +300,7 @@ def fused_block(x, thr, blk, bits, n_heads, shifted, p, seeds, kind="win", stats
                     want_stats=bool(want_stats), merge_out=bool(merge_out),
                     up=(int(up[0]), float(up[1])) if (up is not None and carrier is not None) else None,
                     carry_out=bool(carry_out), book=book, deterministic=bool(deterministic), attn_p=float(attn_p),
-                    prep=prep, seed_base=seed_base, deterministic_backward=bool(deterministic_backward)))
+                    prep=prep, seed_base=seed_base, deterministic_backward=bool(deterministic_backward), tap=tap))
     oc = oc if oc.numel() else None
     if return_carrier is None:
         return_carrier = bool(carry_out)

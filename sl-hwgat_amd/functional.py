@@ -348,6 +348,70 @@ def attn_bwd(kind, qkv, do, dqkv, bits, thr, n_heads, shifted, drop=None):
     _attn_launch("bwd", kind, qkv, (do, dqkv), bits, thr, n_heads, shifted, drop)
 
 
+ATTN_PROBS_CODE = {"win": 0, "pwin": 1, "blk": 2, "band": 3, "wband": 4}      # HWGAT_ATTN_* of include/hwgat_hip.h
+
+
+def _attn_probs_geom(kind, qkv, mask, n_heads):
+    """(B, F, K, W, nW, n_heads, head_dim) of an attn_probs call, through the kind's own `dims` helper (same refusals)"""
+    if qkv.dim() < 4:
+        raise ValueError("qkv must be (B, F, K, 3 d) or (B, F, K, 3, nH, hd)")
+    B, F, K = qkv.shape[:3]
+    d3 = qkv.numel() // max(1, B * F * K)
+    dims = _attn_kind(kind).dims((B, F, K, d3 // 3), mask, n_heads)
+    if kind in ("win", "band"):
+        _, _, nW, nH, hd = dims
+        W = 16
+    elif kind == "pwin":
+        _, _, _, W, nH, hd = dims
+        nW = K // W
+    elif kind == "blk":
+        _, _, _, nH, hd = dims
+        W, nW = K, 1
+    else:
+        _, _, nW, W, nH, hd = dims
+    return B, F, K, W, nW, nH, hd
+
+
+def attn_probs_shape(kind, B, F, K, W, n_heads):
+    """shape of the exported probability tensor: pair kinds (B, F/2, nW, nH, 2W, 2W), band kinds (B, nW, nH, F, W, 3, W)"""
+    nW = K // W
+    if kind in ("win", "pwin", "blk"):
+        return (B, F // 2, nW, n_heads, 2 * W, 2 * W)
+    return (B, nW, n_heads, F, W, 3, W)
+
+
+def attn_probs(kind, qkv, mask, n_heads, shifted=False, probs=True, received=True, out=None):
+    """the eval-mode attention probabilities of `kind` (a key of ATTN_KINDS) for the qkv tensor (B, F, K, 3 d) its fused
+    forward reads and the model's mask rows, written out by hwgat_attn_probs (csrc/attn_probs.hip) -> (probs | None,
+    received | None), both fp32.  probs: the reference's attention tensor -- pair kinds ('win', 'pwin', 'blk')
+    (B, F/2, nW, nH, n, n) with n = 2 W (in a shifted block window fi holds frames (2 fi + 1) % F, (2 fi + 2) % F:
+    explain.window_frames), band kinds ('band', 'wband') (B, nW, nH, F, W, 3, W) with [.., f, i, t, j] = query joint i of
+    frame f -> key joint j of frame f - 1 + t (explain.band_to_dense).  received (B, F, K): the head-mean column sums,
+    how much attention each joint of each frame of the block's input received; computed without materialising P.
+    `out` = (probs buffer | None, received buffer | None): write into these instead of allocating."""
+    if not (probs or received):
+        raise ValueError("attn_probs: ask for probs, received or both")
+    rec = _attn_kind(kind)
+    assert rec.takes_shifted or not shifted, rec.refusal
+    qkv = qkv.contiguous()
+    B, F, K, W, nW, nH, hd = _attn_probs_geom(kind, qkv, mask, n_heads)
+    code = ATTN_PROBS_CODE[kind]
+    p_buf, r_buf = out if out is not None else (None, None)
+    p = r = None
+    if probs:
+        shape = attn_probs_shape(kind, B, F, K, W, nH)
+        p = p_buf if p_buf is not None else torch.empty(shape, device=qkv.device, dtype=torch.float32)
+        if tuple(p.shape) != shape or p.dtype != torch.float32:
+            raise ValueError(f"probs buffer must be fp32 {shape}, got {p.dtype} {tuple(p.shape)}")
+    if received:
+        r = r_buf if r_buf is not None else torch.empty(B, F, K, device=qkv.device, dtype=torch.float32)
+        if tuple(r.shape) != (B, F, K) or r.dtype != torch.float32:
+            raise ValueError(f"received buffer must be fp32 {(B, F, K)}, got {r.dtype} {tuple(r.shape)}")
+    call("hwgat_attn_probs", code, ptr(qkv), ptr(mask), ptr(p), ptr(r), B, F, K, W, nH, hd, int(bool(shifted)),
+         dtype_code(qkv), stream())
+    return p, r
+
+
 class _Attn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, bits, thr, n_heads, shifted, drop, kind):

@@ -102,6 +102,7 @@ class FamilyModel(DeviceSeeds, nn.Module):
         self.part_index: Optional[torch.Tensor] = None           # set by use_part_table()
         self.activation_dtype = torch.float32
         self.threshold_override: Optional[List[float]] = None    # tests: inject train thresholds
+        self.attention_tap = None                                # explain.AttentionTap while armed (`with tap:`), else None
         self._init_device_seeds()
         if device is not None:
             self.to(device)
@@ -151,13 +152,15 @@ class FamilyModel(DeviceSeeds, nn.Module):
         carrier, up = (hand.carrier, hand.up) if (hand.of is h and hand.carrier is not None) else (None, None)
         want, merge = hand.plan.get(k, (False, False))
         seeds = self._site_seeds(k)
+        tap = getattr(self, "attention_tap", None)               # a model unpickled from before the field existed has none
         out, st, oc = fused_block(h, thr, blk, self._mask_bits, n_heads, shifted, p, seeds, self._attn_kind,
                                   stats=have, want_stats=want, merge_out=merge, return_stats=True,
                                   carrier=carrier, up=up, carry_out=(want or k == hand.last_block) and not merge,
                                   return_carrier=True, book=hand.book, deterministic=hand.deterministic,
                                   attn_p=self.attn_drop_rate if self.training else 0.0,
                                   prep=hand.prep.per_block[k] if hand.prep is not None else None,
-                                  seed_base=hand.seed_base, deterministic_backward=hand.deterministic and self.training)
+                                  seed_base=hand.seed_base, deterministic_backward=hand.deterministic and self.training,
+                                  tap=None if tap is None else tap.hook(k, n_heads, shifted))
         hand.of, hand.stats, hand.carrier, hand.up = out, st, oc, ((seeds[2], p) if oc is not None else None)
         return out
 
