@@ -80,7 +80,9 @@ extern "C" {
  *         later additions under the same number (additions only, no existing signature changed):
  *         hwgat_stream_{state_bytes,push,window,decide}, ring-buffered keypoint streams for serve.StreamRecognizer;
  *         hwgat_loader_{state_bytes,select,draw}, the device-resident clip store's shuffle and augmentation draw for
- *         data.DeviceLoader; hwgat_attn_probs(_numel), the attention-map export of the five attention kinds */
+ *         data.DeviceLoader; hwgat_attn_probs(_numel), the attention-map export of the five attention kinds;
+ *         hwgat_mix_{state_bytes,set,draw,apply}, Mixup and temporal CutMix of the pairs of a batch, and
+ *         hwgat_mbsce_{fwd,bwd}, the slice criterion with two targets and a weight per row (additions only) */
 #define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
@@ -982,6 +984,78 @@ int hwgat_loader_draw(const void* state, const float* frames, const int64_t* cli
                       int J, int C, double mask_p, double ratio_lo, double ratio_hi, double shear_std, double rotation_std,
                       int random_sample, int random_shift, void* stream);
 
+/* ---- Mixup and temporal CutMix of the pairs of a batch (train.BatchMixer, csrc/mix.hip).  Two launches in front of the
+ * train step's forward mix the step's static input buffer in place: hwgat_mix_draw matches the batch's live rows into
+ * pairs and draws every pair's decision, hwgat_mix_apply rewrites the rows.  Every value that changes between steps is
+ * a DEVICE word of the mixer state, so both replay in a HIP graph.  Hashes, perm and U are the loader's (above).
+ *
+ * state: hwgat_mix_state_bytes() = 40 bytes of DEVICE memory, 8-byte aligned (hwgat_mix_state): seed, step (the replay
+ *   counter), and the fp64 words prob, cutmix_share, mixup_alpha, cutmix_alpha.  The kernels reduce the alphas to
+ *   [HWGAT_MIX_ALPHA_MIN, 1] when they read them.
+ * hwgat_mix_set (one thread): writes the four hyper words from the host values given as arguments and, when
+ *   `set_counter` is not 0, seed and step as well; stream-ordered like hwgat_opt_set.  prob and cutmix_share outside
+ *   [0, 1] or an alpha outside [HWGAT_MIX_ALPHA_MIN, 1] (a NaN included) is HWGAT_ESHAPE.
+ *
+ * hwgat_mix_draw: ONE workgroup.  n = clamp(*n_rows, 0, B), a NULL n_rows means B.  With seed and step of the state:
+ *     K_step = mix32(seed, HWGAT_MIX_TAG * 2^32 + step)      (the loader's keys use the high words 0 and 1)
+ *     K_sigma = mix32(K_step, 0);   K_p = mix32(K_step, 1 + p), the key of pair p
+ *     U_p(tag, i) = (mix32(K_p + tag, i) + 0.5) / 2^32  in fp64 (exact), with the HWGAT_MIX_TAG_* below
+ *   matching: pair p < n / 2 (integer division) is the rows a = perm(K_sigma, n, 2 p) and b = perm(K_sigma, n, 2 p + 1): a
+ *     uniformly keyed perfect matching of the live rows.  With n odd the row perm(K_sigma, n, n - 1) has no partner; nor
+ *     has any row >= n.
+ *   per pair: mixed iff U_p(TAG_APPLY, 0) < prob; then CutMix iff U_p(TAG_MODE, 0) < cutmix_share, else Mixup;
+ *     alpha = cutmix_alpha or mixup_alpha accordingly; lambda0 ~ Beta(alpha, alpha) by Joehnk's method in fp64: for
+ *     k = 0 .. 63: X = pow(U_p(TAG_BETA, 2 k), 1 / alpha), Y = pow(U_p(TAG_BETA, 2 k + 1), 1 / alpha) (1 / alpha a rounded
+ *     fp64 quotient), S = X + Y; the first k with 0 < S <= 1 gives lambda0 = X / S; none in 64 tries: lambda0 = 0.5 (the
+ *     acceptance probability Gamma(alpha + 1)^2 / Gamma(2 alpha + 1) is at least 1/2 for alpha <= 1: the fallback has
+ *     probability <= 2^-64 and only bounds the loop; alpha >= 0.05 keeps U^(1 / alpha) >= 2^-640 above the denormals).
+ *     Mixup:  lambda = (float)lambda0, seg = (0, 0).
+ *     CutMix: L = clamp(floor((1 - lambda0) * T + 0.5), 0, T) (a rounded fp64 difference, product and sum: no FMA),
+ *             t0 = min(floor(U_p(TAG_START, 0) * (T - L + 1)), T - L), lambda = (float)((double)(T - L) / T), seg = (t0, L).
+ *   records, for every row r < B:
+ *     partner (B) int32   the other row of r's pair when the pair is mixed, else r
+ *     lam     (B) fp32    the pair's lambda for both of its rows; 1.0f when not mixed
+ *     seg     (B, 2) int32  (t0, L) of a CutMix pair for both rows, else (0, 0)
+ *     mode    (B) int32   HWGAT_MIX_NONE / HWGAT_MIX_MIXUP / HWGAT_MIX_CUTMIX
+ *     y_b     (B) int64   y[partner[r]]   (y (B) int64 is only read; y_b must not overlap it)
+ *   pairs (max(B / 2, 1), 2) int32: (a, b) for p < n / 2, (-1, -1) behind.  Every word has one writer.  After a workgroup
+ *   barrier one thread does step += 1 (32-bit wrap).
+ *   1 <= B <= HWGAT_MIX_MAX_BATCH, 1 <= T <= 2^20, else HWGAT_ESHAPE.
+ *
+ * hwgat_mix_apply: x (B, T, R) fp32 contiguous, R the product of the trailing dims; in place.  Pair p < n / 2 with rows
+ *   (a, b) = pairs[p] -- a pair with a row outside [0, n) or a == b is skipped -- and mode[a]:
+ *     Mixup:  w = fsub_rn(1, lambda); every element:  a' = fadd_rn(fmul_rn(lambda, a), fmul_rn(w, b)),
+ *             b' = fadd_rn(fmul_rn(lambda, b), fmul_rn(w, a)): separately rounded fp32 products and sum, no FMA.
+ *     CutMix: frames [t0, t0 + L) of the two rows are swapped ((t0, L) = seg[a] reduced to 0 <= t0 <= T, 0 <= L <= T - t0);
+ *             no other element is read or written.
+ *     none:   the pair is not touched; nor is any row >= n or the unpaired row.
+ *   A pair is symmetric, so one thread reads an element of both rows and writes both: each element has one reader and
+ *   one writer, which is what makes the in-place form safe.  16-byte accesses where both rows' segments share their
+ *   alignment (always when T * R % 4 == 0) with a scalar head and tail up to the 16-byte boundaries, scalar throughout
+ *   otherwise.  No atomics; bit-reproducible.  1 <= B <= HWGAT_MIX_MAX_BATCH, 1 <= T <= 2^20,
+ *   1 <= R, T * R < 2^31, else HWGAT_ESHAPE. */
+#define HWGAT_MIX_MAX_BATCH 65536
+#define HWGAT_MIX_ALPHA_MIN 0.05
+#define HWGAT_MIX_TAG 2
+#define HWGAT_MIX_TAG_APPLY 0x10
+#define HWGAT_MIX_TAG_MODE 0x20
+#define HWGAT_MIX_TAG_BETA 0x30
+#define HWGAT_MIX_TAG_START 0x40
+#define HWGAT_MIX_NONE 0
+#define HWGAT_MIX_MIXUP 1
+#define HWGAT_MIX_CUTMIX 2
+typedef struct {
+    uint32_t seed, step;
+    double prob, cutmix_share, mixup_alpha, cutmix_alpha;
+} hwgat_mix_state;                              /* 40 bytes */
+int64_t hwgat_mix_state_bytes(void);
+int hwgat_mix_set(void* state, double prob, double cutmix_share, double mixup_alpha, double cutmix_alpha, int set_counter,
+                  uint32_t seed, uint32_t step, void* stream);
+int hwgat_mix_draw(void* state, const int64_t* y, const int32_t* n_rows, int32_t* pairs, int32_t* partner, float* lam,
+                   int32_t* seg, int32_t* mode, int64_t* y_b, int B, int T, void* stream);
+int hwgat_mix_apply(float* x, const int32_t* pairs, const float* lam, const int32_t* seg, const int32_t* mode,
+                    const int32_t* n_rows, int B, int T, int64_t R, void* stream);
+
 /* ---- Transformer baseline (ABI 4004; reference hwgat/models/Transformer.py).  Activations (B, T, d) with d = nH * 64.
  *
  * hwgat_seq_attn_fwd: multi-head attention of nn.MultiheadAttention(batch_first=True) with a key-padding mask over the
@@ -1197,6 +1271,28 @@ int hwgat_bsce_fwd(const float* logits, const int64_t* target, const int32_t* n_
                    int C, float eps, void* stream);
 int hwgat_bsce_bwd(const float* logits, const int64_t* target, const int32_t* n_rows, int64_t offset, const float* lse,
                    const float* g, float* dlogits, int64_t B, int C, float eps, void* stream);
+
+/* ---- the slice criterion with two targets and a weight per row (train.MixedCrossEntropyLoss: Mixup / CutMix targets).
+ * Arguments, live rows, dead rows, `offset`, the empty slice and bad targets are hwgat_bsce_*'s, word for word; target_b (B)
+ * int64 and lam (B) fp32 are slice pointers like target.  With l(t) the row loss hwgat_bsce_fwd computes for target t:
+ * hwgat_mbsce_fwd (four launches: v, the rows under target, the rows under target_b, the sums):
+ *   row_loss_b, rank_b (B): l(target_b) and target_b's rank of the live rows, hwgat_sce_fwd's bit for bit
+ *   row_loss[b] = fadd_rn(fmul_rn(lam, l(t)), fmul_rn(fsub_rn(1, lam), l(t_b))): a row with lam == 1.0f and a finite l(t_b)
+ *                 has hwgat_bsce_fwd's bits
+ *   rank[b]     = the rank of the DOMINANT label: target's when lam >= 0.5f, else target_b's;  pred, lse: hwgat_sce_fwd's
+ *   loss[0], correct[0], live[0]: hwgat_bsce_fwd's sums over row_loss and rank as above, in the same fixed order
+ * hwgat_mbsce_bwd: dlogits[b, j] = g[0] / *n_rows * (exp(z[b, j] - lse[b]) - (1 - eps) (lam [j == t] + (1 - lam) [j == t_b])
+ *   - eps / C) for a live row, exactly 0.0f for every other; a live row with a bad target or target_b is NaN throughout.
+ *   The bracket is formed as fmul_rn(1 - eps, fadd_rn(lam [j == t], fsub_rn(1, lam) [j == t_b])): where t == t_b the column
+ *   gets (1 - eps)(lam + (1 - lam)), and that fp32 sum need not be exactly 1 -- such a row may differ from hwgat_bsce_bwd's
+ *   in the last bit unless lam is 0 or 1.  A row with lam == 1.0f has hwgat_bsce_bwd's bits.  No float atomic anywhere. */
+int hwgat_mbsce_fwd(const float* logits, const int64_t* target, const int64_t* target_b, const float* lam,
+                    const int32_t* n_rows, int64_t offset, float* lse, float* row_loss, int32_t* rank, int32_t* pred,
+                    float* loss, int64_t* correct, int32_t* live, float* row_loss_b, int32_t* rank_b, int64_t B, int C,
+                    float eps, void* stream);
+int hwgat_mbsce_bwd(const float* logits, const int64_t* target, const int64_t* target_b, const float* lam,
+                    const int32_t* n_rows, int64_t offset, const float* lse, const float* g, float* dlogits, int64_t B,
+                    int C, float eps, void* stream);
 
 /* ---- the classifier head (csrc/head.hip; reference: the `head` / `classifier` nn.Linear of every model,
  * hwgat/models/HWGATE.py:331,372).  Everything fp32 and row-major; W is (N, K) as nn.Linear stores it.

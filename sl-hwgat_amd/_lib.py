@@ -152,6 +152,12 @@ _SIGS = {
     "hwgat_loader_state_bytes": [],
     "hwgat_loader_select": [_P] * 9 + [_I, _L, _I, _I, _P],
     "hwgat_loader_draw": [_P] * 11 + [_I, _L, _I, _I, _I, _I, _I, _D, _D, _D, _D, _D, _I, _I, _P],
+    "hwgat_mix_state_bytes": [],
+    "hwgat_mix_set": [_P, _D, _D, _D, _D, _I, _U, _U, _P],
+    "hwgat_mix_draw": [_P] * 9 + [_I, _I, _P],
+    "hwgat_mix_apply": [_P] * 6 + [_I, _I, _L, _P],
+    "hwgat_mbsce_fwd": [_P, _P, _P, _P, _P, _L] + [_P] * 9 + [_L, _I, _F, _P],
+    "hwgat_mbsce_bwd": [_P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _I, _F, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

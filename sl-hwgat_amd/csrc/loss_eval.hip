@@ -11,6 +11,9 @@
 //                          on those rows, bsce_sum_k (one workgroup) adds their losses in a fixed order, divides by the
 //                          BATCH's row count and counts the live rows whose target ranks first.
 //   hwgat_bsce_bwd         bsce_bwd_k: sce_bwd_k with the batch's row count as the divisor; exact zeros for the other rows.
+//   hwgat_mbsce_fwd / _bwd the same slice with two targets and a weight per row (train.MixedCrossEntropyLoss): sce_fwd_k
+//                          once per target, mbsce_sum_k blends the row losses and sums; mbsce_bwd_k is bsce_bwd_k with the
+//                          one-hot replaced by lam [j == t] + (1 - lam) [j == t_b].
 //
 // No float or double atomic anywhere: every floating-point sum is a per-thread strided sum followed by a fixed butterfly
 // and a fixed combination of the four waves, so every output is bit-reproducible.  The integer counters of the
@@ -270,6 +273,92 @@ __global__ __launch_bounds__(SCE_THREADS) void bsce_bwd_k(const float* __restric
     }
 }
 
+// l a + (1 - l) b and h (p + q) with every operation rounded on its own (the header's __fmul_rn / __fadd_rn are plain
+// operators that the compiler may contract to an FMA: contraction is switched off for these bodies instead)
+__device__ __forceinline__ float blend_rn(float l, float a, float b) {
+#pragma clang fp contract(off)
+    const float w = 1.f - l;
+    const float x = l * a, y = w * b;
+    return x + y;
+}
+__device__ __forceinline__ float scaled_sum_rn(float h, float p, float q) {
+#pragma clang fp contract(off)
+    const float s = p + q;
+    return h * s;
+}
+
+// ---- the same slice with two targets and a weight per row (hwgat_mbsce_*: Mixup / CutMix targets).  sce_fwd_k runs once per
+// target; mbsce_sum_k blends the two row losses, keeps the dominant label's rank and then sums as bsce_sum_k does
+__global__ __launch_bounds__(SCE_THREADS) void mbsce_sum_k(float* __restrict__ row_loss, const float* __restrict__ row_loss_b,
+                                                          int32_t* __restrict__ rank, const int32_t* __restrict__ rank_b,
+                                                          const float* __restrict__ lam, const int32_t* __restrict__ n_rows,
+                                                          float* __restrict__ loss, int64_t* __restrict__ correct,
+                                                          int64_t offset, int64_t B) {
+    __shared__ float red_f[4];
+    __shared__ int red_i[4];
+    const int64_t v = live_rows(n_rows, offset, B);
+    float s = 0.f;
+    int hit = 0;
+    for (int64_t i = threadIdx.x; i < v; i += SCE_THREADS) {
+        const float l = lam[i];
+        const float r = blend_rn(l, row_loss[i], row_loss_b[i]);
+        const int k = l >= 0.5f ? rank[i] : rank_b[i];        // the dominant label's
+        row_loss[i] = r;
+        rank[i] = k;
+        s += r;
+        hit += k == 0;
+    }
+    s = block_sum(s, red_f);
+    hit = block_sum(hit, red_i);
+    if (threadIdx.x == 0) {
+        loss[0] = v > 0 ? s / (float)*n_rows : 0.f;
+        correct[0] = hit;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(SCE_THREADS) void mbsce_bwd_k(const float* __restrict__ z, const int64_t* __restrict__ target,
+                                                          const int64_t* __restrict__ target_b,
+                                                          const float* __restrict__ lam, const int32_t* __restrict__ n_rows,
+                                                          const float* __restrict__ lse, const float* __restrict__ g,
+                                                          float* __restrict__ dz, int64_t offset, int64_t B, int C, float eps) {
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* zr = z + b * C;
+    float* dr = dz + b * C;
+    const bool live = b < live_rows(n_rows, offset, B);
+    const int64_t t64 = live ? target[b] : 0, u64 = live ? target_b[b] : 0;
+    const bool t_ok = t64 >= 0 && t64 < C && u64 >= 0 && u64 < C;
+    const int t = t_ok ? (int)t64 : -1, u = t_ok ? (int)u64 : -1;      // -1 matches no column
+    const float fill = live ? NAN : 0.f;         // a live row gets here only with a bad target
+    if (!live || !t_ok) {
+        for (int j = tid; j < C; j += SCE_THREADS) dr[j] = fill;
+        return;
+    }
+    const float scale = g[0] / (float)*n_rows;   // a live row implies *n_rows >= 1
+    const float l = lse[b];
+    const float hit = 1.f - eps, flat = eps / (float)C;
+    const float wa = lam[b], wb = 1.f - wa;
+#define MBSCE_HIT(j) (scaled_sum_rn(hit, (j) == t ? wa : 0.f, (j) == u ? wb : 0.f))
+    if (VEC) {
+        const f32x4* zr4 = reinterpret_cast<const f32x4*>(zr);
+        f32x4* dr4 = reinterpret_cast<f32x4*>(dr);
+        for (int q = tid; q < C / 4; q += SCE_THREADS) {
+            const f32x4 v = zr4[q];
+            const int j = 4 * q;
+            f32x4 d;
+            d.x = scale * (expf(v.x - l) - MBSCE_HIT(j) - flat);
+            d.y = scale * (expf(v.y - l) - MBSCE_HIT(j + 1) - flat);
+            d.z = scale * (expf(v.z - l) - MBSCE_HIT(j + 2) - flat);
+            d.w = scale * (expf(v.w - l) - MBSCE_HIT(j + 3) - flat);
+            dr4[q] = d;
+        }
+    } else {
+        for (int j = tid; j < C; j += SCE_THREADS) dr[j] = scale * (expf(zr[j] - l) - MBSCE_HIT(j) - flat);
+    }
+#undef MBSCE_HIT
+}
+
 // accumulator block, in 8-byte words (hwgat_hip.h documents the same offsets)
 constexpr int ACC_N_SAMPLES = 0, ACC_N_BATCHES = 1, ACC_N_INVALID = 2, ACC_LOSS_SAMPLES = 3, ACC_LOSS_BATCHES = 4,
               ACC_RANK_HIST = 5;
@@ -400,5 +489,34 @@ extern "C" int hwgat_bsce_bwd(const float* logits, const int64_t* target, const 
         bsce_bwd_k<true><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_rows, lse, g, dlogits, offset, B, C, eps);
     else
         bsce_bwd_k<false><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, n_rows, lse, g, dlogits, offset, B, C, eps);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_mbsce_fwd(const float* logits, const int64_t* target, const int64_t* target_b, const float* lam,
+                               const int32_t* n_rows, int64_t offset, float* lse, float* row_loss, int32_t* rank,
+                               int32_t* pred, float* loss, int64_t* correct, int32_t* live, float* row_loss_b,
+                               int32_t* rank_b, int64_t B, int C, float eps, void* stream) {
+    if (!logits || !target || !target_b || !lam || !n_rows || !lse || !row_loss || !rank || !pred || !loss || !correct ||
+        !live || !row_loss_b || !rank_b || bad_offset(offset))
+        return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    bsce_live_k<<<1, 64, 0, st>>>(n_rows, live, offset, B);
+    launch_sce_rows(logits, target_b, live, lse, row_loss_b, rank_b, pred, B, C, eps, st);
+    launch_sce_rows(logits, target, live, lse, row_loss, rank, pred, B, C, eps, st);      // lse and pred: the same bits again
+    mbsce_sum_k<<<1, SCE_THREADS, 0, st>>>(row_loss, row_loss_b, rank, rank_b, lam, n_rows, loss, correct, offset, B);
+    HWGAT_LAUNCH_CHECK();
+}
+
+extern "C" int hwgat_mbsce_bwd(const float* logits, const int64_t* target, const int64_t* target_b, const float* lam,
+                               const int32_t* n_rows, int64_t offset, const float* lse, const float* g, float* dlogits,
+                               int64_t B, int C, float eps, void* stream) {
+    if (!logits || !target || !target_b || !lam || !n_rows || !lse || !g || !dlogits || bad_offset(offset)) return HWGAT_EINVAL;
+    if (bad_shape(B, C)) return HWGAT_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (C % 4 == 0 && aligned16(logits) && aligned16(dlogits))
+        mbsce_bwd_k<true><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, target_b, lam, n_rows, lse, g, dlogits, offset, B, C, eps);
+    else
+        mbsce_bwd_k<false><<<(unsigned)B, SCE_THREADS, 0, st>>>(logits, target, target_b, lam, n_rows, lse, g, dlogits, offset, B, C, eps);
     HWGAT_LAUNCH_CHECK();
 }

@@ -1781,3 +1781,126 @@ def loader_draw(state, frames, clip_off, norm, ids, keys, batch_off, clip, maske
          ptr(clip), ptr(masked), ptr(src), ptr(prm), n, frames.shape[0], B, int(max_frames), src.shape[1], J, C,
          float(mask_p), float(ratio[0]), float(ratio[1]), float(shear_std), float(rotation_std), int(bool(random_sample)),
          int(bool(random_shift)), stream())
+
+
+# ---------------------------------------------------------------- Mixup / temporal CutMix (csrc/mix.hip, train.BatchMixer)
+# The mixer state is hwgat_mix_state of include/hwgat_hip.h kept as int64 words: word 0 holds seed (low half) and step (high
+# half), words 1..4 the fp64 hyper words prob, cutmix_share, mixup_alpha, cutmix_alpha.
+MIX_STATE_WORDS = 5
+MIX_MAX_BATCH, MIX_ALPHA_MIN = 65536, 0.05     # HWGAT_MIX_MAX_BATCH, HWGAT_MIX_ALPHA_MIN
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+
+
+def mix_state(device):
+    """a zeroed mixer state block on `device` (write it with mix_set before the first draw)"""
+    if 8 * MIX_STATE_WORDS != _lib.lib().hwgat_mix_state_bytes():
+        raise RuntimeError("the library lays the mixer state out differently from functional.py's constants")
+    return torch.zeros(MIX_STATE_WORDS, dtype=torch.int64, device=device)
+
+
+def _mix_state_check(state):
+    if state.dtype != torch.int64 or state.numel() < MIX_STATE_WORDS:
+        raise ValueError(f"the mixer state must be int64 with {MIX_STATE_WORDS} words")
+
+
+def mix_set(state, prob, cutmix_share, mixup_alpha, cutmix_alpha, seed=None, step=0):
+    """write the four hyper words and, with a `seed`, the seed and the step counter.  One tiny launch, stream-ordered"""
+    _mix_state_check(state)
+    if seed is not None and not (0 <= int(seed) < 2 ** 32 and 0 <= int(step) < 2 ** 32):
+        raise ValueError(f"seed and step must be in [0, 2^32), got {seed}, {step}")
+    call("hwgat_mix_set", ptr(state), float(prob), float(cutmix_share), float(mixup_alpha), float(cutmix_alpha),
+         int(seed is not None), 0 if seed is None else int(seed), int(step) if seed is not None else 0, stream())
+
+
+def _mix_records(B, pairs, partner, lam, seg, mode):
+    for name, t, dt, n in (("pairs", pairs, torch.int32, 2 * max(B // 2, 1)), ("partner", partner, torch.int32, B),
+                           ("lam", lam, torch.float32, B), ("seg", seg, torch.int32, 2 * B), ("mode", mode, torch.int32, B)):
+        if t is not None and (t.dtype != dt or t.numel() != n):
+            raise ValueError(f"{name} must be {dt} with {n} elements for a batch of {B}")
+
+
+def mix_draw(state, y, n_rows, pairs, partner, lam, seg, mode, y_b, T):
+    """one step's matching and decisions from the mixer state: pairs (max(B // 2, 1), 2), partner (B), seg (B, 2), mode (B)
+    int32, lam (B) fp32, y_b (B) int64 = y[partner]; `n_rows` a device int32 word or None (all B rows are live); advances
+    the state's step counter.  One launch; nothing is read back"""
+    _mix_state_check(state)
+    B = y.numel()
+    if y.dtype != torch.int64 or y_b.dtype != torch.int64 or y_b.numel() != B:
+        raise ValueError(f"y and y_b must be int64 with {B} elements")
+    if n_rows is not None and (n_rows.dtype != torch.int32 or n_rows.numel() != 1):
+        raise ValueError("n_rows must be a device int32 tensor of one element")
+    _mix_records(B, pairs, partner, lam, seg, mode)
+    call("hwgat_mix_draw", ptr(state), ptr(y), ptr(n_rows), ptr(pairs), ptr(partner), ptr(lam), ptr(seg), ptr(mode), ptr(y_b),
+         B, int(T), stream())
+
+
+def mix_apply(x, pairs, lam, seg, mode, n_rows=None):
+    """mix the rows of x (B, T, ...) fp32 in place as the records of mix_draw say.  One launch (none for B == 1)"""
+    if x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError(f"x must be fp32 (B, T, ...), got {x.dtype} {tuple(x.shape)}")
+    B, T = x.shape[:2]
+    _mix_records(B, pairs, None, lam, seg, mode)
+    if n_rows is not None and (n_rows.dtype != torch.int32 or n_rows.numel() != 1):
+        raise ValueError("n_rows must be a device int32 tensor of one element")
+    call("hwgat_mix_apply", ptr(x), ptr(pairs), ptr(lam), ptr(seg), ptr(mode), ptr(n_rows), B, T, x[0, 0].numel(), stream())
+
+
+# ---- the slice criterion with two targets: target_b (B,) int64 and lam (B,) fp32 are slices of the mixer's records
+def _mbsce_check(logits, target, target_b, lam, n_rows, offset):
+    _bsce_check(logits, target, n_rows, offset)
+    if target_b.dtype != torch.int64 or target_b.shape != target.shape:
+        raise ValueError(f"target_b must be int64 {tuple(target.shape)}, got {target_b.dtype} {tuple(target_b.shape)}")
+    if lam.dtype != torch.float32 or lam.shape != target.shape:
+        raise ValueError(f"lam must be fp32 {tuple(target.shape)}, got {lam.dtype} {tuple(lam.shape)}")
+
+
+def mbsce_forward(logits, target, target_b, lam, eps, n_rows, offset, out=None):
+    """bsce_forward with two targets and a weight per row: (loss, row_loss, lse, rank, pred, correct, live, row_loss_b,
+    rank_b); row_loss is lam l(t) + (1 - lam) l(t_b), rank the dominant label's (t when lam >= 0.5), row_loss_b / rank_b (B,)
+    the partner label's own.  `out` takes the same nine tensors preallocated"""
+    _mbsce_check(logits, target, target_b, lam, n_rows, offset)
+    B, C = logits.shape
+    if out is None:
+        f = torch.empty(3 * B + 1, device=logits.device, dtype=torch.float32)
+        i = torch.empty(3 * B + 1, device=logits.device, dtype=torch.int32)
+        out = (f[3 * B:], f[:B], f[B:2 * B], i[:B], i[B:2 * B], torch.empty(1, device=logits.device, dtype=torch.int64),
+               i[3 * B:], f[2 * B:3 * B], i[2 * B:3 * B])
+    loss, row_loss, lse, rank, pred, correct, live, row_loss_b, rank_b = out
+    call("hwgat_mbsce_fwd", ptr(logits), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(lse),
+         ptr(row_loss), ptr(rank), ptr(pred), ptr(loss), ptr(correct), ptr(live), ptr(row_loss_b), ptr(rank_b), B, C,
+         float(eps), stream())
+    return out
+
+
+def mbsce_backward(logits, target, target_b, lam, lse, g, eps, n_rows, offset, out=None):
+    """d loss / d logits of mbsce_forward times the device scalar `g`; exactly zero in the dead rows"""
+    _mbsce_check(logits, target, target_b, lam, n_rows, offset)
+    B, C = logits.shape
+    dz = torch.empty_like(logits) if out is None else out
+    call("hwgat_mbsce_bwd", ptr(logits), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(lse), ptr(g),
+         ptr(dz), B, C, float(eps), stream())
+    return dz
+
+
+class _MixedSlicedCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, target_b, lam, eps, n_rows, offset):
+        loss, _, lse, rank, pred, correct = mbsce_forward(logits, target, target_b, lam, eps, n_rows, offset)[:6]
+        ctx.save_for_backward(logits, target, target_b, lam, lse)
+        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
+        ctx.mark_non_differentiable(rank, pred, correct)
+        return loss.view(()), rank, pred, correct.view(())
+
+    @staticmethod
+    def backward(ctx, g, _rank, _pred, _correct):
+        logits, target, target_b, lam, lse = ctx.saved_tensors
+        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
+        dz = mbsce_backward(logits, target, target_b, lam, lse, g, ctx.eps, ctx.n_rows, ctx.offset)
+        return dz, None, None, None, None, None, None
+
+
+def mixed_sliced_ce(logits, target, target_b, lam, eps, n_rows, offset):
+    """(loss, rank, pred, correct): batch_sliced_ce with the pair target -- lam l(target) + (1 - lam) l(target_b) per row,
+    rank and correct on the dominant label -- as an autograd node (forward four launches, backward one)"""
+    return _MixedSlicedCE.apply(logits.float().contiguous(), target.contiguous(), target_b.contiguous(), lam.contiguous(),
+                                float(eps), n_rows, int(offset))

@@ -74,6 +74,197 @@ class BatchSlicedCrossEntropyLoss(torch.nn.Module):
         return self._hits
 
 
+class MixedCrossEntropyLoss(BatchSlicedCrossEntropyLoss):
+    """BatchSlicedCrossEntropyLoss for a batch a `BatchMixer` has mixed (hwgat_mbsce_fwd / hwgat_mbsce_bwd of
+    csrc/loss_eval.hip): row r's loss is lam[r] l(y[r]) + (1 - lam[r]) l(y_b[r]), with the mixer's records `lam` and `y_b`
+    of the latest draw read at the slice's place, `mixer.y_b[offset:offset + b]`.  A row the mixer left alone has lam 1 and
+    the parent's bits.  `last_rank` and `correct()` refer to the dominant label (y[r] when lam[r] >= 0.5, else y_b[r]).
+    The step that owns the batch binds the mixer (`bind_mixer`) and calls `place(n_rows, offset)` before each slice."""
+
+    def __init__(self, smooth_factor: float = 0.01, mixer=None):
+        super().__init__(smooth_factor)
+        self.mixer = mixer
+
+    def bind_mixer(self, mixer):
+        if self.mixer is not None and self.mixer is not mixer:
+            raise ValueError("MixedCrossEntropyLoss is bound to another BatchMixer: one criterion serves one mixer")
+        self.mixer = mixer
+
+    def forward(self, input, target):
+        if self.n_rows is None or self.mixer is None or self.mixer.y_b is None:
+            raise RuntimeError("MixedCrossEntropyLoss: bind_mixer(mixer), mixer.apply(...) and place(n_rows, offset) first -- "
+                               "TrainStep(mixer=...) and GraphedTrainStep(mixer=...) do")
+        b, o = input.shape[0], self.offset
+        if o + b > self.mixer.y_b.shape[0]:
+            raise ValueError(f"the slice [{o}, {o + b}) lies outside the mixer's batch of {self.mixer.y_b.shape[0]} rows")
+        loss, self.last_rank, self.last_pred, self._hits = _functional().mixed_sliced_ce(
+            input, target, self.mixer.y_b[o:o + b], self.mixer.lam[o:o + b], self.smooth_factor, self.n_rows, o)
+        return loss
+
+
+def _unit(name, v, lo=0.0):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not lo <= v <= 1.0:     # a NaN fails the comparison
+        raise ValueError(f"BatchMixer: {name} must be a number in [{lo}, 1], got {v!r}")
+    return float(v)
+
+
+class BatchMixer:
+    """Mixup and temporal CutMix of the clips of a batch, inside the train step (csrc/mix.hip; formulas: include/hwgat_hip.h,
+    "Mixup and temporal CutMix").  Every step the live rows are matched into random pairs; a pair is mixed with
+    probability `prob`, by CutMix with probability `cutmix_share` (frames [t0, t0 + L) of the two clips are swapped), else
+    by Mixup (lam a + (1 - lam) b and its mirror), lam from Beta(alpha, alpha).  Targets become the pair (y, y_b) with the
+    weight `lam` per row, which `MixedCrossEntropyLoss` takes.
+
+        mixer = train.BatchMixer(mixup_alpha=0.4, cutmix_alpha=1.0, prob=1.0, cutmix_share=0.5, seed=0)
+        step = train.GraphedTrainStep(model, opt, x, y, ragged=True, mixer=mixer)
+        mixer.prob = 0.0                         # the last epochs unmixed: the next step's launch, no new capture
+
+    The draw is a counter-based hash of (seed, step), `step` a device word every draw advances, so the two launches replay
+    in a graph and a run is reproducible.  The hyper-parameters are plain attributes; when one changed, one hwgat_mix_set
+    launch carries them to the device before the next step (as `push_hyper` does for the optimizers).  Alphas are limited
+    to [0.05, 1] (Joehnk's sampler needs alpha <= 1; below 0.05 its powers leave the doubles).  `seed` and `step` may be set
+    before or after `bind` (after it, setting either is one hwgat_mix_set launch); reading `step` after `bind` is a host
+    read of the device word.  A mixer serves one batch shape `(B, T)`, fixed by `bind`."""
+
+    def __init__(self, mixup_alpha=0.4, cutmix_alpha=1.0, prob=1.0, cutmix_share=0.5, seed=0):
+        self.mixup_alpha, self.cutmix_alpha, self.prob, self.cutmix_share = mixup_alpha, cutmix_alpha, prob, cutmix_share
+        self._hyper()
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"BatchMixer: seed must be an integer in [0, 2^32), got {seed!r}")
+        self._state = self._pushed = None
+        self._seed, self._step = int(seed), 0
+        self.pairs = self.partner = self.lam = self.seg = self.mode = self.y_b = None
+        self.B = self.T = None
+
+    def _hyper(self):
+        """the four hyper-parameters, validated, in the order of the device words"""
+        return (_unit("prob", self.prob), _unit("cutmix_share", self.cutmix_share),
+                _unit("mixup_alpha", self.mixup_alpha, 0.05), _unit("cutmix_alpha", self.cutmix_alpha, 0.05))
+
+    # ---- device side
+    def bind(self, device, B, T):
+        """allocate the state block and the per-row records for batches of B clips of T frames (once)"""
+        if self._state is not None:
+            if (self.B, self.T) != (int(B), int(T)):
+                raise ValueError(f"BatchMixer is bound to batches of ({self.B}, {self.T}, ...), got ({B}, {T}, ...): a mixer "
+                                 "serves one batch shape -- pad short batches (TrainStep(pad_to=...), "
+                                 "GraphedTrainStep(ragged=True)) or drop them")
+            return self
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("BatchMixer needs an MI355X device; there is no CPU fallback")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("BatchMixer: bind() before capturing")
+        HF = _functional()
+        if not 1 <= int(B) <= HF.MIX_MAX_BATCH or int(T) < 1:
+            raise ValueError(f"BatchMixer: no batch of {B} clips of {T} frames (at most {HF.MIX_MAX_BATCH} clips)")
+        hyper = self._hyper()
+        self.B, self.T = int(B), int(T)
+        i32 = torch.zeros(2 * max(self.B // 2, 1) + 4 * self.B, dtype=torch.int32, device=device)
+        npair = 2 * max(self.B // 2, 1)
+        self.pairs = i32[:npair].view(-1, 2)
+        self.partner, self.mode = i32[npair:npair + self.B], i32[npair + self.B:npair + 2 * self.B]
+        self.seg = i32[npair + 2 * self.B:].view(self.B, 2)
+        self.lam = torch.ones(self.B, dtype=torch.float32, device=device)
+        self.y_b = torch.zeros(self.B, dtype=torch.int64, device=device)
+        self._state = HF.mix_state(device)
+        HF.mix_set(self._state, *hyper, seed=self.seed, step=self._step)
+        self._pushed = hyper
+        return self
+
+    @property
+    def seed(self):
+        return self._seed
+
+    @seed.setter
+    def seed(self, v):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v < 2 ** 32:
+            raise ValueError(f"BatchMixer: seed must be an integer in [0, 2^32), got {v!r}")
+        if self._state is not None:                          # the counter goes on where the device has it
+            self._step = self.step
+        self._seed = int(v)
+        self._write_counter()
+
+    def _write_counter(self):
+        """seed, step and the hyper words to the device, when there is one"""
+        if self._state is not None:
+            self._pushed = self._hyper()
+            _functional().mix_set(self._state, *self._pushed, seed=self._seed, step=self._step)
+
+    @property
+    def step(self):
+        """the number of draws so far: the device word once bound (a host read), else the value the first draw starts at"""
+        if self._state is None:
+            return self._step
+        return int(self._state[:1].cpu().numpy().view(np.uint32)[1])
+
+    @step.setter
+    def step(self, c):
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= c < 2 ** 32:
+            raise ValueError(f"BatchMixer: step must be an integer in [0, 2^32), got {c!r}")
+        self._step = int(c)
+        self._write_counter()
+
+    def push_hyper(self):
+        """one launch when a hyper-parameter changed since the last one, none otherwise"""
+        hyper = self._hyper()
+        if self._state is not None and hyper != self._pushed:
+            _functional().mix_set(self._state, *hyper)
+            self._pushed = hyper
+
+    def apply(self, x, y, n_rows=None):
+        """draw + apply: mix x (B, T, ...) fp32 in place and leave the records of the step (`partner`, `lam`, `seg`, `mode`,
+        `y_b`, `pairs`) on the device; `n_rows`: the device int32 word with the live row count, or None (all rows)"""
+        self.bind(x.device, x.shape[0], x.shape[1])
+        if not torch.cuda.is_current_stream_capturing():         # a captured step pushes before each replay instead
+            self.push_hyper()
+        HF = _functional()
+        HF.mix_draw(self._state, y, n_rows, self.pairs, self.partner, self.lam, self.seg, self.mode, self.y_b, self.T)
+        HF.mix_apply(x, self.pairs, self.lam, self.seg, self.mode, n_rows)
+
+    def records(self):
+        """the latest draw's records as numpy arrays (one sync): partner, lam, seg, mode, y_b, pairs"""
+        if self._state is None:
+            raise RuntimeError("BatchMixer has drawn nothing yet: its records live on the device of its first step (or bind())")
+        return dict(partner=self.partner.cpu().numpy(), lam=self.lam.cpu().numpy(), seg=self.seg.cpu().numpy(),
+                    mode=self.mode.cpu().numpy(), y_b=self.y_b.cpu().numpy(), pairs=self.pairs.cpu().numpy())
+
+    # ---- what a warm-up must not leave behind
+    def snapshot(self):
+        return None if self._state is None else self._state.clone()
+
+    def restore(self, snap):
+        if self._state is not None and snap is not None:
+            self._state.copy_(snap)
+
+    # ---- for a checkpoint's own extra key: plain Python values
+    def state_dict(self):
+        return dict(seed=self.seed, step=self.step, prob=float(self.prob), cutmix_share=float(self.cutmix_share),
+                    mixup_alpha=float(self.mixup_alpha), cutmix_alpha=float(self.cutmix_alpha))
+
+    def load_state_dict(self, sd):
+        prob, share, a_mix, a_cut = (sd[k] for k in ("prob", "cutmix_share", "mixup_alpha", "cutmix_alpha"))
+        seed = int(sd["seed"])
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError(f"BatchMixer: seed {seed} of the state dict is outside [0, 2^32)")
+        _unit("prob", prob), _unit("cutmix_share", share), _unit("mixup_alpha", a_mix, 0.05), _unit("cutmix_alpha", a_cut, 0.05)
+        self.prob, self.cutmix_share, self.mixup_alpha, self.cutmix_alpha = prob, share, a_mix, a_cut
+        self._seed = seed
+        self.step = int(sd["step"])                              # writes seed, step and the hyper words when bound
+
+
+def _check_mixer(mixer, criterion, what):
+    """a mixed batch needs the criterion with two targets and a weight per row; returns it bound to the mixer"""
+    if not isinstance(mixer, BatchMixer):
+        raise ValueError(f"{what}: mixer must be a train.BatchMixer or None, got {type(mixer).__name__}")
+    criterion = criterion if criterion is not None else MixedCrossEntropyLoss()
+    if not isinstance(criterion, MixedCrossEntropyLoss):
+        raise ValueError(f"{what} needs a train.MixedCrossEntropyLoss criterion (a mixed row has two targets and a weight, "
+                         f"and every other criterion takes one integer target per row), got {type(criterion).__name__}")
+    criterion.bind_mixer(mixer)
+    return criterion
+
+
 def _check_micro_batch(micro_batch):
     if micro_batch is not None and (isinstance(micro_batch, bool) or not isinstance(micro_batch, numbers.Integral)
                                     or micro_batch < 1):
@@ -175,11 +366,22 @@ class TrainStep:
 
     `meter`: a `TrainMeter`; every call ends with its fold launch (after the optimizer's and the averager's), which adds
     the step's loss, correct count and row count -- and the verdict and norm of the device optimizer's guard -- to the
-    meter's device words.  `None` (the default): the launch sequence is what it has always been."""
+    meter's device words.  `None` (the default): the launch sequence is what it has always been.
 
-    def __init__(self, model, optimizer=None, reducer=None, criterion=None, micro_batch=None, pad_to=None, meter=None):
-        self.model, self.opt, self.reducer, self.meter = model, optimizer, reducer, meter
-        self.pad_to, self._pad = pad_to, None
+    `mixer`: a `BatchMixer`; every call starts with its two launches, which mix the whole batch -- the padded buffer, or a
+    copy of `x`: never the caller's tensor -- before any slicing, so partners may sit in different micro-batches.  The
+    criterion is a `MixedCrossEntropyLoss` (the default then; anything else is refused) and is told each slice's place,
+    with `pad_to` or without (the row count is then a constant word).  BatchNorm models take a mixer without `pad_to`.
+    Without `pad_to` the mixer is bound to the first batch's `(B, T)` and every later batch must have that many rows (a
+    short last batch raises: drop it, or use `pad_to`).
+    `None` (the default): nothing changes."""
+
+    def __init__(self, model, optimizer=None, reducer=None, criterion=None, micro_batch=None, pad_to=None, meter=None,
+                 mixer=None):
+        self.model, self.opt, self.reducer, self.meter, self.mixer = model, optimizer, reducer, meter, mixer
+        self.pad_to, self._pad, self._all_rows = pad_to, None, None     # _all_rows: (n, the constant word holding n)
+        if mixer is not None:
+            criterion = _check_mixer(mixer, criterion, "TrainStep(mixer=...)")
         if pad_to is not None:
             if isinstance(pad_to, bool) or not isinstance(pad_to, numbers.Integral) or pad_to < 1:
                 raise ValueError(f"pad_to must be a positive integer or None, got {pad_to!r}")
@@ -205,13 +407,21 @@ class TrainStep:
             self._pad.load(x, y)
             x, y = self._pad.x, self._pad.y
         n = x.shape[0]
+        place = self.n_rows
+        if self.mixer is not None:
+            if self.pad_to is None:                          # a buffer of the step's own, and the constant row count
+                x = x.detach().clone()
+                if self._all_rows is None or self._all_rows[0] != n:
+                    self._all_rows = (n, torch.full((1,), n, device=x.device, dtype=torch.int32))
+                place = self._all_rows[1]
+            self.mixer.apply(x, y, self.n_rows)
         mb = self.micro_batch if self.micro_batch and self.micro_batch < n else n
         n_acc = (n + mb - 1) // mb
         if self.reducer is not None:
             self.reducer.zero_grad(n_acc)
         elif self.opt is not None:
             self.opt.zero_grad(set_to_none=True)
-        total, correct = _run_slices(self.model, self.criterion, x, y, mb, weighted=self.pad_to is None, n_rows=self.n_rows)
+        total, correct = _run_slices(self.model, self.criterion, x, y, mb, weighted=place is None, n_rows=place)
         if self.reducer is not None:
             self.reducer.finish()
         if self.opt is not None:
@@ -294,6 +504,16 @@ class GraphedTrainStep:
     captured, after the backward.  The warm-up leaves the meter as it found it.  `None` (the default): the captured node
     sequence is what it has always been.
 
+    Mixing.  `mixer=BatchMixer(...)` makes the mixer's two launches (hwgat_mix_draw, hwgat_mix_apply) the first nodes of
+    the graph, in front of the first forward: every replay matches the live rows of the static batch into pairs and mixes
+    the static input buffer in place, once, before any slicing (partners may sit in different micro-batches).  The
+    criterion must be a `MixedCrossEntropyLoss` (the default then), which is told each slice's place with `ragged` or
+    without (the row count is then a constant word).  The mixer's hyper-parameters are device words: `mixer.prob = 0.0`
+    reaches the next replay like a new lr.  The warm-up leaves the mixer's step counter where it was: with `mixer.step = c`
+    before construction, replay k draws what the eager step draws in its k-th call from the same `c`.  A replay rewrites
+    `step.x`; a caller that stages its batches there (`loader.bind(step.x, step.y)`) writes a fresh batch before every
+    replay anyway.  BatchNorm models take a mixer without `ragged`.  `None` (the default): nothing changes.
+
     Inputs are copied into static buffers; `loss` / `correct` are static device tensors rewritten by every replay.
     Shapes are fixed at capture.  Parameters must not be reallocated afterwards (same rule as serve.GraphedEval).
     The warm-up's traces in the model's buffers (BatchNorm running statistics) are undone like those in the weights.
@@ -302,12 +522,14 @@ class GraphedTrainStep:
     the base seed (seeding.DeviceSeeds._next_step_seed); in the graph that copy is a node after the seed advance."""
 
     def __init__(self, model, optimizer, x, y, criterion=None, warmup=2, reducer=None, micro_batch=None, ragged=False,
-                 meter=None):
+                 meter=None, mixer=None):
         import importlib
         HF = importlib.import_module(__package__ + ".functional")
         micro_batch = _check_micro_batch(micro_batch)
         if micro_batch is not None and reducer is not None:
             raise NotImplementedError("micro_batch with a reducer: the all-reduce inside a capture is untested")
+        if mixer is not None:
+            criterion = _check_mixer(mixer, criterion, "GraphedTrainStep(mixer=...)")
         if ragged:
             if reducer is not None:
                 raise NotImplementedError("ragged with a reducer: ranks with different row counts need a weighted mean")
@@ -321,7 +543,7 @@ class GraphedTrainStep:
         for grp in optimizer.param_groups:
             if not self.in_graph and not grp.get("capturable", False):
                 raise ValueError("the optimizer must be built with capturable=True (its step count then lives on the device)")
-        self.model, self.opt, self.reducer, self.meter = model, optimizer, reducer, meter
+        self.model, self.opt, self.reducer, self.meter, self.mixer = model, optimizer, reducer, meter, mixer
         self.criterion = criterion or SmoothedCrossEntropyLoss()
         self.ragged, self._pad = bool(ragged), None
         if self.ragged:
@@ -331,6 +553,12 @@ class GraphedTrainStep:
         else:
             self.x, self.y = x.detach().clone(), y.detach().clone()
         B = x.shape[0]
+        # the word the criterion is placed with: the ragged step's row count, or -- for a mixer without it -- the constant B
+        self._place = self.n_rows
+        if mixer is not None:
+            mixer.bind(x.device, B, x.shape[1]).push_hyper()  # state and records exist before the capture
+            if self._place is None:
+                self._place = torch.full((1,), B, device=x.device, dtype=torch.int32)
         self.micro_batch = micro_batch if micro_batch is not None and micro_batch < B else B
         self.n_slices = (B + self.micro_batch - 1) // self.micro_batch
         start = int(model._drop_calls)
@@ -346,9 +574,13 @@ class GraphedTrainStep:
         else:
             keep_state = {p: {k: v.clone() for k, v in st.items() if torch.is_tensor(v)} for p, st in optimizer.state.items()}
         keep_meter = None if meter is None else meter.bind(dev).snapshot()   # the block exists before the capture
+        keep_mixer = None if mixer is None else mixer.snapshot()
+        keep_x = None if mixer is None else self.x.clone()   # the warm-up mixes the static batch in place
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 self._one()
+                if mixer is not None:
+                    self.x.copy_(keep_x)
         torch.cuda.current_stream(dev).wait_stream(side)
         with torch.no_grad():
             for p, q in zip(model.parameters(), keep_p):
@@ -367,7 +599,9 @@ class GraphedTrainStep:
                                 v.zero_()
             if meter is not None:                        # the warm-up's folds never happened
                 meter.restore(keep_meter)
-        del keep_p, keep_b, keep_state, keep_meter
+            if mixer is not None:                        # nor its draws: the step counter is where the caller left it
+                mixer.restore(keep_mixer)
+        del keep_p, keep_b, keep_state, keep_meter, keep_mixer, keep_x
         model.device_seed_counter = True                 # from here on the device counts the steps itself
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
@@ -395,7 +629,9 @@ class GraphedTrainStep:
 
     def _one(self, step=True):
         self.opt.zero_grad(set_to_none=True)
-        if self.n_slices == 1 and not self.ragged:       # the unsliced step, node for node what it has always been
+        if self.mixer is not None:                       # once, on the whole static batch, before any slicing
+            self.mixer.apply(self.x, self.y, self.n_rows)
+        if self.n_slices == 1 and self._place is None:   # the unsliced step, node for node what it has always been
             out = self.model(self.x)
             loss = self.criterion(out, self.y)
             loss.backward()
@@ -404,8 +640,8 @@ class GraphedTrainStep:
             if step:
                 self.opt.step()
             return self._fold(loss.detach(), _correct(self.criterion, out, self.y))
-        loss, correct = _run_slices(self.model, self.criterion, self.x, self.y, self.micro_batch, weighted=not self.ragged,
-                                    n_rows=self.n_rows)
+        loss, correct = _run_slices(self.model, self.criterion, self.x, self.y, self.micro_batch, weighted=self._place is None,
+                                    n_rows=self._place)
         if step:                                         # once, after the last slice (no reducer here: refused above)
             self.opt.step()
         return self._fold(loss, correct)
@@ -439,6 +675,8 @@ class GraphedTrainStep:
                 self.y.copy_(y, non_blocking=True)
         if self.in_graph:
             self.opt.push_hyper()                        # launches only when a param group's values changed
+        if self.mixer is not None:
+            self.mixer.push_hyper()                      # likewise
         self.graph.replay()
         self.model._drop_calls += self.n_slices          # host mirror of the device counter (model._seeds() in tests)
         for p, g in self._grads:
@@ -741,7 +979,8 @@ class EpochLoop:
     `lr`: the value recorded under 'learning_rate' (the reference's cfg.lr); default: the first param group's lr now.
     `eval_averaged=True` evaluates on the optimizer's averaged weights (`optimizer.averager.applied()`).
     `meter`: a `TrainMeter` of the caller's (say, one with a step log); `evaluator`: anything with reset() / update(x, y) /
-    result() -> {"loss", "acc": {k: ...}} in the Evaluator's place.
+    result() -> {"loss", "acc": {k: ...}} in the Evaluator's place.  `mixer`: a `BatchMixer` handed to the train step (which
+    then uses a `MixedCrossEntropyLoss`); its state goes into the checkpoints.  Validation is untouched.
 
     `run(train_batches, val_batches, epochs, start_epoch=None)`: two re-iterable sources of (x, y) batches, on the CPU
     (copied with non_blocking=True; pinning is the loader's business, see collate.PinnedBatcher) or on the device.
@@ -753,13 +992,14 @@ class EpochLoop:
 
     `resume(path)` loads a checkpoint of this loop (checkpoint.load_checkpoint): weights, optimizer, scheduler, the four
     lists, `start_epoch = epoch + 1`, best values from the lists; and from the file's 'extra' key the guard's, the
-    averager's and the meter's state and the model's dropout counter, so dropout masks go on where they stopped.  Torch's
+    averager's, the meter's and the mixer's state and the model's dropout counter, so dropout masks and the mixer's draws
+    go on where they stopped.  Torch's
     device generator state is NOT carried: it draws HWGATE's train-mode window thresholds (HWGATE.py:96), so a resumed
     HWGATE run draws other thresholds than the uninterrupted one would have."""
 
     def __init__(self, model, optimizer, scheduler, batch_size, example, num_classes, smooth_factor=0.01, k=1, graph=True,
                  micro_batch=None, out_prefix=None, save_interval=100, early_stopper=None, lr=None, eval_averaged=False,
-                 meter=None, evaluator=None):
+                 meter=None, evaluator=None, mixer=None):
         if isinstance(batch_size, bool) or not isinstance(batch_size, numbers.Integral) or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
         x, y = example
@@ -779,7 +1019,7 @@ class EpochLoop:
         self.micro_batch = _check_micro_batch(micro_batch)
         self.out_prefix, self.eval_averaged = out_prefix, bool(eval_averaged)
         self.lr = _plain_lr(optimizer.param_groups[0]["lr"]) if lr is None else lr
-        self.meter, self.evaluator, self.step = meter, evaluator, None
+        self.meter, self.evaluator, self.step, self.mixer = meter, evaluator, None, mixer
         self.book = EpochBook(save_interval, early_stopper)
         self.start_epoch = 0
         self.padded = bool(getattr(model, "clips_independent_in_train", False))
@@ -800,16 +1040,19 @@ class EpochLoop:
     def _build_step(self):
         x, y = self._on_device(*self.example)
         self.model.train()
-        if self.padded:
+        if self.mixer is not None:
+            crit = MixedCrossEntropyLoss(self.smooth_factor)
+        elif self.padded:
             crit = BatchSlicedCrossEntropyLoss(self.smooth_factor)
         else:
             crit = FusedSmoothedCrossEntropyLoss(self.smooth_factor)
+        extra = {} if self.mixer is None else dict(mixer=self.mixer)      # without one the calls are what they were
         if self.graph:
             self.step = GraphedTrainStep(self.model, self.opt, x, y, criterion=crit, micro_batch=self.micro_batch,
-                                         ragged=self.padded, meter=self.meter)
+                                         ragged=self.padded, meter=self.meter, **extra)
         else:
             self.step = TrainStep(self.model, self.opt, criterion=crit, micro_batch=self.micro_batch,
-                                  pad_to=self.batch_size if self.padded else None, meter=self.meter)
+                                  pad_to=self.batch_size if self.padded else None, meter=self.meter, **extra)
 
     def _build_evaluator(self):
         import importlib
@@ -851,9 +1094,12 @@ class EpochLoop:
     # ---- checkpoints
     def _extra(self):
         guard, averager = _guard_of(self.opt), getattr(self.opt, "averager", None)
-        return dict(guard=None if guard is None else guard.state_dict(),
-                    averager=None if averager is None else averager.state_dict(),
-                    meter=self.meter.state_dict(), drop_calls=int(getattr(self.model, "_drop_calls", 0)))
+        extra = dict(guard=None if guard is None else guard.state_dict(),
+                     averager=None if averager is None else averager.state_dict(),
+                     meter=self.meter.state_dict(), drop_calls=int(getattr(self.model, "_drop_calls", 0)))
+        if self.mixer is not None:
+            extra["mixer"] = self.mixer.state_dict()
+        return extra
 
     def _save(self, suffix, epoch):
         import importlib
@@ -878,6 +1124,8 @@ class EpochLoop:
             averager.load_state_dict(extra["averager"])
         if extra.get("meter") is not None:
             self.meter.load_state_dict(extra["meter"])
+        if self.mixer is not None and extra.get("mixer") is not None:
+            self.mixer.load_state_dict(extra["mixer"])
         if "drop_calls" in extra and hasattr(self.model, "_drop_calls"):
             self.model._drop_calls = int(extra["drop_calls"])
             if self.model._seed_state.is_cuda:           # the device counter a captured step advances by itself
