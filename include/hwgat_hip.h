@@ -82,7 +82,8 @@ extern "C" {
  *         hwgat_loader_{state_bytes,select,draw}, the device-resident clip store's shuffle and augmentation draw for
  *         data.DeviceLoader; hwgat_attn_probs(_numel), the attention-map export of the five attention kinds;
  *         hwgat_mix_{state_bytes,set,draw,apply}, Mixup and temporal CutMix of the pairs of a batch, and
- *         hwgat_mbsce_{fwd,bwd}, the slice criterion with two targets and a weight per row (additions only) */
+ *         hwgat_mbsce_{fwd,bwd}, the slice criterion with two targets and a weight per row;
+ *         hwgat_kd_{state_bytes,set,fwd,bwd}, the same criterion distilled from a teacher's logits (additions only) */
 #define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
@@ -1293,6 +1294,55 @@ int hwgat_mbsce_fwd(const float* logits, const int64_t* target, const int64_t* t
 int hwgat_mbsce_bwd(const float* logits, const int64_t* target, const int64_t* target_b, const float* lam,
                     const int32_t* n_rows, int64_t offset, const float* lse, const float* g, float* dlogits, int64_t B,
                     int C, float eps, void* stream);
+
+/* ---- the slice criterion distilled from a teacher (train.DistilledCrossEntropyLoss, train.Distiller): hwgat_mbsce_*'s
+ * loss blended with the tempered KL divergence from the teacher's logits.  Arguments, live rows, dead rows, `offset`,
+ * *n_rows, the empty slice, bad targets and the limits on B and C are hwgat_bsce_fwd's, word for word; teacher (B, C) fp32
+ * is a slice pointer like logits.  target_b and lam may BOTH be NULL: no mixer, every row has the one target (lam = 1) and
+ * row_loss_b / rank_b are not touched (they may be NULL then); one NULL and one non-NULL is HWGAT_EINVAL.
+ * state: hwgat_kd_state_bytes() = 8 bytes of DEVICE memory, 8-byte aligned: float alpha, tau.  hwgat_kd_set (one thread,
+ *   stream-ordered) writes both; alpha outside [0, 1], tau outside [HWGAT_KD_TAU_MIN, HWGAT_KD_TAU_MAX] or a NaN is
+ *   HWGAT_ESHAPE before any launch.  The kernels clamp what they read to the same ranges (a NaN: the lower end).
+ * For a live row with student logits z, teacher logits u, p = softmax(u / tau), q = softmax(z / tau):
+ *   hard        = the row loss hwgat_mbsce_fwd computes (lam NULL: hwgat_bsce_fwd's), bit for bit
+ *   lse_s, lse_t (B) fp32 = logsumexp(z / tau), logsumexp(u / tau)
+ *   row_kd  (B) fp32 = tau^2 sum_j p_j (log p_j - log q_j); a term with p_j = 0 (u_j = -inf) counts 0.  Evaluated as
+ *                 tau^2 (sum_j p_j d_j - log1p(sum_j q_j expm1(d_j))), d_j = (u_j - z_j) / tau - (max u - max z) / tau, the
+ *                 sums over j in double: no term of order 1 is cancelled, and a row with u == z bit for bit gives exactly
+ *                 0.0f.  A teacher row with a NaN or +inf gives NaN (and so a NaN row_loss and loss); so does a column
+ *                 with z_j = -inf and u_j finite, where the divergence is infinite
+ *   row_loss    = (1 - alpha) hard + alpha row_kd
+ *   t_pred  (B) int32 = the lowest index holding the teacher row's maximum (pred's rule)
+ *   lse, rank, pred, correct[0], live[0]: hwgat_mbsce_fwd's
+ *   loss[0], kd[0] = the live rows' row_loss, row_kd summed in hwgat_bsce_fwd's fixed order over *n_rows; exactly 0 for an
+ *                 empty slice
+ *   agree[0]     int64 = live rows with pred == t_pred;  t_correct[0] int64 = live rows whose t_pred is the dominant label
+ *   When the alpha word is exactly 0.0f the teacher is not read: row_loss, loss[0] have hwgat_mbsce_fwd's bits (lam NULL:
+ *   hwgat_bsce_fwd's), row_kd, lse_s, lse_t and kd[0] are 0, t_pred is -1, agree[0] and t_correct[0] are 0.
+ * hwgat_kd_fwd is at most five launches (v, the rows under target_b -- not with lam NULL --, the rows under target, the
+ *   rows' KL, the sums): one more than hwgat_mbsce_fwd.
+ * hwgat_kd_bwd (one launch): for a live row
+ *   dlogits[b, j] = g[0] / *n_rows ((1 - alpha)(exp(z_j - lse) - (1 - eps) hit_j - eps / C)
+ *                                   + alpha tau (exp(z_j / tau - lse_s) / Z_s - exp(u_j / tau - lse_t) / Z_t))
+ *   with hit_j hwgat_mbsce_bwd's bracket (lam NULL: the one-hot) and Z_s = sum_j exp(z_j / tau - lse_s), Z_t likewise: 1 up
+ *   to the rounding of lse_s / lse_t to fp32, summed in double in the fixed order -- the two softmaxes differ by order
+ *   1 / tau, and that rounding would otherwise be the gradient's error.  Exactly 0.0f for every dead row.  With the alpha word
+ *   exactly 0.0f it evaluates hwgat_mbsce_bwd's expression (lam NULL: hwgat_bsce_bwd's bits) and reads no teacher.
+ * No float or double atomic anywhere; a repeat is bit-equal.  Rows off a 16-byte boundary and C % 4 != 0 take the scalar
+ * loads; rows of more than 4096 columns are read from memory twice instead of staged. */
+#define HWGAT_KD_TAU_MIN 0.25
+#define HWGAT_KD_TAU_MAX 32.0
+int64_t hwgat_kd_state_bytes(void);
+int hwgat_kd_set(void* state, float alpha, float tau, void* stream);
+int hwgat_kd_fwd(const float* logits, const float* teacher, const int64_t* target, const int64_t* target_b,
+                 const float* lam, const int32_t* n_rows, int64_t offset, const void* state, float* lse, float* row_loss,
+                 int32_t* rank, int32_t* pred, float* loss, int64_t* correct, int32_t* live, float* row_loss_b,
+                 int32_t* rank_b, float* lse_s, float* lse_t, float* row_kd, int32_t* t_pred, float* kd, int64_t* agree,
+                 int64_t* t_correct, int64_t B, int C, float eps, void* stream);
+int hwgat_kd_bwd(const float* logits, const float* teacher, const int64_t* target, const int64_t* target_b,
+                 const float* lam, const int32_t* n_rows, int64_t offset, const void* state, const float* lse,
+                 const float* lse_s, const float* lse_t, const float* g, float* dlogits, int64_t B, int C, float eps,
+                 void* stream);
 
 /* ---- the classifier head (csrc/head.hip; reference: the `head` / `classifier` nn.Linear of every model,
  * hwgat/models/HWGATE.py:331,372).  Everything fp32 and row-major; W is (N, K) as nn.Linear stores it.

@@ -158,6 +158,10 @@ _SIGS = {
     "hwgat_mix_apply": [_P] * 6 + [_I, _I, _L, _P],
     "hwgat_mbsce_fwd": [_P, _P, _P, _P, _P, _L] + [_P] * 9 + [_L, _I, _F, _P],
     "hwgat_mbsce_bwd": [_P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _I, _F, _P],
+    "hwgat_kd_state_bytes": [],
+    "hwgat_kd_set": [_P, _F, _F, _P],
+    "hwgat_kd_fwd": [_P] * 6 + [_L] + [_P] * 17 + [_L, _I, _F, _P],
+    "hwgat_kd_bwd": [_P] * 6 + [_L] + [_P] * 6 + [_L, _I, _F, _P],
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],

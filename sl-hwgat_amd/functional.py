@@ -1904,3 +1904,103 @@ def mixed_sliced_ce(logits, target, target_b, lam, eps, n_rows, offset):
     rank and correct on the dominant label -- as an autograd node (forward four launches, backward one)"""
     return _MixedSlicedCE.apply(logits.float().contiguous(), target.contiguous(), target_b.contiguous(), lam.contiguous(),
                                 float(eps), n_rows, int(offset))
+
+
+# ---------------------------------------------------------------- knowledge distillation (csrc/loss_eval.hip, train.Distiller)
+# The slice criterion with a teacher's logits beside the labels.  The state is two device floats, alpha and tau.
+KD_STATE_WORDS = 2
+KD_TAU_MIN, KD_TAU_MAX = 0.25, 32.0            # HWGAT_KD_TAU_MIN, HWGAT_KD_TAU_MAX
+
+
+def kd_state(device):
+    """a zeroed distillation state on `device` (write it with kd_set before the first forward)"""
+    if 4 * KD_STATE_WORDS != _lib.lib().hwgat_kd_state_bytes():
+        raise RuntimeError("the library lays the distillation state out differently from functional.py's constants")
+    return torch.zeros(KD_STATE_WORDS, dtype=torch.float32, device=device)
+
+
+def _kd_state_check(state):
+    if state.dtype != torch.float32 or state.numel() != KD_STATE_WORDS:
+        raise ValueError(f"the distillation state must be fp32 with {KD_STATE_WORDS} words")
+
+
+def kd_set(state, alpha, tau):
+    """write alpha and tau.  One tiny launch, stream-ordered"""
+    _kd_state_check(state)
+    call("hwgat_kd_set", ptr(state), float(alpha), float(tau), stream())
+
+
+def _kd_check(logits, teacher, target, target_b, lam, state, n_rows, offset):
+    if (target_b is None) != (lam is None):
+        raise ValueError("target_b and lam come together (a mixer's records) or not at all")
+    if lam is None:
+        _bsce_check(logits, target, n_rows, offset)
+    else:
+        _mbsce_check(logits, target, target_b, lam, n_rows, offset)
+    if teacher.dtype != torch.float32 or teacher.shape != logits.shape:
+        raise ValueError(f"teacher must be fp32 {tuple(logits.shape)}, got {teacher.dtype} {tuple(teacher.shape)}")
+    _kd_state_check(state)
+
+
+def kd_forward(logits, teacher, target, target_b, lam, state, eps, n_rows, offset, out=None):
+    """mbsce_forward blended with the tempered KL from the teacher's logits: (loss, row_loss, lse, rank, pred, correct, live,
+    row_loss_b, rank_b, lse_s, lse_t, row_kd, t_pred, kd, agree, t_correct).  `target_b` and `lam` are both None without a
+    mixer (row_loss_b / rank_b are then not written).  `out` takes the same sixteen tensors preallocated"""
+    _kd_check(logits, teacher, target, target_b, lam, state, n_rows, offset)
+    B, C = logits.shape
+    if out is None:
+        f = torch.empty(6 * B + 2, device=logits.device, dtype=torch.float32)
+        i = torch.empty(4 * B + 1, device=logits.device, dtype=torch.int32)
+        l = torch.empty(3, device=logits.device, dtype=torch.int64)
+        out = (f[6 * B:6 * B + 1], f[:B], f[B:2 * B], i[:B], i[B:2 * B], l[:1], i[4 * B:], f[2 * B:3 * B], i[2 * B:3 * B],
+               f[3 * B:4 * B], f[4 * B:5 * B], f[5 * B:6 * B], i[3 * B:4 * B], f[6 * B + 1:], l[1:2], l[2:])
+    loss, row_loss, lse, rank, pred, correct, live, row_loss_b, rank_b, lse_s, lse_t, row_kd, t_pred, kd, agree, t_correct = out
+    mixed = lam is not None
+    call("hwgat_kd_fwd", ptr(logits), ptr(teacher), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(state),
+         ptr(lse), ptr(row_loss), ptr(rank), ptr(pred), ptr(loss), ptr(correct), ptr(live),
+         ptr(row_loss_b) if mixed else None, ptr(rank_b) if mixed else None, ptr(lse_s), ptr(lse_t), ptr(row_kd), ptr(t_pred),
+         ptr(kd), ptr(agree), ptr(t_correct), B, C, float(eps), stream())
+    return out
+
+
+def kd_backward(logits, teacher, target, target_b, lam, state, lse, lse_s, lse_t, g, eps, n_rows, offset, out=None):
+    """d loss / d logits of kd_forward times the device scalar `g`; exactly zero in the dead rows"""
+    _kd_check(logits, teacher, target, target_b, lam, state, n_rows, offset)
+    B, C = logits.shape
+    dz = torch.empty_like(logits) if out is None else out
+    call("hwgat_kd_bwd", ptr(logits), ptr(teacher), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(state),
+         ptr(lse), ptr(lse_s), ptr(lse_t), ptr(g), ptr(dz), B, C, float(eps), stream())
+    return dz
+
+
+class _DistilledSlicedCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, teacher, target, target_b, lam, state, eps, n_rows, offset):
+        out = kd_forward(logits, teacher, target, target_b, lam, state, eps, n_rows, offset)
+        loss, _, lse, rank, pred, correct = out[:6]
+        lse_s, lse_t, _, t_pred, kd, agree, t_correct = out[9:]
+        ctx.mixed = lam is not None
+        ctx.save_for_backward(logits, teacher, target, lse, lse_s, lse_t, state, *((target_b, lam) if ctx.mixed else ()))
+        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
+        # the views that go out are what is marked: a float view left unmarked would carry a grad_fn and keep the node alive
+        correct, kd, agree, t_correct = correct.view(()), kd.view(()), agree.view(()), t_correct.view(())
+        ctx.mark_non_differentiable(rank, pred, correct, t_pred, kd, agree, t_correct)
+        return loss.view(()), rank, pred, correct, t_pred, kd, agree, t_correct
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        logits, teacher, target, lse, lse_s, lse_t, state = ctx.saved_tensors[:7]
+        target_b, lam = ctx.saved_tensors[7:] if ctx.mixed else (None, None)
+        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
+        dz = kd_backward(logits, teacher, target, target_b, lam, state, lse, lse_s, lse_t, g, ctx.eps, ctx.n_rows, ctx.offset)
+        return (dz,) + (None,) * 8
+
+
+def distilled_sliced_ce(logits, teacher, target, target_b, lam, state, eps, n_rows, offset):
+    """(loss, rank, pred, correct, t_pred, kd, agree, t_correct): mixed_sliced_ce (batch_sliced_ce when `target_b` and `lam`
+    are None) blended with the tempered KL from `teacher` as (1 - alpha) hard + alpha kd, alpha and tau read from the device
+    words of `state` when the kernels run, as an autograd node (forward at most five launches, backward one).  The
+    gradient goes to the student's logits only"""
+    return _DistilledSlicedCE.apply(logits.float().contiguous(), teacher.detach().float().contiguous(), target.contiguous(),
+                                    None if target_b is None else target_b.contiguous(),
+                                    None if lam is None else lam.contiguous(), state, float(eps), n_rows, int(offset))

@@ -265,6 +265,177 @@ def _check_mixer(mixer, criterion, what):
     return criterion
 
 
+def _kd_number(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not lo <= v <= hi:      # a NaN fails the comparison
+        raise ValueError(f"Distiller: {name} must be a number in [{lo}, {hi}], got {v!r}")
+    return float(v)
+
+
+class Distiller:
+    """Knowledge distillation inside the train step: owns the frozen teacher and the two device words the distilled
+    criterion reads (csrc/loss_eval.hip, hwgat_kd_*; formulas: include/hwgat_hip.h).  Every slice of a step the teacher sees
+    the very input the student sees (after the mixer, when there is one) in an eval forward without gradients, and the
+    slice's loss is (1 - alpha) hard + alpha T^2 KL(softmax(teacher / T) || softmax(student / T)).
+
+        distiller = train.Distiller(teacher, alpha=0.5, temperature=4.0)
+        step = train.GraphedTrainStep(student, opt, x, y, ragged=True, distiller=distiller)
+        distiller.alpha = 0.0                    # the last epochs on the labels alone: the next replay, no new capture
+
+    `alpha` in [0, 1] and `temperature` in [0.25, 32] are properties; when one changed, one hwgat_kd_set launch carries
+    both to the device before the next step (`push_hyper`).  With alpha 0 the kernels do not read the teacher's logits
+    and the loss and gradient have the undistilled criterion's bits (the teacher's forward still runs).  The teacher is
+    put into eval() with requires_grad_(False) and stays the caller's: its weights are in no state dict of this object."""
+
+    def __init__(self, teacher, alpha=0.5, temperature=4.0):
+        if not isinstance(teacher, torch.nn.Module):
+            raise ValueError(f"Distiller: teacher must be a torch.nn.Module, got {type(teacher).__name__}")
+        self._alpha, self._tau = alpha, temperature
+        self._hyper()
+        self.teacher = teacher.eval().requires_grad_(False)
+        self._state = self._pushed = None
+        self.logits = None                       # the teacher's fp32 logits of the latest observe()
+
+    def _hyper(self):
+        """(alpha, temperature), validated, in the order of the device words"""
+        HF = _functional()
+        return (_kd_number("alpha", self._alpha, 0.0, 1.0),
+                _kd_number("temperature", self._tau, HF.KD_TAU_MIN, HF.KD_TAU_MAX))
+
+    @property
+    def alpha(self):
+        return self._alpha
+
+    @alpha.setter
+    def alpha(self, v):
+        self._alpha = _kd_number("alpha", v, 0.0, 1.0)
+
+    @property
+    def temperature(self):
+        return self._tau
+
+    @temperature.setter
+    def temperature(self, v):
+        HF = _functional()
+        self._tau = _kd_number("temperature", v, HF.KD_TAU_MIN, HF.KD_TAU_MAX)
+
+    # ---- device side
+    def bind(self, device):
+        """allocate the two device words (once) and write them"""
+        if self._state is not None:
+            return self
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("Distiller needs an MI355X device; there is no CPU fallback")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("Distiller: bind() before capturing")
+        hyper = self._hyper()
+        HF = _functional()
+        self._state = HF.kd_state(device)
+        HF.kd_set(self._state, *hyper)
+        self._pushed = hyper
+        return self
+
+    @property
+    def state(self):
+        """the device words (alpha, tau) the criterion's kernels read; None before bind()"""
+        return self._state
+
+    def push_hyper(self):
+        """one launch when alpha or the temperature changed since the last one, none otherwise (none while unbound)"""
+        hyper = self._hyper()                    # validated before any launch
+        if self._state is not None and hyper != self._pushed:
+            _functional().kd_set(self._state, *hyper)
+            self._pushed = hyper
+
+    def observe(self, xs):
+        """the teacher's eval forward of one slice, without gradients; keeps its fp32 logits for the criterion"""
+        if self.teacher.training:
+            raise RuntimeError("Distiller: the teacher is in train() mode -- it must stay in eval() (teacher.eval())")
+        with torch.no_grad():
+            self.logits = self.teacher(xs).float()
+        return self.logits
+
+    def _addresses(self):
+        return tuple(t.data_ptr() for t in list(self.teacher.parameters()) + list(self.teacher.buffers()))
+
+    # ---- for a checkpoint's own extra key: plain Python values
+    def state_dict(self):
+        alpha, tau = self._hyper()
+        return dict(alpha=alpha, temperature=tau)
+
+    def load_state_dict(self, sd):
+        HF = _functional()
+        alpha = _kd_number("alpha", sd["alpha"], 0.0, 1.0)
+        tau = _kd_number("temperature", sd["temperature"], HF.KD_TAU_MIN, HF.KD_TAU_MAX)
+        self._alpha, self._tau = alpha, tau
+        self.push_hyper()
+
+
+class DistilledCrossEntropyLoss(MixedCrossEntropyLoss):
+    """MixedCrossEntropyLoss with a teacher (hwgat_kd_fwd / hwgat_kd_bwd of csrc/loss_eval.hip): a live row's loss is
+    (1 - alpha) hard + alpha T^2 KL(teacher || student), `hard` the parent's row loss -- with a bound mixer the mixed one,
+    read at the slice's place, without one the single-target loss of BatchSlicedCrossEntropyLoss.  alpha and T are the
+    distiller's device words.  The step that owns the batch binds the distiller (`bind_distiller`), calls
+    `place(n_rows, offset)` and `distiller.observe(slice)` before each slice.  `correct()`, `last_rank` and `last_pred` are
+    the parent's; `last_kd` is the slice's share of the batch-mean KD term, `agree()` the number of live rows whose arg-max
+    is the teacher's, `teacher_correct()` the number whose teacher arg-max (`last_teacher_pred`) is the dominant label."""
+
+    def __init__(self, smooth_factor: float = 0.01, mixer=None, distiller=None):
+        super().__init__(smooth_factor, mixer)
+        self.distiller = distiller
+        self.last_kd = self.last_teacher_pred = self._agree = self._t_hits = None
+
+    def bind_distiller(self, distiller):
+        if self.distiller is not None and self.distiller is not distiller:
+            raise ValueError("DistilledCrossEntropyLoss is bound to another Distiller: one criterion serves one distiller")
+        self.distiller = distiller
+
+    def forward(self, input, target):
+        d = self.distiller
+        if self.n_rows is None or d is None or d.state is None or d.logits is None:
+            raise RuntimeError("DistilledCrossEntropyLoss: bind_distiller(distiller), distiller.bind(device), "
+                               "distiller.observe(slice) and place(n_rows, offset) first -- TrainStep(distiller=...) and "
+                               "GraphedTrainStep(distiller=...) do")
+        if tuple(d.logits.shape) != tuple(input.shape):
+            raise ValueError(f"the teacher gives logits of shape {tuple(d.logits.shape)} for a slice on which the student gives "
+                             f"{tuple(input.shape)}: distillation needs the same classes in the same order")
+        b, o = input.shape[0], self.offset
+        y_b = lam = None
+        if self.mixer is not None:
+            if self.mixer.y_b is None:
+                raise RuntimeError("DistilledCrossEntropyLoss: the bound mixer has drawn nothing yet (mixer.apply(...) first)")
+            if o + b > self.mixer.y_b.shape[0]:
+                raise ValueError(f"the slice [{o}, {o + b}) lies outside the mixer's batch of {self.mixer.y_b.shape[0]} rows")
+            y_b, lam = self.mixer.y_b[o:o + b], self.mixer.lam[o:o + b]
+        (loss, self.last_rank, self.last_pred, self._hits, self.last_teacher_pred, self.last_kd, self._agree,
+         self._t_hits) = _functional().distilled_sliced_ce(input, d.logits, target, y_b, lam, d.state, self.smooth_factor,
+                                                           self.n_rows, o)
+        return loss
+
+    def agree(self):
+        return self._agree
+
+    def teacher_correct(self):
+        return self._t_hits
+
+
+def _check_distiller(distiller, criterion, model, reducer, what):
+    """a distilled batch needs the criterion that takes the teacher's logits; returns it bound to the distiller"""
+    if not isinstance(distiller, Distiller):
+        raise ValueError(f"{what}: distiller must be a train.Distiller or None, got {type(distiller).__name__}")
+    if distiller.teacher is model:
+        raise ValueError(f"{what}: the teacher is the student object -- a model cannot be distilled from itself (the teacher "
+                         "is frozen in eval(), the student trains)")
+    if reducer is not None:
+        raise NotImplementedError("distiller with a reducer: multi-rank distillation is not built")
+    criterion = criterion if criterion is not None else DistilledCrossEntropyLoss()
+    if not isinstance(criterion, DistilledCrossEntropyLoss):
+        raise ValueError(f"{what} needs a train.DistilledCrossEntropyLoss criterion (a distilled row has the teacher's logits "
+                         f"beside its labels, and every other criterion takes labels only), got {type(criterion).__name__}")
+    criterion.bind_distiller(distiller)
+    return criterion
+
+
 def _check_micro_batch(micro_batch):
     if micro_batch is not None and (isinstance(micro_batch, bool) or not isinstance(micro_batch, numbers.Integral)
                                     or micro_batch < 1):
@@ -308,16 +479,20 @@ class _PaddedBatch:
             self.rows = n
 
 
-def _run_slices(model, criterion, x, y, mb, weighted=True, n_rows=None):
+def _run_slices(model, criterion, x, y, mb, weighted=True, n_rows=None, distiller=None):
     """forward, loss and backward of x / y in slices of `mb` rows, gradients accumulating; (loss, correct) summed in slice
     order.  `weighted`: the slice's mean loss times n_i / n.  `n_rows`: the batch is zero-padded, the criterion is told
-    each slice's place and returns its share of the mean as it is.  Nothing of a slice outlives its backward but the sums."""
+    each slice's place and returns its share of the mean as it is.  Nothing of a slice outlives its backward but the sums.
+    `distiller`: its teacher sees each slice before the student does, and the criterion's three distillation sums
+    (kd, agree, teacher_correct) are left, summed the same way, in `criterion.step_sums`."""
     n = x.shape[0]
-    total = correct = None
+    total = correct = sums = None
     for i in range(0, n, mb):
         xs, ys = x[i:i + mb], y[i:i + mb]
         if n_rows is not None:
             criterion.place(n_rows, i)
+        if distiller is not None:
+            distiller.observe(xs)
         out = model(xs)
         loss = criterion(out, ys)
         if weighted:
@@ -326,7 +501,12 @@ def _run_slices(model, criterion, x, y, mb, weighted=True, n_rows=None):
         total = loss.detach() if total is None else total + loss.detach()
         c = _correct(criterion, out, ys)
         correct = c if correct is None else correct + c
+        if distiller is not None:
+            part = (criterion.last_kd, criterion.agree(), criterion.teacher_correct())
+            sums = part if sums is None else tuple(a + b for a, b in zip(sums, part))
         del out, loss, c
+    if distiller is not None:
+        criterion.step_sums = sums
     return total, correct
 
 
@@ -374,12 +554,22 @@ class TrainStep:
     with `pad_to` or without (the row count is then a constant word).  BatchNorm models take a mixer without `pad_to`.
     Without `pad_to` the mixer is bound to the first batch's `(B, T)` and every later batch must have that many rows (a
     short last batch raises: drop it, or use `pad_to`).
-    `None` (the default): nothing changes."""
+    `None` (the default): nothing changes.
+
+    `distiller`: a `Distiller`; before each slice's student forward its teacher runs an eval forward of the same slice
+    (after the mixer, when there is one) and the criterion -- a `DistilledCrossEntropyLoss`, the default then; anything
+    else is refused -- blends the labels' loss with the KL from the teacher's logits.  It is told each slice's place with
+    `pad_to` or without (the row count is then a constant word).  `kd`, `agree` and `teacher_correct` hold the step's
+    slice sums beside `loss` and `correct`.  A `reducer` is refused.  `None` (the default): nothing changes."""
 
     def __init__(self, model, optimizer=None, reducer=None, criterion=None, micro_batch=None, pad_to=None, meter=None,
-                 mixer=None):
+                 mixer=None, distiller=None):
         self.model, self.opt, self.reducer, self.meter, self.mixer = model, optimizer, reducer, meter, mixer
+        self.distiller = distiller
+        self.kd = self.agree = self.teacher_correct = None
         self.pad_to, self._pad, self._all_rows = pad_to, None, None     # _all_rows: (n, the constant word holding n)
+        if distiller is not None:
+            criterion = _check_distiller(distiller, criterion, model, reducer, "TrainStep(distiller=...)")
         if mixer is not None:
             criterion = _check_mixer(mixer, criterion, "TrainStep(mixer=...)")
         if pad_to is not None:
@@ -408,20 +598,27 @@ class TrainStep:
             x, y = self._pad.x, self._pad.y
         n = x.shape[0]
         place = self.n_rows
-        if self.mixer is not None:
+        if self.mixer is not None or self.distiller is not None:
             if self.pad_to is None:                          # a buffer of the step's own, and the constant row count
-                x = x.detach().clone()
+                if self.mixer is not None:
+                    x = x.detach().clone()
                 if self._all_rows is None or self._all_rows[0] != n:
                     self._all_rows = (n, torch.full((1,), n, device=x.device, dtype=torch.int32))
                 place = self._all_rows[1]
+        if self.mixer is not None:
             self.mixer.apply(x, y, self.n_rows)
+        if self.distiller is not None:
+            self.distiller.bind(x.device).push_hyper()
         mb = self.micro_batch if self.micro_batch and self.micro_batch < n else n
         n_acc = (n + mb - 1) // mb
         if self.reducer is not None:
             self.reducer.zero_grad(n_acc)
         elif self.opt is not None:
             self.opt.zero_grad(set_to_none=True)
-        total, correct = _run_slices(self.model, self.criterion, x, y, mb, weighted=place is None, n_rows=place)
+        total, correct = _run_slices(self.model, self.criterion, x, y, mb, weighted=place is None, n_rows=place,
+                                     **({} if self.distiller is None else dict(distiller=self.distiller)))
+        if self.distiller is not None:
+            self.kd, self.agree, self.teacher_correct = self.criterion.step_sums
         if self.reducer is not None:
             self.reducer.finish()
         if self.opt is not None:
@@ -514,6 +711,18 @@ class GraphedTrainStep:
     `step.x`; a caller that stages its batches there (`loader.bind(step.x, step.y)`) writes a fresh batch before every
     replay anyway.  BatchNorm models take a mixer without `ragged`.  `None` (the default): nothing changes.
 
+    Distillation.  `distiller=Distiller(teacher, ...)` makes the teacher's eval forward of each slice and the distilled
+    criterion's launches (hwgat_kd_fwd, hwgat_kd_bwd) nodes of the same graph: per slice the teacher's forward on the
+    static input (behind the mixer's launches, when there is a mixer), then the student's forward, the criterion -- a
+    `DistilledCrossEntropyLoss`, the default then; anything else is refused -- and the backward.  The criterion is told
+    each slice's place with `ragged` or without (the row count is then a constant word).  alpha and the temperature are
+    device words: `distiller.alpha = 0.0` reaches the next replay like a new lr, and from then on the replays leave the
+    weights the undistilled step leaves.  `kd`, `agree` and `teacher_correct` are static device tensors with the slice sums
+    in slice order, like `loss` and `correct`; the meter's loss is the step's total loss.  The teacher's parameters and
+    buffers must not be reallocated after the capture either; the warm-up leaves nothing behind in the teacher, and no
+    replay writes to it.  The teacher must not be the student, and a `reducer` is refused.  `None` (the default): the
+    captured node sequence is what it has always been.
+
     Inputs are copied into static buffers; `loss` / `correct` are static device tensors rewritten by every replay.
     Shapes are fixed at capture.  Parameters must not be reallocated afterwards (same rule as serve.GraphedEval).
     The warm-up's traces in the model's buffers (BatchNorm running statistics) are undone like those in the weights.
@@ -522,12 +731,14 @@ class GraphedTrainStep:
     the base seed (seeding.DeviceSeeds._next_step_seed); in the graph that copy is a node after the seed advance."""
 
     def __init__(self, model, optimizer, x, y, criterion=None, warmup=2, reducer=None, micro_batch=None, ragged=False,
-                 meter=None, mixer=None):
+                 meter=None, mixer=None, distiller=None):
         import importlib
         HF = importlib.import_module(__package__ + ".functional")
         micro_batch = _check_micro_batch(micro_batch)
         if micro_batch is not None and reducer is not None:
             raise NotImplementedError("micro_batch with a reducer: the all-reduce inside a capture is untested")
+        if distiller is not None:
+            criterion = _check_distiller(distiller, criterion, model, reducer, "GraphedTrainStep(distiller=...)")
         if mixer is not None:
             criterion = _check_mixer(mixer, criterion, "GraphedTrainStep(mixer=...)")
         if ragged:
@@ -544,6 +755,8 @@ class GraphedTrainStep:
             if not self.in_graph and not grp.get("capturable", False):
                 raise ValueError("the optimizer must be built with capturable=True (its step count then lives on the device)")
         self.model, self.opt, self.reducer, self.meter, self.mixer = model, optimizer, reducer, meter, mixer
+        self.distiller = distiller
+        self.kd = self.agree = self.teacher_correct = None
         self.criterion = criterion or SmoothedCrossEntropyLoss()
         self.ragged, self._pad = bool(ragged), None
         if self.ragged:
@@ -557,6 +770,10 @@ class GraphedTrainStep:
         self._place = self.n_rows
         if mixer is not None:
             mixer.bind(x.device, B, x.shape[1]).push_hyper()  # state and records exist before the capture
+            if self._place is None:
+                self._place = torch.full((1,), B, device=x.device, dtype=torch.int32)
+        if distiller is not None:
+            distiller.bind(x.device).push_hyper()            # the two words exist before the capture
             if self._place is None:
                 self._place = torch.full((1,), B, device=x.device, dtype=torch.int32)
         self.micro_batch = micro_batch if micro_batch is not None and micro_batch < B else B
@@ -576,6 +793,7 @@ class GraphedTrainStep:
         keep_meter = None if meter is None else meter.bind(dev).snapshot()   # the block exists before the capture
         keep_mixer = None if mixer is None else mixer.snapshot()
         keep_x = None if mixer is None else self.x.clone()   # the warm-up mixes the static batch in place
+        keep_t = None if distiller is None else [b.clone() for b in distiller.teacher.buffers()]
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 self._one()
@@ -601,7 +819,10 @@ class GraphedTrainStep:
                 meter.restore(keep_meter)
             if mixer is not None:                        # nor its draws: the step counter is where the caller left it
                 mixer.restore(keep_mixer)
-        del keep_p, keep_b, keep_state, keep_meter, keep_mixer, keep_x
+            if distiller is not None:                    # an eval forward writes no buffer; should one, it is undone
+                for b, q in zip(distiller.teacher.buffers(), keep_t):
+                    b.copy_(q)
+        del keep_p, keep_b, keep_state, keep_meter, keep_mixer, keep_x, keep_t
         model.device_seed_counter = True                 # from here on the device counts the steps itself
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
@@ -641,7 +862,9 @@ class GraphedTrainStep:
                 self.opt.step()
             return self._fold(loss.detach(), _correct(self.criterion, out, self.y))
         loss, correct = _run_slices(self.model, self.criterion, self.x, self.y, self.micro_batch, weighted=self._place is None,
-                                    n_rows=self._place)
+                                    n_rows=self._place, **({} if self.distiller is None else dict(distiller=self.distiller)))
+        if self.distiller is not None:                   # static tensors of the graph's pool, like loss and correct
+            self.kd, self.agree, self.teacher_correct = self.criterion.step_sums
         if step:                                         # once, after the last slice (no reducer here: refused above)
             self.opt.step()
         return self._fold(loss, correct)
@@ -654,7 +877,8 @@ class GraphedTrainStep:
         return loss, correct
 
     def _addresses(self):
-        return tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
+        own = tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
+        return own if self.distiller is None else own + self.distiller._addresses()
 
     def __call__(self, x, y):
         if not self.model.training:
@@ -662,7 +886,8 @@ class GraphedTrainStep:
         if not self.ragged and (x.shape != self.x.shape or y.shape != self.y.shape):
             raise ValueError(f"captured for {tuple(self.x.shape)} / {tuple(self.y.shape)}, got {tuple(x.shape)} / {tuple(y.shape)}")
         if self._addresses() != self._addr:
-            raise RuntimeError("a parameter or buffer of the model was reallocated after the capture: capture again")
+            raise RuntimeError("a parameter or buffer of the model" + (" or of the teacher" if self.distiller is not None else "")
+                               + " was reallocated after the capture: capture again")
         averager = getattr(self.opt, "averager", None)
         if averager is not None:                         # a replay bypasses the optimizer's step() and its check
             averager._refuse_applied("a GraphedTrainStep replay")
@@ -677,6 +902,10 @@ class GraphedTrainStep:
             self.opt.push_hyper()                        # launches only when a param group's values changed
         if self.mixer is not None:
             self.mixer.push_hyper()                      # likewise
+        if self.distiller is not None:
+            if self.distiller.teacher.training:
+                raise RuntimeError("Distiller: the teacher is in train() mode -- the captured step holds its eval() forward")
+            self.distiller.push_hyper()                  # likewise
         self.graph.replay()
         self.model._drop_calls += self.n_slices          # host mirror of the device counter (model._seeds() in tests)
         for p, g in self._grads:
@@ -980,7 +1209,9 @@ class EpochLoop:
     `eval_averaged=True` evaluates on the optimizer's averaged weights (`optimizer.averager.applied()`).
     `meter`: a `TrainMeter` of the caller's (say, one with a step log); `evaluator`: anything with reset() / update(x, y) /
     result() -> {"loss", "acc": {k: ...}} in the Evaluator's place.  `mixer`: a `BatchMixer` handed to the train step (which
-    then uses a `MixedCrossEntropyLoss`); its state goes into the checkpoints.  Validation is untouched.
+    then uses a `MixedCrossEntropyLoss`); its state goes into the checkpoints.  `distiller`: a `Distiller` handed to the
+    train step (which then uses a `DistilledCrossEntropyLoss`); alpha and the temperature go into the checkpoints, the
+    teacher's weights do not.  Validation is untouched.
 
     `run(train_batches, val_batches, epochs, start_epoch=None)`: two re-iterable sources of (x, y) batches, on the CPU
     (copied with non_blocking=True; pinning is the loader's business, see collate.PinnedBatcher) or on the device.
@@ -992,14 +1223,16 @@ class EpochLoop:
 
     `resume(path)` loads a checkpoint of this loop (checkpoint.load_checkpoint): weights, optimizer, scheduler, the four
     lists, `start_epoch = epoch + 1`, best values from the lists; and from the file's 'extra' key the guard's, the
-    averager's, the meter's and the mixer's state and the model's dropout counter, so dropout masks and the mixer's draws
+    averager's, the meter's, the mixer's and the distiller's state and the model's dropout counter, so dropout masks and the mixer's draws
     go on where they stopped.  Torch's
     device generator state is NOT carried: it draws HWGATE's train-mode window thresholds (HWGATE.py:96), so a resumed
     HWGATE run draws other thresholds than the uninterrupted one would have."""
 
     def __init__(self, model, optimizer, scheduler, batch_size, example, num_classes, smooth_factor=0.01, k=1, graph=True,
                  micro_batch=None, out_prefix=None, save_interval=100, early_stopper=None, lr=None, eval_averaged=False,
-                 meter=None, evaluator=None, mixer=None):
+                 meter=None, evaluator=None, mixer=None, distiller=None):
+        if distiller is not None:
+            _check_distiller(distiller, None, model, None, "EpochLoop(distiller=...)")
         if isinstance(batch_size, bool) or not isinstance(batch_size, numbers.Integral) or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
         x, y = example
@@ -1020,6 +1253,7 @@ class EpochLoop:
         self.out_prefix, self.eval_averaged = out_prefix, bool(eval_averaged)
         self.lr = _plain_lr(optimizer.param_groups[0]["lr"]) if lr is None else lr
         self.meter, self.evaluator, self.step, self.mixer = meter, evaluator, None, mixer
+        self.distiller = distiller
         self.book = EpochBook(save_interval, early_stopper)
         self.start_epoch = 0
         self.padded = bool(getattr(model, "clips_independent_in_train", False))
@@ -1040,13 +1274,17 @@ class EpochLoop:
     def _build_step(self):
         x, y = self._on_device(*self.example)
         self.model.train()
-        if self.mixer is not None:
+        if self.distiller is not None:
+            crit = DistilledCrossEntropyLoss(self.smooth_factor)
+        elif self.mixer is not None:
             crit = MixedCrossEntropyLoss(self.smooth_factor)
         elif self.padded:
             crit = BatchSlicedCrossEntropyLoss(self.smooth_factor)
         else:
             crit = FusedSmoothedCrossEntropyLoss(self.smooth_factor)
         extra = {} if self.mixer is None else dict(mixer=self.mixer)      # without one the calls are what they were
+        if self.distiller is not None:
+            extra["distiller"] = self.distiller
         if self.graph:
             self.step = GraphedTrainStep(self.model, self.opt, x, y, criterion=crit, micro_batch=self.micro_batch,
                                          ragged=self.padded, meter=self.meter, **extra)
@@ -1099,6 +1337,8 @@ class EpochLoop:
                      meter=self.meter.state_dict(), drop_calls=int(getattr(self.model, "_drop_calls", 0)))
         if self.mixer is not None:
             extra["mixer"] = self.mixer.state_dict()
+        if self.distiller is not None:
+            extra["distiller"] = self.distiller.state_dict()
         return extra
 
     def _save(self, suffix, epoch):
@@ -1126,6 +1366,8 @@ class EpochLoop:
             self.meter.load_state_dict(extra["meter"])
         if self.mixer is not None and extra.get("mixer") is not None:
             self.mixer.load_state_dict(extra["mixer"])
+        if self.distiller is not None and extra.get("distiller") is not None:
+            self.distiller.load_state_dict(extra["distiller"])
         if "drop_calls" in extra and hasattr(self.model, "_drop_calls"):
             self.model._drop_calls = int(extra["drop_calls"])
             if self.model._seed_state.is_cuda:           # the device counter a captured step advances by itself
