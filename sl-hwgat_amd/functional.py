@@ -1377,36 +1377,119 @@ def dgcn_masked_sum(a, ma, b, mb):
 # rows): rows at or beyond it are left untouched by the forward and the accumulator and are zero in the backward.
 EVAL_ACC_HEADER_WORDS = 5       # n_samples, n_batches, n_invalid (int64), loss_sum_samples, loss_sum_batches (double)
 
-
-def _sce_check(logits, target):
+# The four criteria are one body.  `offset` None: the whole batch, `count` its n_valid; else one slice of a zero-padded
+# batch, `count` the batch's n_rows (a device int32 (1,) with its real row count) and `offset` the slice's first row in it
+# (a host integer): rows of the slice at or beyond n_rows - offset are dead.  target_b (B,) int64 and lam (B,) fp32, slices
+# of a mixer's records, make the target a pair; `teacher` (B, C) fp32 with the distillation `state` adds the soft term.
+def _ce_check(logits, target, count, offset, target_b, lam, teacher, state):
+    if (target_b is None) != (lam is None):
+        raise ValueError("target_b and lam come together (a mixer's records) or not at all")
     if logits.dim() != 2 or logits.dtype != torch.float32:
         raise ValueError(f"logits must be fp32 (B, C), got {logits.dtype} {tuple(logits.shape)}")
     if target.dtype != torch.int64 or target.shape != logits.shape[:1]:
         raise ValueError(f"target must be int64 (B,), got {target.dtype} {tuple(target.shape)}")
+    if offset is not None:
+        if count is None or count.dtype != torch.int32 or count.numel() != 1:
+            raise ValueError("n_rows must be a device int32 tensor of one element")
+        if not 0 <= offset < 2 ** 31:
+            raise ValueError(f"the slice's offset must be in [0, 2^31), got {offset}")
+    if lam is not None:
+        if target_b.dtype != torch.int64 or target_b.shape != target.shape:
+            raise ValueError(f"target_b must be int64 {tuple(target.shape)}, got {target_b.dtype} {tuple(target_b.shape)}")
+        if lam.dtype != torch.float32 or lam.shape != target.shape:
+            raise ValueError(f"lam must be fp32 {tuple(target.shape)}, got {lam.dtype} {tuple(lam.shape)}")
+    if teacher is not None:
+        if teacher.dtype != torch.float32 or teacher.shape != logits.shape:
+            raise ValueError(f"teacher must be fp32 {tuple(logits.shape)}, got {teacher.dtype} {tuple(teacher.shape)}")
+        _kd_state_check(state)
+
+
+def _ce_outputs(logits, sliced, paired, taught):
+    """the forward's result tuple on three fresh buffers (per-row vectors first, the scalars behind them): loss, row_loss,
+    lse, rank, pred; a slice adds correct, live; a pair or a teacher row_loss_b, rank_b; a teacher lse_s, lse_t, row_kd,
+    t_pred, kd, agree, t_correct"""
+    B, dev = logits.shape[0], logits.device
+    nf, ni = (6, 4) if taught else (3, 3) if paired else (2, 2)
+    f = torch.empty(nf * B + 1 + taught, device=dev, dtype=torch.float32)
+    i = torch.empty(ni * B + sliced, device=dev, dtype=torch.int32)
+    out = (f[nf * B:nf * B + 1], f[:B], f[B:2 * B], i[:B], i[B:2 * B])
+    if sliced:
+        words = torch.empty(3 if taught else 1, device=dev, dtype=torch.int64)
+        out += (words[:1], i[ni * B:])
+    if paired or taught:
+        out += (f[2 * B:3 * B], i[2 * B:3 * B])
+    if taught:
+        out += (f[3 * B:4 * B], f[4 * B:5 * B], f[5 * B:6 * B], i[3 * B:4 * B], f[6 * B + 1:], words[1:2], words[2:])
+    return out
+
+
+def _ce_entry(sliced, paired, taught):
+    """the entry points' stem: each form has its own, named after what it adds"""
+    return "hwgat_kd" if taught else "hwgat_mbsce" if paired else "hwgat_bsce" if sliced else "hwgat_sce"
+
+
+def _ce_forward(logits, target, eps, count, offset=None, target_b=None, lam=None, teacher=None, state=None, out=None):
+    _ce_check(logits, target, count, offset, target_b, lam, teacher, state)
+    B, C = logits.shape
+    sliced, paired, taught = offset is not None, lam is not None, teacher is not None
+    if out is None:
+        out = _ce_outputs(logits, sliced, paired, taught)
+    # the parameter lists of the four entry points are cuts of hwgat_kd_fwd's: what a restricted form lacks, it does not
+    # take (built up in place, once, after the choice: this is host time of every step)
+    args = (ptr(logits),)
+    if taught:
+        args += (ptr(teacher),)
+    args += (ptr(target),)
+    if paired or taught:
+        args += (ptr(target_b), ptr(lam))
+    args += (ptr(count),)
+    if sliced:
+        args += (offset,)
+    if taught:
+        args += (ptr(state),)
+    args += (ptr(out[2]), ptr(out[1]), ptr(out[3]), ptr(out[4]), ptr(out[0]))          # lse, row_loss, rank, pred, loss
+    if sliced:
+        args += (ptr(out[5]), ptr(out[6]))                                                # correct, live
+    if paired or taught:
+        args += (ptr(out[7]), ptr(out[8])) if paired else (None, None)                    # row_loss_b, rank_b: not written
+    if taught:
+        args += tuple(map(ptr, out[9:]))                       # lse_s, lse_t, row_kd, t_pred, kd, agree, t_correct
+    call(_ce_entry(sliced, paired, taught) + "_fwd", *args, B, C, float(eps), stream())
+    return out
+
+
+def _ce_backward(logits, target, lse, g, eps, count, offset=None, target_b=None, lam=None, teacher=None, state=None,
+                 lse_s=None, lse_t=None, out=None):
+    _ce_check(logits, target, count, offset, target_b, lam, teacher, state)
+    B, C = logits.shape
+    sliced, paired, taught = offset is not None, lam is not None, teacher is not None
+    dz = torch.empty_like(logits) if out is None else out
+    args = (ptr(logits),)
+    if taught:
+        args += (ptr(teacher),)
+    args += (ptr(target),)
+    if paired or taught:
+        args += (ptr(target_b), ptr(lam))
+    args += (ptr(count),)
+    if sliced:
+        args += (offset,)
+    if taught:
+        args += (ptr(state), ptr(lse), ptr(lse_s), ptr(lse_t))
+    else:
+        args += (ptr(lse),)
+    call(_ce_entry(sliced, paired, taught) + "_bwd", *args, ptr(g), ptr(dz), B, C, float(eps), stream())
+    return dz
 
 
 def sce_forward(logits, target, eps, n_valid=None, out=None):
     """(loss (1,), row_loss (B,), lse (B,), rank (B,) int32, pred (B,) int32) of the smoothed cross-entropy; `out` takes the
     same five tensors preallocated"""
-    _sce_check(logits, target)
-    B, C = logits.shape
-    if out is None:
-        f = torch.empty(2 * B + 1, device=logits.device, dtype=torch.float32)
-        i = torch.empty(2, B, device=logits.device, dtype=torch.int32)
-        out = (f[2 * B:], f[:B], f[B:2 * B], i[0], i[1])
-    loss, row_loss, lse, rank, pred = out
-    call("hwgat_sce_fwd", ptr(logits), ptr(target), ptr(n_valid), ptr(lse), ptr(row_loss), ptr(rank), ptr(pred), ptr(loss),
-         B, C, float(eps), stream())
-    return out
+    return _ce_forward(logits, target, eps, n_valid, out=out)
 
 
 def sce_backward(logits, target, lse, g, eps, n_valid=None, out=None):
     """d loss / d logits times the device scalar `g` (float32, one element)"""
-    _sce_check(logits, target)
-    B, C = logits.shape
-    dz = torch.empty_like(logits) if out is None else out
-    call("hwgat_sce_bwd", ptr(logits), ptr(target), ptr(n_valid), ptr(lse), ptr(g), ptr(dz), B, C, float(eps), stream())
-    return dz
+    return _ce_backward(logits, target, lse, g, eps, n_valid, out=out)
 
 
 def eval_acc_words(num_classes, k_max, cap):
@@ -1447,64 +1530,108 @@ def smooth_ce(logits, target, eps, n_valid=None):
     return _SmoothCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_valid)
 
 
-# ---- the same loss for one slice of a zero-padded batch: `n_rows` is a device int32 (1,) holding the batch's real row count,
-# `offset` the slice's first row in the batch (a host integer); rows of the slice at or beyond n_rows - offset are dead
-def _bsce_check(logits, target, n_rows, offset):
-    _sce_check(logits, target)
-    if n_rows is None or n_rows.dtype != torch.int32 or n_rows.numel() != 1:
-        raise ValueError("n_rows must be a device int32 tensor of one element")
-    if not 0 <= int(offset) < 2 ** 31:
-        raise ValueError(f"the slice's offset must be in [0, 2^31), got {offset}")
+class _SlicedCE(torch.autograd.Function):
+    """the autograd node of the three slice criteria.  Results: loss, rank, pred, correct; a teacher adds t_pred, kd, agree,
+    t_correct.  Only the loss is differentiable, and only with respect to the (student's) logits.  (The whole-batch
+    criterion keeps _SmoothCE: its n_valid has other semantics and it has no correct count)"""
+
+    @staticmethod
+    def forward(ctx, logits, target, eps, n_rows, offset, target_b, lam, teacher, state):
+        out = _ce_forward(logits, target, eps, n_rows, offset, target_b, lam, teacher, state)
+        ctx.paired, ctx.taught = lam is not None, teacher is not None
+        ctx.save_for_backward(logits, target, out[2], *((target_b, lam) if ctx.paired else ()),
+                              *((teacher, state, out[9], out[10]) if ctx.taught else ()))        # out[2]: lse; lse_s, lse_t
+        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
+        # the views that go out are what is marked: a float view left unmarked would carry a grad_fn and keep the node alive
+        res = (out[3], out[4], out[5].view(()))            # rank, pred, correct
+        if ctx.taught:
+            res += (out[12], out[13].view(()), out[14].view(()), out[15].view(()))
+        ctx.mark_non_differentiable(*res)
+        return (out[0].view(()),) + res
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        logits, target, lse, *rest = ctx.saved_tensors
+        target_b, lam = rest[:2] if ctx.paired else (None, None)
+        teacher, state, lse_s, lse_t = rest[-4:] if ctx.taught else (None,) * 4
+        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
+        dz = _ce_backward(logits, target, lse, g, ctx.eps, ctx.n_rows, ctx.offset, target_b, lam, teacher, state, lse_s, lse_t)
+        return (dz,) + (None,) * 8
 
 
+def _needs(form, **members):
+    """a restricted launcher refuses what its form cannot do without, instead of quietly becoming a smaller form"""
+    missing = [k for k, v in members.items() if v is None]
+    if missing:
+        raise ValueError(f"{form} needs {' and '.join(missing)}")
+
+
+# ---- the same loss for one slice of a zero-padded batch
 def bsce_forward(logits, target, eps, n_rows, offset, out=None):
     """(loss (1,), row_loss (B,), lse (B,), rank (B,) int32, pred (B,) int32, correct (1,) int64, live (1,) int32) of one
     slice: loss is the live rows' sum over the BATCH's row count (exactly 0 for a slice without live rows), correct the
     number of live rows whose target ranks first; dead rows of the per-row outputs are not written.  `out` takes the same
     seven tensors preallocated"""
-    _bsce_check(logits, target, n_rows, offset)
-    B, C = logits.shape
-    if out is None:
-        f = torch.empty(2 * B + 1, device=logits.device, dtype=torch.float32)
-        i = torch.empty(2 * B + 1, device=logits.device, dtype=torch.int32)
-        out = (f[2 * B:], f[:B], f[B:2 * B], i[:B], i[B:2 * B], torch.empty(1, device=logits.device, dtype=torch.int64),
-               i[2 * B:])
-    loss, row_loss, lse, rank, pred, correct, live = out
-    call("hwgat_bsce_fwd", ptr(logits), ptr(target), ptr(n_rows), int(offset), ptr(lse), ptr(row_loss), ptr(rank), ptr(pred),
-         ptr(loss), ptr(correct), ptr(live), B, C, float(eps), stream())
-    return out
+    return _ce_forward(logits, target, eps, n_rows, int(offset), out=out)
 
 
 def bsce_backward(logits, target, lse, g, eps, n_rows, offset, out=None):
     """d loss / d logits of bsce_forward times the device scalar `g`; exactly zero in the dead rows"""
-    _bsce_check(logits, target, n_rows, offset)
-    B, C = logits.shape
-    dz = torch.empty_like(logits) if out is None else out
-    call("hwgat_bsce_bwd", ptr(logits), ptr(target), ptr(n_rows), int(offset), ptr(lse), ptr(g), ptr(dz), B, C, float(eps),
-         stream())
-    return dz
-
-
-class _BatchSlicedCE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, eps, n_rows, offset):
-        loss, _, lse, rank, pred, correct, _ = bsce_forward(logits, target, eps, n_rows, offset)
-        ctx.save_for_backward(logits, target, lse)
-        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
-        ctx.mark_non_differentiable(rank, pred, correct)
-        return loss.view(()), rank, pred, correct.view(())
-
-    @staticmethod
-    def backward(ctx, g, _rank, _pred, _correct):
-        logits, target, lse = ctx.saved_tensors
-        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
-        return bsce_backward(logits, target, lse, g, ctx.eps, ctx.n_rows, ctx.offset), None, None, None, None
+    return _ce_backward(logits, target, lse, g, eps, n_rows, int(offset), out=out)
 
 
 def batch_sliced_ce(logits, target, eps, n_rows, offset):
     """(loss, rank, pred, correct): a slice's share of the batch-mean smoothed cross-entropy as an autograd node (forward
     three launches, backward one), with the detached rank and arg-max of its live rows and their correct count (int64)"""
-    return _BatchSlicedCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_rows, int(offset))
+    return _SlicedCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_rows, int(offset), None, None, None,
+                          None)
+
+
+# ---- the slice criterion with two targets
+def mbsce_forward(logits, target, target_b, lam, eps, n_rows, offset, out=None):
+    """bsce_forward with two targets and a weight per row: (loss, row_loss, lse, rank, pred, correct, live, row_loss_b,
+    rank_b); row_loss is lam l(t) + (1 - lam) l(t_b), rank the dominant label's (t when lam >= 0.5), row_loss_b / rank_b (B,)
+    the partner label's own.  `out` takes the same nine tensors preallocated"""
+    _needs("mbsce_forward", target_b=target_b, lam=lam)
+    return _ce_forward(logits, target, eps, n_rows, int(offset), target_b, lam, out=out)
+
+
+def mbsce_backward(logits, target, target_b, lam, lse, g, eps, n_rows, offset, out=None):
+    """d loss / d logits of mbsce_forward times the device scalar `g`; exactly zero in the dead rows"""
+    _needs("mbsce_backward", target_b=target_b, lam=lam)
+    return _ce_backward(logits, target, lse, g, eps, n_rows, int(offset), target_b, lam, out=out)
+
+
+def mixed_sliced_ce(logits, target, target_b, lam, eps, n_rows, offset):
+    """(loss, rank, pred, correct): batch_sliced_ce with the pair target -- lam l(target) + (1 - lam) l(target_b) per row,
+    rank and correct on the dominant label -- as an autograd node (forward four launches, backward one)"""
+    return _SlicedCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_rows, int(offset),
+                          target_b.contiguous(), lam.contiguous(), None, None)
+
+
+# ---- the slice criterion with a teacher's logits beside the labels (the state: kd_state / kd_set below)
+def kd_forward(logits, teacher, target, target_b, lam, state, eps, n_rows, offset, out=None):
+    """mbsce_forward blended with the tempered KL from the teacher's logits: (loss, row_loss, lse, rank, pred, correct, live,
+    row_loss_b, rank_b, lse_s, lse_t, row_kd, t_pred, kd, agree, t_correct).  `target_b` and `lam` are both None without a
+    mixer (row_loss_b / rank_b are then not written).  `out` takes the same sixteen tensors preallocated"""
+    _needs("kd_forward", teacher=teacher, state=state)
+    return _ce_forward(logits, target, eps, n_rows, int(offset), target_b, lam, teacher, state, out=out)
+
+
+def kd_backward(logits, teacher, target, target_b, lam, state, lse, lse_s, lse_t, g, eps, n_rows, offset, out=None):
+    """d loss / d logits of kd_forward times the device scalar `g`; exactly zero in the dead rows"""
+    _needs("kd_backward", teacher=teacher, state=state, lse_s=lse_s, lse_t=lse_t)
+    return _ce_backward(logits, target, lse, g, eps, n_rows, int(offset), target_b, lam, teacher, state, lse_s, lse_t, out=out)
+
+
+def distilled_sliced_ce(logits, teacher, target, target_b, lam, state, eps, n_rows, offset):
+    """(loss, rank, pred, correct, t_pred, kd, agree, t_correct): mixed_sliced_ce (batch_sliced_ce when `target_b` and `lam`
+    are None) blended with the tempered KL from `teacher` as (1 - alpha) hard + alpha kd, alpha and tau read from the device
+    words of `state` when the kernels run, as an autograd node (forward at most five launches, backward one).  The
+    gradient goes to the student's logits only"""
+    return _SlicedCE.apply(logits.float().contiguous(), target.contiguous(), float(eps), n_rows, int(offset),
+                          None if target_b is None else target_b.contiguous(), None if lam is None else lam.contiguous(),
+                          teacher.detach().float().contiguous(), state)
 
 
 # ---------------------------------------------------------------- train meters (csrc/train_meter.hip, train.TrainMeter)
@@ -1845,67 +1972,6 @@ def mix_apply(x, pairs, lam, seg, mode, n_rows=None):
     call("hwgat_mix_apply", ptr(x), ptr(pairs), ptr(lam), ptr(seg), ptr(mode), ptr(n_rows), B, T, x[0, 0].numel(), stream())
 
 
-# ---- the slice criterion with two targets: target_b (B,) int64 and lam (B,) fp32 are slices of the mixer's records
-def _mbsce_check(logits, target, target_b, lam, n_rows, offset):
-    _bsce_check(logits, target, n_rows, offset)
-    if target_b.dtype != torch.int64 or target_b.shape != target.shape:
-        raise ValueError(f"target_b must be int64 {tuple(target.shape)}, got {target_b.dtype} {tuple(target_b.shape)}")
-    if lam.dtype != torch.float32 or lam.shape != target.shape:
-        raise ValueError(f"lam must be fp32 {tuple(target.shape)}, got {lam.dtype} {tuple(lam.shape)}")
-
-
-def mbsce_forward(logits, target, target_b, lam, eps, n_rows, offset, out=None):
-    """bsce_forward with two targets and a weight per row: (loss, row_loss, lse, rank, pred, correct, live, row_loss_b,
-    rank_b); row_loss is lam l(t) + (1 - lam) l(t_b), rank the dominant label's (t when lam >= 0.5), row_loss_b / rank_b (B,)
-    the partner label's own.  `out` takes the same nine tensors preallocated"""
-    _mbsce_check(logits, target, target_b, lam, n_rows, offset)
-    B, C = logits.shape
-    if out is None:
-        f = torch.empty(3 * B + 1, device=logits.device, dtype=torch.float32)
-        i = torch.empty(3 * B + 1, device=logits.device, dtype=torch.int32)
-        out = (f[3 * B:], f[:B], f[B:2 * B], i[:B], i[B:2 * B], torch.empty(1, device=logits.device, dtype=torch.int64),
-               i[3 * B:], f[2 * B:3 * B], i[2 * B:3 * B])
-    loss, row_loss, lse, rank, pred, correct, live, row_loss_b, rank_b = out
-    call("hwgat_mbsce_fwd", ptr(logits), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(lse),
-         ptr(row_loss), ptr(rank), ptr(pred), ptr(loss), ptr(correct), ptr(live), ptr(row_loss_b), ptr(rank_b), B, C,
-         float(eps), stream())
-    return out
-
-
-def mbsce_backward(logits, target, target_b, lam, lse, g, eps, n_rows, offset, out=None):
-    """d loss / d logits of mbsce_forward times the device scalar `g`; exactly zero in the dead rows"""
-    _mbsce_check(logits, target, target_b, lam, n_rows, offset)
-    B, C = logits.shape
-    dz = torch.empty_like(logits) if out is None else out
-    call("hwgat_mbsce_bwd", ptr(logits), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(lse), ptr(g),
-         ptr(dz), B, C, float(eps), stream())
-    return dz
-
-
-class _MixedSlicedCE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, target_b, lam, eps, n_rows, offset):
-        loss, _, lse, rank, pred, correct = mbsce_forward(logits, target, target_b, lam, eps, n_rows, offset)[:6]
-        ctx.save_for_backward(logits, target, target_b, lam, lse)
-        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
-        ctx.mark_non_differentiable(rank, pred, correct)
-        return loss.view(()), rank, pred, correct.view(())
-
-    @staticmethod
-    def backward(ctx, g, _rank, _pred, _correct):
-        logits, target, target_b, lam, lse = ctx.saved_tensors
-        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
-        dz = mbsce_backward(logits, target, target_b, lam, lse, g, ctx.eps, ctx.n_rows, ctx.offset)
-        return dz, None, None, None, None, None, None
-
-
-def mixed_sliced_ce(logits, target, target_b, lam, eps, n_rows, offset):
-    """(loss, rank, pred, correct): batch_sliced_ce with the pair target -- lam l(target) + (1 - lam) l(target_b) per row,
-    rank and correct on the dominant label -- as an autograd node (forward four launches, backward one)"""
-    return _MixedSlicedCE.apply(logits.float().contiguous(), target.contiguous(), target_b.contiguous(), lam.contiguous(),
-                                float(eps), n_rows, int(offset))
-
-
 # ---------------------------------------------------------------- knowledge distillation (csrc/loss_eval.hip, train.Distiller)
 # The slice criterion with a teacher's logits beside the labels.  The state is two device floats, alpha and tau.
 KD_STATE_WORDS = 2
@@ -1928,79 +1994,3 @@ def kd_set(state, alpha, tau):
     """write alpha and tau.  One tiny launch, stream-ordered"""
     _kd_state_check(state)
     call("hwgat_kd_set", ptr(state), float(alpha), float(tau), stream())
-
-
-def _kd_check(logits, teacher, target, target_b, lam, state, n_rows, offset):
-    if (target_b is None) != (lam is None):
-        raise ValueError("target_b and lam come together (a mixer's records) or not at all")
-    if lam is None:
-        _bsce_check(logits, target, n_rows, offset)
-    else:
-        _mbsce_check(logits, target, target_b, lam, n_rows, offset)
-    if teacher.dtype != torch.float32 or teacher.shape != logits.shape:
-        raise ValueError(f"teacher must be fp32 {tuple(logits.shape)}, got {teacher.dtype} {tuple(teacher.shape)}")
-    _kd_state_check(state)
-
-
-def kd_forward(logits, teacher, target, target_b, lam, state, eps, n_rows, offset, out=None):
-    """mbsce_forward blended with the tempered KL from the teacher's logits: (loss, row_loss, lse, rank, pred, correct, live,
-    row_loss_b, rank_b, lse_s, lse_t, row_kd, t_pred, kd, agree, t_correct).  `target_b` and `lam` are both None without a
-    mixer (row_loss_b / rank_b are then not written).  `out` takes the same sixteen tensors preallocated"""
-    _kd_check(logits, teacher, target, target_b, lam, state, n_rows, offset)
-    B, C = logits.shape
-    if out is None:
-        f = torch.empty(6 * B + 2, device=logits.device, dtype=torch.float32)
-        i = torch.empty(4 * B + 1, device=logits.device, dtype=torch.int32)
-        l = torch.empty(3, device=logits.device, dtype=torch.int64)
-        out = (f[6 * B:6 * B + 1], f[:B], f[B:2 * B], i[:B], i[B:2 * B], l[:1], i[4 * B:], f[2 * B:3 * B], i[2 * B:3 * B],
-               f[3 * B:4 * B], f[4 * B:5 * B], f[5 * B:6 * B], i[3 * B:4 * B], f[6 * B + 1:], l[1:2], l[2:])
-    loss, row_loss, lse, rank, pred, correct, live, row_loss_b, rank_b, lse_s, lse_t, row_kd, t_pred, kd, agree, t_correct = out
-    mixed = lam is not None
-    call("hwgat_kd_fwd", ptr(logits), ptr(teacher), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(state),
-         ptr(lse), ptr(row_loss), ptr(rank), ptr(pred), ptr(loss), ptr(correct), ptr(live),
-         ptr(row_loss_b) if mixed else None, ptr(rank_b) if mixed else None, ptr(lse_s), ptr(lse_t), ptr(row_kd), ptr(t_pred),
-         ptr(kd), ptr(agree), ptr(t_correct), B, C, float(eps), stream())
-    return out
-
-
-def kd_backward(logits, teacher, target, target_b, lam, state, lse, lse_s, lse_t, g, eps, n_rows, offset, out=None):
-    """d loss / d logits of kd_forward times the device scalar `g`; exactly zero in the dead rows"""
-    _kd_check(logits, teacher, target, target_b, lam, state, n_rows, offset)
-    B, C = logits.shape
-    dz = torch.empty_like(logits) if out is None else out
-    call("hwgat_kd_bwd", ptr(logits), ptr(teacher), ptr(target), ptr(target_b), ptr(lam), ptr(n_rows), int(offset), ptr(state),
-         ptr(lse), ptr(lse_s), ptr(lse_t), ptr(g), ptr(dz), B, C, float(eps), stream())
-    return dz
-
-
-class _DistilledSlicedCE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, teacher, target, target_b, lam, state, eps, n_rows, offset):
-        out = kd_forward(logits, teacher, target, target_b, lam, state, eps, n_rows, offset)
-        loss, _, lse, rank, pred, correct = out[:6]
-        lse_s, lse_t, _, t_pred, kd, agree, t_correct = out[9:]
-        ctx.mixed = lam is not None
-        ctx.save_for_backward(logits, teacher, target, lse, lse_s, lse_t, state, *((target_b, lam) if ctx.mixed else ()))
-        ctx.eps, ctx.n_rows, ctx.offset = eps, n_rows, offset
-        # the views that go out are what is marked: a float view left unmarked would carry a grad_fn and keep the node alive
-        correct, kd, agree, t_correct = correct.view(()), kd.view(()), agree.view(()), t_correct.view(())
-        ctx.mark_non_differentiable(rank, pred, correct, t_pred, kd, agree, t_correct)
-        return loss.view(()), rank, pred, correct, t_pred, kd, agree, t_correct
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        logits, teacher, target, lse, lse_s, lse_t, state = ctx.saved_tensors[:7]
-        target_b, lam = ctx.saved_tensors[7:] if ctx.mixed else (None, None)
-        g = g.reshape(1).to(torch.float32)                 # stays on the device: nothing is read back
-        dz = kd_backward(logits, teacher, target, target_b, lam, state, lse, lse_s, lse_t, g, ctx.eps, ctx.n_rows, ctx.offset)
-        return (dz,) + (None,) * 8
-
-
-def distilled_sliced_ce(logits, teacher, target, target_b, lam, state, eps, n_rows, offset):
-    """(loss, rank, pred, correct, t_pred, kd, agree, t_correct): mixed_sliced_ce (batch_sliced_ce when `target_b` and `lam`
-    are None) blended with the tempered KL from `teacher` as (1 - alpha) hard + alpha kd, alpha and tau read from the device
-    words of `state` when the kernels run, as an autograd node (forward at most five launches, backward one).  The
-    gradient goes to the student's logits only"""
-    return _DistilledSlicedCE.apply(logits.float().contiguous(), teacher.detach().float().contiguous(), target.contiguous(),
-                                    None if target_b is None else target_b.contiguous(),
-                                    None if lam is None else lam.contiguous(), state, float(eps), n_rows, int(offset))

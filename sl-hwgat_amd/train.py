@@ -34,9 +34,7 @@ class FusedSmoothedCrossEntropyLoss(torch.nn.Module):
         self.last_rank = self.last_pred = None
 
     def forward(self, input, target):
-        import importlib
-        HF = importlib.import_module(__package__ + ".functional")
-        loss, self.last_rank, self.last_pred = HF.smooth_ce(input, target, self.smooth_factor)
+        loss, self.last_rank, self.last_pred = _functional().smooth_ce(input, target, self.smooth_factor)
         return loss
 
     def correct(self):
@@ -61,13 +59,11 @@ class BatchSlicedCrossEntropyLoss(torch.nn.Module):
         self.n_rows, self.offset = n_rows, int(offset)
 
     def forward(self, input, target):
-        import importlib
-        HF = importlib.import_module(__package__ + ".functional")
         if self.n_rows is None:
             raise RuntimeError("BatchSlicedCrossEntropyLoss: place(n_rows, offset) first -- TrainStep(pad_to=...) and "
                                "GraphedTrainStep(ragged=True) do")
-        loss, self.last_rank, self.last_pred, self._hits = HF.batch_sliced_ce(input, target, self.smooth_factor,
-                                                                              self.n_rows, self.offset)
+        loss, self.last_rank, self.last_pred, self._hits = _functional().batch_sliced_ce(
+            input, target, self.smooth_factor, self.n_rows, self.offset)
         return loss
 
     def correct(self):
@@ -94,12 +90,19 @@ class MixedCrossEntropyLoss(BatchSlicedCrossEntropyLoss):
         if self.n_rows is None or self.mixer is None or self.mixer.y_b is None:
             raise RuntimeError("MixedCrossEntropyLoss: bind_mixer(mixer), mixer.apply(...) and place(n_rows, offset) first -- "
                                "TrainStep(mixer=...) and GraphedTrainStep(mixer=...) do")
-        b, o = input.shape[0], self.offset
-        if o + b > self.mixer.y_b.shape[0]:
-            raise ValueError(f"the slice [{o}, {o + b}) lies outside the mixer's batch of {self.mixer.y_b.shape[0]} rows")
+        y_b, lam = self._mixer_slice(input.shape[0])
         loss, self.last_rank, self.last_pred, self._hits = _functional().mixed_sliced_ce(
-            input, target, self.mixer.y_b[o:o + b], self.mixer.lam[o:o + b], self.smooth_factor, self.n_rows, o)
+            input, target, y_b, lam, self.smooth_factor, self.n_rows, self.offset)
         return loss
+
+    def _mixer_slice(self, b):
+        """(y_b, lam) of the bound mixer's latest draw at the slice's place, rows [offset, offset + b)"""
+        m, o = self.mixer, self.offset
+        if m.y_b is None:                                  # the distilled criterion's case: the forward above refuses it itself
+            raise RuntimeError(f"{type(self).__name__}: the bound mixer has drawn nothing yet (mixer.apply(...) first)")
+        if o + b > m.y_b.shape[0]:
+            raise ValueError(f"the slice [{o}, {o + b}) lies outside the mixer's batch of {m.y_b.shape[0]} rows")
+        return m.y_b[o:o + b], m.lam[o:o + b]
 
 
 def _unit(name, v, lo=0.0):
@@ -399,17 +402,10 @@ class DistilledCrossEntropyLoss(MixedCrossEntropyLoss):
         if tuple(d.logits.shape) != tuple(input.shape):
             raise ValueError(f"the teacher gives logits of shape {tuple(d.logits.shape)} for a slice on which the student gives "
                              f"{tuple(input.shape)}: distillation needs the same classes in the same order")
-        b, o = input.shape[0], self.offset
-        y_b = lam = None
-        if self.mixer is not None:
-            if self.mixer.y_b is None:
-                raise RuntimeError("DistilledCrossEntropyLoss: the bound mixer has drawn nothing yet (mixer.apply(...) first)")
-            if o + b > self.mixer.y_b.shape[0]:
-                raise ValueError(f"the slice [{o}, {o + b}) lies outside the mixer's batch of {self.mixer.y_b.shape[0]} rows")
-            y_b, lam = self.mixer.y_b[o:o + b], self.mixer.lam[o:o + b]
+        y_b, lam = (None, None) if self.mixer is None else self._mixer_slice(input.shape[0])
         (loss, self.last_rank, self.last_pred, self._hits, self.last_teacher_pred, self.last_kd, self._agree,
          self._t_hits) = _functional().distilled_sliced_ce(input, d.logits, target, y_b, lam, d.state, self.smooth_factor,
-                                                           self.n_rows, o)
+                                                           self.n_rows, self.offset)
         return loss
 
     def agree(self):

@@ -277,6 +277,58 @@ def test_every_kernel_is_bit_reproducible(B, C):
     assert a["n"] == 3 * B and a["batches"] == 3 and int(a["hist"].sum()) == 3 * B
 
 
+# ------------------------------------------------------------------------------------------ kernels: the one row rule
+def _bits(t):
+    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _word(n):
+    return torch.tensor([n], device=DEV, dtype=torch.int32)
+
+
+# (b, C, floats the logits sit past a 16-byte boundary): the cases of tests/test_gpu_graph_micro.py
+ROW_RULE_CASES = [(3, 7, 0), (4, 2003, 1), (5, 2002, 0), (3, 2004, 0), (3, 2004, 1)]
+
+
+@pytest.mark.parametrize("b,C,shift", ROW_RULE_CASES)
+def test_slice_at_offset_zero_is_the_batch_with_n_valid_bit_for_bit(b, C, shift):
+    """A slice that starts at row 0 of a batch with n real rows has n live rows and divides by n: the same rows, the same
+    sums in the same order and the same divisor as the whole batch with n_valid = n.  So loss, the live rows' outputs and
+    the whole gradient (exact zeros in the dead rows) agree in every bit; only the empty case differs by rule (slice: 0,
+    batch: NaN).  A slice at or beyond the batch's last real row is as empty as one of a batch without rows."""
+    eps = 0.01
+    g = torch.Generator().manual_seed(1000 * b + C)
+    flat = torch.zeros(b * C + 4, device=DEV)
+    zd = flat[shift:shift + b * C].view(b, C)
+    zd.copy_(torch.randn(b, C, generator=g))
+    assert zd.data_ptr() % 16 == 4 * shift and zd.is_contiguous()
+    yd = torch.randint(0, C, (b,), generator=g).to(DEV)
+    yd[0] = zd[0].argmax()                                   # one row that counts as correct
+    up = g_dev()
+    for n in range(1, b + 1):
+        s_loss, s_rows, s_lse, s_rank, s_pred, correct, live = HF.bsce_forward(zd, yd, eps, _word(n), 0)
+        b_loss, b_rows, b_lse, b_rank, b_pred = HF.sce_forward(zd, yd, eps, n_valid=_word(n))
+        assert torch.equal(_bits(s_loss), _bits(b_loss)) and torch.isfinite(s_loss).all()
+        for s, t in ((s_rows, b_rows), (s_lse, b_lse), (s_rank, b_rank), (s_pred, b_pred)):
+            assert torch.equal(_bits(s[:n]), _bits(t[:n]))
+        assert int(correct) == int((s_rank[:n] == 0).sum()) >= 1 and int(live) == n
+        s_dz = HF.bsce_backward(zd, yd, s_lse, up, eps, _word(n), 0, out=torch.full((b, C), 7.5, device=DEV))
+        b_dz = HF.sce_backward(zd, yd, b_lse, up, eps, _word(n), out=torch.full((b, C), 7.5, device=DEV))
+        assert torch.equal(_bits(s_dz), _bits(b_dz))
+        assert (_bits(s_dz[n:]) == 0).all() and (s_dz[:n] != 0).any(dim=1).all()
+    # no live row.  The slice: +0.0 and zeros, from an empty batch and from an offset at or beyond the batch's last real row
+    lse = HF.sce_forward(zd, yd, eps)[2]
+    for n_rows, offset in ((0, 0), (2, 2), (2, 5)):
+        out = HF.bsce_forward(zd, yd, eps, _word(n_rows), offset)
+        assert int(_bits(out[0])) == 0 and int(out[5]) == 0 and int(out[6]) == 0
+        dz = HF.bsce_backward(zd, yd, lse, up, eps, _word(n_rows), offset, out=torch.full((b, C), 7.5, device=DEV))
+        assert (_bits(dz) == 0).all()
+    # the batch: an empty mean is NaN; the gradient is zeros all the same
+    assert torch.isnan(HF.sce_forward(zd, yd, eps, n_valid=_word(0))[0]).all()
+    dz = HF.sce_backward(zd, yd, lse, up, eps, _word(0), out=torch.full((b, C), 7.5, device=DEV))
+    assert (_bits(dz) == 0).all()
+
+
 # ------------------------------------------------------------------------------------------ the criterion in a train step
 def _hwgate(training=True):
     """the configuration of tests/test_gpu_graph.py"""
