@@ -83,7 +83,9 @@ extern "C" {
  *         data.DeviceLoader; hwgat_attn_probs(_numel), the attention-map export of the five attention kinds;
  *         hwgat_mix_{state_bytes,set,draw,apply}, Mixup and temporal CutMix of the pairs of a batch, and
  *         hwgat_mbsce_{fwd,bwd}, the slice criterion with two targets and a weight per row;
- *         hwgat_kd_{state_bytes,set,fwd,bwd}, the same criterion distilled from a teacher's logits (additions only) */
+ *         hwgat_kd_{state_bytes,set,fwd,bwd}, the same criterion distilled from a teacher's logits (additions only);
+ *         hwgat_modality, the bone / motion / bone-motion views of a keypoint clip, and hwgat_ens_fuse, the fused score of
+ *         an ensemble's member logits (additions only) */
 #define HWGAT_ABI_VERSION 4007
 int hwgat_abi_version(void);
 
@@ -1362,6 +1364,48 @@ int hwgat_kd_bwd(const float* logits, const float* teacher, const int64_t* targe
 int hwgat_head_fwd(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K, void* stream);
 int hwgat_head_bwd_dx(const float* dY, const float* W, float* dX, int M, int N, int K, void* stream);
 int hwgat_head_bwd_dw(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, void* stream);
+
+/* ---- input modalities (csrc/modality.hip; modality.Modality, the models' `input_modality`).  The four views of a keypoint
+ * clip that multi-stream skeleton recognisers train on.  x and out are (B, T, J, C) fp32, contiguous; out must not overlap
+ * x (HWGAT_EINVAL).  parent: J int32 words in DEVICE memory, p = parent[j] the joint that joint j hangs on, parent[j] == j a
+ * root; the kernel reduces what it reads to [0, J).  parent may be NULL for the kinds that do not read it.
+ *   HWGAT_MOD_JOINT        out[b,t,j,c] = x[b,t,j,c]
+ *   HWGAT_MOD_BONE         out[b,t,j,c] = x[b,t,j,c] - x[b,t,p,c];  a root gives +0.0 whatever x holds
+ *   HWGAT_MOD_MOTION       out[b,t,j,c] = x[b,t+1,j,c] - x[b,t,j,c] for t < T - 1;  0 at t = T - 1
+ *   HWGAT_MOD_BONE_MOTION  out[b,t,j,c] = (x[b,t+1,j,c] - x[b,t+1,p,c]) - (x[b,t,j,c] - x[b,t,p,c]), each bracket rounded to
+ *                          fp32 (a root's bracket is +0.0), then their difference;  0 at t = T - 1
+ * Padding (use_pad != 0): frame (b, t) is padding iff x[b,t,0,0] == pad_value -- hwgat_seq_embed_fwd's rule for the
+ * key-padding words.  A padded frame is copied to out unchanged for every kind, and the two motion kinds give 0 at a frame
+ * whose successor is padded.  With use_pad == 0 pad_value is not read.
+ * Every entry is a copy, one IEEE subtraction or the difference of two: the result is exact.  One launch, one pass, no
+ * atomics, no LDS, no workspace.
+ * HWGAT_EINVAL: a NULL x or out, a non-positive size, a NULL parent with a bone kind, overlapping x and out.  HWGAT_ESHAPE:
+ * kind outside 0..3, J C > 2^20, more than 2^31 - 1 workgroups of 256 entries. */
+#define HWGAT_MOD_JOINT 0
+#define HWGAT_MOD_BONE 1
+#define HWGAT_MOD_MOTION 2
+#define HWGAT_MOD_BONE_MOTION 3
+int hwgat_modality(const float* x, const int32_t* parent, float* out, int B, int T, int J, int C, int kind, int use_pad,
+                   float pad_value, void* stream);
+
+/* ---- score ensemble (csrc/ensemble.hip; ensemble.Ensemble).  z (M, B, C) fp32: the logits of M members; w: M fp32 weights
+ * in DEVICE memory, read when the kernel runs (a captured evaluation follows a new weight without a new capture);
+ * out (B, C) fp32, overwritten.  1 <= M <= HWGAT_ENS_MAX_MEMBERS and mode 0 or 1, else HWGAT_ESHAPE; a NULL pointer or a
+ * non-positive B or C is HWGAT_EINVAL.
+ *   HWGAT_ENS_LOGIT  out[b,c] = sum_m w[m] z[m,b,c], every product and sum rounded to fp32, members in order from 0.0: the
+ *                    error is at most (M + 1) 2^-24 sum_m |w[m] z[m,b,c]|.  Every member is read.
+ *   HWGAT_ENS_PROB   out[b,c] = log sum_m w[m] softmax(z[m,b,:])[c], evaluated as the log-sum-exp over the members of
+ *                    log w[m] + z[m,b,c] - lse[m,b] with the largest term taken out: no probability is formed, so none
+ *                    underflows.  lse[m,b] = max + log(sum expf(z - max)), the sum and everything after it in double; an
+ *                    entry is rounded to fp32 once.  A member whose weight is not > 0 is not read.  With weights summing
+ *                    to 1 a row of out is a normalised log-distribution; with one member of weight 1 it is its
+ *                    log_softmax.  A class to which every member read gives -inf is -inf.
+ * Non-finite logits of a member that is read propagate (a NaN makes its row of out NaN in prob mode, its entry in logit
+ * mode); nothing is masked.  One launch, one workgroup per row b, no float atomics, no workspace: a repeat is bit-equal. */
+#define HWGAT_ENS_MAX_MEMBERS 8
+#define HWGAT_ENS_LOGIT 0
+#define HWGAT_ENS_PROB 1
+int hwgat_ens_fuse(const float* z, const float* w, float* out, int M, int B, int C, int mode, void* stream);
 
 #ifdef __cplusplus
 }

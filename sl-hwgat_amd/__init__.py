@@ -25,8 +25,11 @@ from .models.DecoupledGCN import Model as DecoupledGCNModel
 from .models.model_params import (HWGATEParams, HGATEParams, WGATEParams, GATEParams, TransformerParams, STGCNParams,
                                   DecoupledGCNParams)
 from . import explain
+from . import modality
+from . import ensemble
 
 __all__ = ["Model", "HWGATEParams", "HGATEModel", "HGATEParams", "WGATEModel", "WGATEParams", "GATEModel", "GATEParams",
            "TransformerModel",
            "TransformerParams", "STGCNModel", "STGCNParams", "DecoupledGCNModel", "DecoupledGCNParams", "functional",
-           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim", "data", "explain"]
+           "part_table", "_lib", "checkpoint", "augment", "evaluate", "optim", "data", "explain",
+           "modality", "ensemble"]

@@ -165,6 +165,8 @@ _SIGS = {
     "hwgat_head_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dx": [_P, _P, _P, _I, _I, _I, _P],
     "hwgat_head_bwd_dw": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "hwgat_modality": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "hwgat_ens_fuse": [_P, _P, _P, _I, _I, _I, _I, _P],
 }
 _lib = None
 

@@ -1994,3 +1994,80 @@ def kd_set(state, alpha, tau):
     """write alpha and tau.  One tiny launch, stream-ordered"""
     _kd_state_check(state)
     call("hwgat_kd_set", ptr(state), float(alpha), float(tau), stream())
+
+
+# ---------------------------------------------------------------- input modalities (csrc/modality.hip, modality.Modality)
+MOD_KINDS = ("joint", "bone", "motion", "bone_motion")          # HWGAT_MOD_*: the position is the code
+
+
+def _overlap(a, b):
+    """two contiguous tensors share memory"""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def modality(x, parent, kind, pad_value=None, out=None):
+    """the `kind` view (a name of MOD_KINDS or its code) of the keypoints x (B, T, J, C) fp32: joints, bones over the device
+    int32 table `parent` (J,), joint motion or bone motion; `pad_value` marks padded frames by their first word (None: no
+    padding).  x is left alone; returns a new tensor, or `out`.  One launch"""
+    code = MOD_KINDS.index(kind) if kind in MOD_KINDS else kind
+    if isinstance(code, bool) or not isinstance(code, int) or not 0 <= code < len(MOD_KINDS):
+        raise ValueError(f"modality: kind must be one of {MOD_KINDS} (or 0..3), got {kind!r}")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError(f"modality: x must be an fp32 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"modality: x must be a non-empty (B, T, J, C) tensor, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("modality: x must be contiguous")
+    B, T, J, C = x.shape
+    if code in (1, 3):
+        if parent is None:
+            raise ValueError(f"modality: kind {MOD_KINDS[code]!r} needs the parent table")
+        if parent.dtype != torch.int32 or tuple(parent.shape) != (J,):
+            raise ValueError(f"modality: parent must be a device int32 tensor of {J} elements, got {parent.dtype} "
+                             f"{tuple(parent.shape)}")
+    else:
+        parent = None
+    if out is None:
+        ptr(x)                                                    # refuses a CPU or strided x before anything is allocated
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+        raise ValueError(f"modality: out must be a contiguous fp32 {tuple(x.shape)} tensor")
+    elif _overlap(x, out):
+        raise ValueError("modality: out must not alias x (a frame's neighbours are read after stores)")
+    call("hwgat_modality", ptr(x), ptr(parent), ptr(out), B, T, J, C, code, int(pad_value is not None),
+         0.0 if pad_value is None else float(pad_value), stream())
+    return out
+
+
+# ---------------------------------------------------------------- score ensemble (csrc/ensemble.hip, ensemble.Ensemble)
+ENS_MAX_MEMBERS = 8                                              # HWGAT_ENS_MAX_MEMBERS
+ENS_MODES = ("logit", "prob")                                    # HWGAT_ENS_LOGIT, HWGAT_ENS_PROB
+
+
+def ens_fuse(z, w, mode, out=None):
+    """the fused score (B, C) of member logits z (M, B, C) fp32 under the device weights w (M,) fp32: mode 'logit' the
+    weighted sum of the logits, 'prob' the log of the weighted mean of the softmaxes.  One launch"""
+    if mode not in ENS_MODES:
+        raise ValueError(f"ens_fuse: mode must be one of {ENS_MODES}, got {mode!r}")
+    for name, t in (("z", z), ("w", w)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"ens_fuse: {name} must be an fp32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if z.dim() != 3 or z.numel() == 0:
+        raise ValueError(f"ens_fuse: z must be a non-empty (M, B, C) tensor, got {tuple(z.shape)}")
+    if not z.is_contiguous() or not w.is_contiguous():
+        raise ValueError("ens_fuse: z and w must be contiguous")
+    M, B, C = z.shape
+    if not 1 <= M <= ENS_MAX_MEMBERS:
+        raise ValueError(f"ens_fuse: 1 to {ENS_MAX_MEMBERS} members, got {M}")
+    if tuple(w.shape) != (M,):
+        raise ValueError(f"ens_fuse: w must hold {M} weights, got {tuple(w.shape)}")
+    if out is None:
+        ptr(z)
+        out = torch.empty((B, C), device=z.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, C) or not out.is_contiguous():
+        raise ValueError(f"ens_fuse: out must be a contiguous fp32 {(B, C)} tensor")
+    elif _overlap(z, out):
+        raise ValueError("ens_fuse: out must not alias z")
+    call("hwgat_ens_fuse", ptr(z), ptr(w), ptr(out), M, B, C, ENS_MODES.index(mode), stream())
+    return out

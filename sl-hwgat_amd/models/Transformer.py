@@ -127,6 +127,11 @@ class Model(DeviceSeeds, nn.Module):
 
     def forward_features(self, src):
         B, T = src.shape[0], src.shape[1]
+        if getattr(self, "input_modality", None) is not None:
+            if src.dim() != 4:
+                raise ValueError(f"an input modality needs (B, T, K, C) keypoints, got {tuple(src.shape)}: flattened frames "
+                                 "do not say which words are a joint's coordinates")
+            src = self._input_view(src.contiguous().float(), pad_value=self.pad_index)   # padded frames keep their marker
         x = src.reshape(B, T, -1)
         if x.shape[2] != self.input_dim:
             raise ValueError(f"expected {self.input_dim} features per frame, got {x.shape[2]} (input {tuple(src.shape)})")

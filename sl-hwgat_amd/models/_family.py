@@ -172,7 +172,7 @@ class FamilyModel(DeviceSeeds, nn.Module):
             if self.part_index is None:
                 raise ValueError(f"got {x.shape[2]} joints, model has {self.num_kps} slots and no part table")
             idx = self.part_index
-        x = x.contiguous().float()
+        x = self._input_view(x.contiguous().float())      # the modality sees the raw joints, in front of the part gather
         pe = self.pos_encoder.pe.view(self.temporal_dim, self.embed_dim) if self.pe else None
         seed_base = self._next_step_seed() if self.training else None     # this call's base seed: _call_base
         p_pe = self.drop_rate if (self.training and self.pe) else 0.0     # Dropout lives in PositionalEncoding

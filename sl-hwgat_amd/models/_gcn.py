@@ -106,7 +106,8 @@ class GCNModel(DeviceSeeds, nn.Module):
         N, T, V, C = x.shape
         if T < 1:
             raise ValueError("at least one frame")
-        return batch_norm_rows(x.contiguous().float().view(N * T, V * C), self.data_bn, self.training).view(N, T, V, C)
+        x = self._input_view(x.contiguous().float())
+        return batch_norm_rows(x.view(N * T, V * C), self.data_bn, self.training).view(N, T, V, C)
 
     def _tap(self, h):
         if self.block_tap is not None:

@@ -12,6 +12,7 @@ import torch
 from torch import nn
 
 from . import functional as HF
+from .modality import Modality
 
 
 class DeviceSeeds:
@@ -28,6 +29,7 @@ class DeviceSeeds:
         self.deterministic_eval = True                            # eval(): fixed-order sums, bit-reproducible logits
         self.deterministic_train = False                          # train(): the same for the whole step (slower: no float atomics anywhere)
         self.hip_head = False                                     # True: the classifier nn.Linear runs on csrc/head.hip (_classify)
+        self.input_modality = None                                # modality.Modality the forward reads its input through (set_input_modality)
 
     def _site_seeds(self, k):
         """four dropout-SITE seeds of block k (host integers that never change): proj, fc1, fc2 outputs
@@ -72,6 +74,24 @@ class DeviceSeeds:
         (`deterministic_train = True`: fixed-order row statistics, pooled sum and parameter gradients -- the reference's
         single-device training repeats itself bit for bit with fixed seeds, this is the mode that does the same)"""
         return bool(self.deterministic_train if self.training else self.deterministic_eval)
+
+    def set_input_modality(self, modality):
+        """read the input through `modality` (modality.Modality: bones, motion, bone motion) from the next forward on, or as
+        it comes with None (the default: no launch is added and every bit is what it was).  The view is one launch in
+        front of the model's first kernel and writes a tensor of its own; the caller's input is left alone.  The parent
+        table is a non-persistent buffer (`_modality_parents`, registered here): `state_dict()` keeps its keys and
+        `.to(device)` moves it"""
+        if modality is not None and not isinstance(modality, Modality):
+            raise ValueError(f"set_input_modality takes a modality.Modality or None, got {type(modality).__name__}")
+        table = None if modality is None or modality.table is None else modality.table.to(self._seed_state.device)
+        self.input_modality = modality
+        self.register_buffer("_modality_parents", table, persistent=False)
+        return self
+
+    def _input_view(self, x, pad_value=None):
+        """the model's input site: x (B, T, J, C) fp32 contiguous as the caller gave it -> what the first kernel reads"""
+        m = getattr(self, "input_modality", None)                 # a model unpickled from before the field existed has none
+        return x if m is None else m.apply(x, self._buffers.get("_modality_parents"), pad_value)
 
     def _classify(self, linear, feat):
         """the model's last layer.  With `hip_head` set, an nn.Linear whose width the head kernels take

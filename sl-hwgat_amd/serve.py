@@ -67,7 +67,11 @@ class GraphedEval:
             self._forward()
         # the derived weight copies the captured launches read and rewrite: referenced here so that a later eager forward,
         # which may replace the model's cache entry, cannot hand their memory back to the allocator under the graph
+        # (of the model itself and, for a model made of models -- ensemble.Ensemble --, of every module below it)
         self._preps = dict(model.__dict__.get("_weight_prep_cache", {}))
+        for name, sub in model.named_modules():
+            if sub is not model and "_weight_prep_cache" in sub.__dict__:
+                self._preps.update({(name,) + key: wp for key, wp in sub.__dict__["_weight_prep_cache"].items()})
         self._captured = self._addresses()
 
     def _forward(self):
@@ -81,7 +85,10 @@ class GraphedEval:
     def _addresses(self):
         """addresses of everything the captured launches take by pointer from the model"""
         m = self.model
-        sig = HF.WeightPrep.signature(m.block_list(), m.activation_dtype, False)[2] if hasattr(m, "block_list") else ()
+        sig = ()
+        for sub in m.modules():                               # the model itself first; an ensemble's members after it
+            if hasattr(sub, "block_list"):
+                sig += HF.WeightPrep.signature(sub.block_list(), sub.activation_dtype, False)[2]
         rest = tuple(t.data_ptr() for t in list(m.parameters()) + list(m.buffers()))
         return sig, rest
 
@@ -149,8 +156,8 @@ class StreamRecognizer:
             for ev in rec.poll()["events"]:
                 print(ev.stream, ev.cls, ev.conf)
 
-    `model` is any of the seven models taking (B, T, K, C) in eval(); T = `model.temporal_dim` is the clip length the window
-    is resampled to.  `out_joints=None` hands the model the raw joints (HWGATE with `use_part_table(part_table(29))`); a
+    `model` is any of the seven models taking (B, T, K, C) in eval(), or an ensemble.Ensemble of them; T =
+    `model.temporal_dim` is the clip length the window is resampled to.  `out_joints=None` hands the model the raw joints (HWGATE with `use_part_table(part_table(29))`); a
     gather table hands it that layout.  A stream is ready once it holds `min_frames` frames and a frame whose origin and
     anchor joints are non-zero (with anchors a positive finite distance apart); a stream that is not ready gets a benign
     input row and its decision state does not move.  `alpha`, `threshold`, `hold`, `blank_class` live in device words

@@ -1219,8 +1219,9 @@ class EpochLoop:
 
     `resume(path)` loads a checkpoint of this loop (checkpoint.load_checkpoint): weights, optimizer, scheduler, the four
     lists, `start_epoch = epoch + 1`, best values from the lists; and from the file's 'extra' key the guard's, the
-    averager's, the meter's, the mixer's and the distiller's state and the model's dropout counter, so dropout masks and the mixer's draws
-    go on where they stopped.  Torch's
+    averager's, the meter's, the mixer's and the distiller's state, the model's dropout counter and its input modality
+    (which must be the model's current one: `resume` refuses another), so dropout masks and the mixer's draws go on where
+    they stopped.  Torch's
     device generator state is NOT carried: it draws HWGATE's train-mode window thresholds (HWGATE.py:96), so a resumed
     HWGATE run draws other thresholds than the uninterrupted one would have."""
 
@@ -1335,6 +1336,9 @@ class EpochLoop:
             extra["mixer"] = self.mixer.state_dict()
         if self.distiller is not None:
             extra["distiller"] = self.distiller.state_dict()
+        modality = getattr(self.model, "input_modality", None)
+        if modality is not None:                                   # without one the entry is absent, as it always was
+            extra["modality"] = modality.state()
         return extra
 
     def _save(self, suffix, epoch):
@@ -1351,8 +1355,13 @@ class EpochLoop:
         import importlib
         checkpoint = importlib.import_module(__package__ + ".checkpoint")
         dev = self._device()
-        _, _, _, lists, start = checkpoint.load_checkpoint(path, self.model, self.opt, self.scheduler, device=dev)
         extra = checkpoint.read_extra(path, device=dev)
+        modality = getattr(self.model, "input_modality", None)
+        have, want = extra.get("modality"), None if modality is None else modality.state()
+        if have != want:                                          # before anything is loaded: a refusal changes nothing
+            raise ValueError(f"{path} was trained on the input modality {have}, the model reads {want}: set the model's "
+                             "input_modality to the checkpoint's (modality.Modality.from_state) before resuming")
+        _, _, _, lists, start = checkpoint.load_checkpoint(path, self.model, self.opt, self.scheduler, device=dev)
         guard, averager = _guard_of(self.opt), getattr(self.opt, "averager", None)
         if guard is not None and extra.get("guard") is not None:
             guard.load_state_dict(extra["guard"])
