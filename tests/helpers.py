@@ -7,6 +7,9 @@ import torch
 from oracle import hwgat_oracle as O
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# every stage width models/HWGATE.py::width_problem accepts (test_width_cpu.py holds the rule to exactly this list; the
+# GPU width tests run the LayerNorm family at every entry)
+ALL_WIDTHS = list(range(64, 1025, 64))
 
 
 def load_fixture(name):
@@ -200,6 +203,34 @@ def tie_free_threshold(p0, nominal, span=1.25):
     ratio = edges[1:] / edges[:-1]
     i = int(ratio.argmax())
     return float((edges[i] * edges[i + 1]).sqrt()), float(ratio[i].sqrt() - 1.0)
+
+
+def oracle_tie_free_thresholds(params, x, nominal, **oracle_kw):
+    """One train-mode threshold per block of a whole HWGATE model, near `nominal[block]`, each at the centre of the widest
+    gap of that block's own unmasked probabilities (tie_free_threshold) in the fp64 oracle.  Chosen block by block in
+    execution order, so that a block sees the activations the earlier choices produce.  `oracle_kw`: OracleHWGAT's
+    keywords (num_kps, temporal_dim, depths, num_heads, adj).  Returns (thresholds, smallest margin).
+    Why: with ~10^6 probabilities per block a fixed threshold has one within ~10^-6 of it, which is inside what fp32
+    rounding (the Fourier embedding's sin / cos of arguments of ~100 rad alone carry ~10^-5) moves a probability by; a
+    flipped entry of weight ~0.3 moves a clip's logits by ~10^-3."""
+    inner, chosen, margins = O.window_attention, [], []
+
+    def choosing(q, k, v, adj, smask=None, thr=None, attn_keep=None):
+        p0 = torch.softmax((q.detach() * q.shape[-1] ** -0.5) @ k.detach().transpose(-2, -1), dim=-1)
+        t, _ = tie_free_threshold(p0, thr)
+        t = float(np.float32(t))                        # thresholds travel as float32 (fixtures, threshold_override)
+        chosen.append(t)
+        margins.append(float((p0 / t - 1.0).abs().min()))
+        return inner(q, k, v, adj, smask, t, attn_keep)
+
+    O.window_attention = choosing
+    try:
+        with torch.no_grad():
+            oracle = O.OracleHWGAT({k: v.double() for k, v in params.items()}, **oracle_kw)
+            oracle.forward(x.double(), thresholds=list(nominal))
+    finally:
+        O.window_attention = inner
+    return chosen, min(margins)
 
 
 BF16_SELECTOR_BAND = 2.0 ** -6

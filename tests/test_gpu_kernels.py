@@ -80,6 +80,19 @@ def test_mfma_operand_layout():
 @pytest.mark.parametrize("shifted", [False, True])
 @pytest.mark.parametrize("thr", [None, 0.07, 0.0005, 0.9999])
 def test_window_attention_fwd_bwd(hd, nH, nW, F, B, shifted, thr):
+    _window_attention_fwd_bwd(hd, nH, nW, F, B, shifted, thr)
+
+
+# the head counts of stage widths 320 (5 x 64), 960 (15 x 64) and 960 with head_dim 32 (30 x 32): odd head counts, and a
+# grid of heads no power-of-two width asks for
+@pytest.mark.parametrize("hd,nH,nW,F,B", [(64, 5, 2, 4, 1), (64, 15, 1, 4, 1), (32, 30, 1, 4, 1)])
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("thr", [None, 0.07])
+def test_window_attention_fwd_bwd_at_the_head_counts_of_odd_widths(hd, nH, nW, F, B, shifted, thr):
+    _window_attention_fwd_bwd(hd, nH, nW, F, B, shifted, thr)
+
+
+def _window_attention_fwd_bwd(hd, nH, nW, F, B, shifted, thr):
     g = torch.Generator().manual_seed(hd + nW + F)
     d, K = nH * hd, nW * 16
     qkv = torch.randn(B, F, K, 3 * d, generator=g) * 0.8

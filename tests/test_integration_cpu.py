@@ -59,17 +59,36 @@ def load_model(cfg):                                                            
     return model
 
 
-@pytest.mark.parametrize("name,cls", [("HWGATE_AMD", "Model"), ("HGATE_AMD", "HGATEModel"), ("WGATE_AMD", "WGATEModel")])
-def test_backend_resolves_by_file_name_like_the_reference(scratch_tree, name, cls):
+# (shim file, the package's model class, its params class, the state_dict key of the classifier's weight); the four
+# graph-attention models share HWGATE's attributes and state_dict layout, the three baselines have their own
+SHIMS_TABLE = [("HWGATE_AMD", "Model", "HWGATEParams", "head.weight"),
+               ("HGATE_AMD", "HGATEModel", "HGATEParams", "head.weight"),
+               ("WGATE_AMD", "WGATEModel", "WGATEParams", "head.weight"),
+               ("GATE_AMD", "GATEModel", "GATEParams", "head.weight"),
+               ("Transformer_AMD", "TransformerModel", "TransformerParams", "classifier.weight"),
+               ("STGCN_AMD", "STGCNModel", "STGCNParams", "head.classifier.weight"),
+               ("DecoupledGCN_AMD", "DecoupledGCNModel", "DecoupledGCNParams", "head.classifier.weight")]
+
+
+def test_every_shipped_shim_is_in_the_table():
+    shipped = sorted(n[:-3] for n in os.listdir(SHIMS) if n.endswith("_AMD.py"))
+    assert shipped == sorted(row[0] for row in SHIMS_TABLE)
+
+
+@pytest.mark.parametrize("name,cls,params,head", SHIMS_TABLE, ids=[f"{row[0]}-{row[1]}" for row in SHIMS_TABLE])
+def test_backend_resolves_by_file_name_like_the_reference(scratch_tree, name, cls, params, head):
     hw = importlib.import_module("sl-hwgat_amd")
     cfg = _Cfg(name, "INCLUDE")
-    assert type(cfg.model_params) is getattr(hw, cls.replace("Model", "") + "Params" if cls != "Model" else "HWGATEParams")
+    assert type(cfg.model_params) is getattr(hw, params)
     model = load_model(cfg)
     assert type(model) is getattr(hw, cls)
-    assert model.num_classes == 262 and model.temporal_dim == 64
     assert isinstance(model, torch.nn.Module) and sum(p.numel() for p in model.parameters() if p.requires_grad) > 1e6
     # what utils.train needs next: parameters() for AdamW (utils.py:76), state_dict() for checkpoints (utils.py:166)
-    assert "B" in model.state_dict() and any(k.endswith("attn.qkv.weight") for k in model.state_dict())
+    sd = model.state_dict()
+    assert sd[head].shape[0] == 262                              # dataset_params["INCLUDE"]["num_class"] reached the classifier
+    if cls.endswith("GATEModel") or cls == "Model":
+        assert model.num_classes == 262 and model.temporal_dim == 64
+        assert "B" in sd and any(k.endswith("attn.qkv.weight") for k in sd)
 
 
 def test_shims_work_in_place_without_the_environment_variable(monkeypatch):
